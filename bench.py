@@ -1,6 +1,13 @@
 """Horn-Schunck throughput bench (BASELINE.json metric: Mpix*iter/s + pairs/s).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1080p|4k|8k]
+                    [--dump-outputs DIR] [--full]
+
+A plain run is the headline leg alone: it generates the pairs, captures the
+solve, warms up, times K steps, writes rank 0's (u, v) of the last timed step
+with --dump-outputs (DIR/u.npy, DIR/v.npy, float32: whole, or above 64 MB the
+same seeded sample of elements from run to run) and prints the line.  --full
+adds every check, leg and baseline listed below.
 
 One step = one full solve (K1 gradients + `iters` Jacobi iterations, the
 reference's getFlow, hornSchunck.cpp:43-75) of a batch of synthetic frame
@@ -17,9 +24,10 @@ environment) and N > 1, bench.py starts N rank processes itself
 (torch.distributed.run, 127.0.0.1) and exits with their status; under a
 launcher whose WORLD_SIZE differs from N it refuses to run (status 2).
 
-Rank 0 prints ONE JSON line.  Every timed output is checked: before the
-timed steps the output planes are filled with NaN, so a pass only if the
-timed replays themselves computed (u, v); a parity miss anywhere exits 3.
+Rank 0 prints ONE JSON line.  Before the timed steps the output planes are
+filled with NaN, so what is dumped or checked is what the timed replays
+themselves computed.  With --full every timed output is checked, and a
+parity miss anywhere exits 3; the line then also carries:
   parity        pair 0 of the TIMED solve (seed 1000) against the float64
                 oracle's golden checksums (tests/golden/bench_golden.*,
                 made by tests/golden/make_bench_golden.py): max|du|/max|u| on
@@ -142,6 +150,15 @@ def parse(argv=None):
     ap.add_argument("--levels", type=int, default=0,
                     help="pyramid levels (default: the workload's; 1 = plain getFlow)")
     ap.add_argument("--kb", type=int, default=0, help="iterations per K2 launch (0 auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, also run and check everything else the "
+                         "line can carry: parity, roofline, the other BASELINE configs, "
+                         "e2e, stream, bands, host API and the CPU baselines (the --no-* "
+                         "flags below trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="resident mode: write rank 0's (u, v) of the last timed step to "
+                         "DIR/u.npy and DIR/v.npy (float32; whole if both fit 64 MB, else "
+                         "the same seeded sample of elements of each)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=0,
                     help="Jacobi iterations of the CPU sample (0: auto ~15 s)")
@@ -149,19 +166,19 @@ def parse(argv=None):
     ap.add_argument("--no-graph", action="store_true",
                     help="time eager solves instead of hipGraph replays of one solve")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the configs[2] (4K) block of the default run")
+                    help="skip the configs[2] (4K) block of the default --full run")
     ap.add_argument("--no-w3", action="store_true",
-                    help="skip the window-3 block of the default run (SURVEY §8d)")
+                    help="skip the window-3 block of the default --full run (SURVEY §8d)")
     ap.add_argument("--no-8k", action="store_true",
-                    help="skip the configs[4] (8K pyramid) block of the default run")
+                    help="skip the configs[4] (8K pyramid) block of the default --full run")
     ap.add_argument("--no-single", action="store_true",
-                    help="skip the single-pair blocks of the default run")
+                    help="skip the single-pair blocks of the default --full run")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end pairs/s leg")
     ap.add_argument("--no-stream", action="store_true", help="skip the config-4 stream leg")
     ap.add_argument("--no-bands", action="store_true",
-                    help="skip the config-5 row-band leg of the default run")
+                    help="skip the config-5 row-band leg of the default --full run")
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the host-buffer getFlow leg of the default run")
+                    help="skip the host-buffer getFlow leg of the default --full run")
     ap.add_argument("--mode", choices=["resident", "stream", "bands"], default="resident",
                     help="resident: pairs generated on each rank, already in HBM "
                          "(the metric, plus the secondary / e2e / stream legs); stream: "
@@ -184,7 +201,11 @@ def parse(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, check they see each other (gloo all-reduce), "
                          "print n_gpus and exit: the launcher plumbing alone, no GPU work")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.mode != "resident":
+        ap.error("--dump-outputs writes the resident leg's (u, v): not with --mode "
+                 + args.mode)
+    return args
 
 
 # --------------------------------------------------------------- guards
@@ -485,12 +506,38 @@ def roofline_leg(wl_name, hsflow, dev, I0, I1, rows, cols, batch, window, iters,
     return roof
 
 
+# --------------------------------------------------------------- outputs
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, planes):
+    """--dump-outputs: each of `planes` (name -> device tensor, all of one
+    shape) as out_dir/<name>.npy, float32.  Whole when together they fit
+    DUMP_MAX_BYTES; otherwise the same sorted sample of flat element indices
+    of each, drawn without replacement from a fixed seed, so two builds
+    given the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(planes.values())).numel()
+    per_plane = DUMP_MAX_BYTES // (4 * len(planes))
+    idx = None
+    if n > per_plane:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=per_plane // 2,
+                                                               replace=False))
+    for name, t in planes.items():
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if idx is None else a.reshape(-1)[idx])
+
+
 # --------------------------------------------------------------- resident
 def resident_leg(wl_name, args, dev, world, rank, init_dist=None, window=None, batch=None,
-                 keep=False, roofline=True):
+                 keep=False, roofline=True, check=True, dump=None):
     """One workload, inputs resident in HBM: a step is one full solve of
     `batch` pairs per rank (hipGraph replay).  Returns the leg's dict (and,
-    with keep, rank 0's timed (u, v) for cross-checks)."""
+    with keep, rank 0's timed (u, v) for cross-checks).  roofline and check
+    (the parity of the timed output against the golden) are the --full
+    extras of the headline leg; dump: rank 0 writes the timed (u, v) there."""
     import numpy as np
     import torch
     import hsflow
@@ -576,10 +623,12 @@ def resident_leg(wl_name, args, dev, world, rank, init_dist=None, window=None, b
 
     # parity of the timed output: pair 0 of rank 0 is seed 1000
     parity = None
-    if rank == 0:
+    if rank == 0 and check:
         golden = golden_entry(rows, cols, iters, window, levels, alpha)
         parity = parity_check(u[0].cpu().numpy(), v[0].cpu().numpy(), golden)
         parity["outputs_nan_filled_before_timing"] = True
+    if rank == 0 and dump:
+        dump_outputs(dump, {"u": u, "v": v})
     kept = (u.clone(), v.clone()) if (keep and rank == 0) else None
 
     px_all = sum(r * c for r, c in (hsflow.pyramid_level_size(rows, cols, l)
@@ -605,7 +654,9 @@ def resident_leg(wl_name, args, dev, world, rank, init_dist=None, window=None, b
            "value": round(value, 1), "unit": "Mpix*iter/s",
            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
            "pairs_per_s_resident": round(total_pairs / elapsed, 2),
-           "step": step_kind, "untimed_prewarm": warm, "roofline": roof, "parity": parity}
+           "step": step_kind, "untimed_prewarm": warm, "roofline": roof, "parity": parity,
+           "iters_per_launch": hsflow.iters_per_launch(rows, cols, batch, window),
+           "kernel": hsflow.jacobi_kernel_name(rows, cols, batch, window)}
     del I0, I1, ws, pws
     torch.cuda.empty_cache()
     if keep:
@@ -1052,9 +1103,14 @@ def main():
                    not args.dtype)
     if args.kb:
         hsflow.set_iters_per_launch(args.kb)
+    # a plain run is the headline leg alone: set up, warm up, time the steps,
+    # dump, print; every other leg, check and baseline waits for --full
+    full = args.full
+    default_run = default_run and full
     keep = default_run and not args.no_stream
     progress(f"resident {args.workload}", rank)
-    prim = resident_leg(args.workload, args, dev, world, rank, init_dist, keep=keep)
+    prim = resident_leg(args.workload, args, dev, world, rank, init_dist, keep=keep,
+                        roofline=full, check=full, dump=args.dump_outputs)
     resident_ref = None
     if keep:
         prim, resident_ref = prim
@@ -1075,9 +1131,9 @@ def main():
         for wl in ("1080p", "4k"):
             progress(f"single pair {wl}", rank)
             singles[wl] = resident_leg(wl, args, dev, world, rank, batch=1)
-    stream_peak = hbm_stream_peak(dev) if rank == 0 else None
+    stream_peak = hbm_stream_peak(dev) if (full and rank == 0) else None
     e2e = None
-    if not args.no_e2e and args.workload != "8k" and rank == 0:
+    if full and not args.no_e2e and args.workload != "8k" and rank == 0:
         e2e = e2e_leg(args.workload, args, dev)
     strm = None
     if default_run and not args.no_stream:
@@ -1098,7 +1154,7 @@ def main():
     c1 = config1_leg(dev) if (default_run and rank == 0) else None
     host_api = host_api_leg() if (default_run and rank == 0 and not args.no_host_api) else None
     cpu = cpu_all = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         progress("cpu baseline", rank)
         # on every line, N > 1 included: the host-core figure the GPU counts
         # are read against (north_star)
@@ -1146,8 +1202,11 @@ def main():
             "cpu_baseline_all_cores": cpu_all,
         }
         line["config"]["parallelism"] = f"frame-parallel x{world}"
-        line["config"]["iters_per_launch"] = prim["roofline"]["iters_per_launch"]
-        line["config"]["kernel"] = prim["roofline"]["kernel"]
+        line["config"]["iters_per_launch"] = prim["iters_per_launch"]
+        line["config"]["kernel"] = prim["kernel"]
+        line["full"] = full
+        if args.dump_outputs:
+            line["outputs_dumped_to"] = args.dump_outputs
         if e2e is not None:
             line.update(e2e)
         keys = ("workload", "value", "unit", "ms_per_step", "pairs_per_s_resident", "roofline",
@@ -1182,8 +1241,9 @@ def main():
             ps = [l["parity"] for l in ls if l is not None and l.get("parity") is not None]
             oks = [p["ok"] for p in ps if p.get("ok") is not None]
             verdict[name] = (all(oks) if oks else None)
-        line["parity_all"] = {"ok": all(v is not False for v in verdict.values()),
-                              "configs": verdict}
+        if full:
+            line["parity_all"] = {"ok": all(v is not False for v in verdict.values()),
+                                  "configs": verdict}
         print(json.dumps(line), flush=True)
         for leg in (prim, sec, w3, c5, c1, strm, bands, *singles.values(), *ha.values()):
             if leg is not None and leg.get("parity") is not None and \

@@ -4,18 +4,18 @@
 # line) with N ranks (default 2; 4 gives the 2 x 2 block grid, corners
 # included) sharing the box's one GPU over gloo.  Not a scaling measurement:
 # the ranks share a device.  The legs without communication are skipped (the
-# default run covers them at N = 1).
+# --full run covers them at N = 1).  Output under $OUT_DIR (default bench_out/).
 #   bash scripts/bench_ranks_rehearsal.sh [N]
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+cd "$(dirname "$0")/.."
+OUT="${OUT_DIR:-bench_out}"; mkdir -p "$OUT"
 N=${1:-2}
 HSFLOW_BENCH_BACKEND=gloo HSFLOW_BENCH_DEVICE=0 timeout -k 10 400 \
   python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-  --master-port $((29510 + N)) bench.py --gpus "$N" --steps 3 --warmup 1 --no-cpu-baseline \
+  --master-port $((29510 + N)) bench.py --full --gpus "$N" --steps 3 --warmup 1 --no-cpu-baseline \
   --no-secondary --no-w3 --no-8k --no-single --no-e2e --no-host-api \
-  > gpurun_out/ranks$N.out 2> gpurun_out/ranks$N.err
+  > "$OUT/ranks$N.out" 2> "$OUT/ranks$N.err"
 rc=$?
-grep '^{' gpurun_out/ranks$N.out
-tail -3 gpurun_out/ranks$N.err
+grep '^{' "$OUT/ranks$N.out"
+tail -3 "$OUT/ranks$N.err"
 exit $rc

@@ -1,9 +1,11 @@
 """Does the kernel trace of a bench run account for its ms_per_step?
 
-    rocprofv3 --kernel-trace --stats -d gpurun_out/bench_trace -o run \
-        --output-format csv -- python3 bench.py --no-secondary --no-w3 --no-8k \
-        --no-single --no-e2e --no-stream --no-cpu-baseline --no-bands --no-host-api > gpurun_out/bench_trace.json
-    python scripts/trace_fit.py gpurun_out/bench_trace gpurun_out/bench_trace.json
+    rocprofv3 --kernel-trace --stats -d OUT/bench_trace -o run \
+        --output-format csv -- python3 bench.py --full --no-secondary --no-w3 --no-8k \
+        --no-single --no-e2e --no-stream --no-cpu-baseline --no-bands --no-host-api > OUT/bench_trace.json
+    python scripts/trace_fit.py OUT/bench_trace OUT/bench_trace.json
+
+(--full: the roofline leg's launches are the landmark the trace is split at.)
 
 The primary leg runs: one eager solve, a capture (no kernels execute), W
 warm-up replays, K timed replays, then the roofline leg (K1 once, then

@@ -1,6 +1,7 @@
-"""bench.py keeps the driver's contract: one JSON line with the metric fields,
-a `roofline` object and a `cpu_baseline` object (the float64 port of
-hornSchunck.cpp on a bounded sample)."""
+"""bench.py keeps the driver's contract: one JSON line with the metric fields;
+with --full also a `roofline` object and a `cpu_baseline` object (the float64
+port of hornSchunck.cpp on a bounded sample).  A plain run is the headline leg
+alone and can write its timed outputs (--dump-outputs)."""
 import json
 import os
 import subprocess
@@ -27,7 +28,7 @@ def test_cpu_baseline_leg_shape():
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1",
                           "--warmup", "1", "--iters", "24", "--roofline-reps", "1",
                           "--cpu-iters", "1"], capture_output=True, text=True, timeout=600,
                          cwd=ROOT)
@@ -47,6 +48,82 @@ def test_bench_prints_one_contract_line():
     assert "workload" in d["config"]
     # the timed output was checked after NaN-filling it before the steps
     assert d["parity"]["outputs_nan_filled_before_timing"] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_leg_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full: the contract fields, --steps timed steps, no other leg,
+    check or baseline; --dump-outputs writes the timed (u, v) of every pair
+    (8 x 1080 x 1920 f32 each: a seeded sample, 64 MB at most in all)."""
+    import numpy as np
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                          "--steps", "3", "--warmup", "1", "--iters", "24",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True,
+                         timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert REQUIRED <= set(d)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "Mpix*iter/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    # value and ms_per_step describe the same timed steps
+    px_iter = 8 * 1080 * 1920 * 24
+    # (the line rounds ms_per_step to 1e-3 ms and value to 0.1)
+    tol = (0.0005 / d["ms_per_step"] + 1e-4) * d["value"] + 0.05
+    assert abs(d["value"] - px_iter / d["ms_per_step"] / 1e3) <= tol
+    assert d["config"]["kernel"] in ("hs_jacobi_strip_kernel", "hs_jacobi_wg_kernel")
+    assert d["full"] is False
+    assert d["roofline"] is None and d["parity"] is None and d["cpu_baseline"] is None
+    for leg in ("secondary", "config5", "single_pair", "window3", "stream", "bands", "host_api",
+                "config1", "pairs_per_s_e2e", "torch_copy_gbps", "parity_all"):
+        assert leg not in d, leg
+    files = sorted(os.listdir(dump))
+    assert files == ["u.npy", "v.npy"]
+    u, v = (np.load(dump / f) for f in files)
+    assert u.dtype == v.dtype == np.float32 and u.shape == v.shape and u.size > 0
+    assert u.nbytes + v.nbytes <= 64 << 20
+    # the planes held NaN when the timed steps began
+    assert np.isfinite(u).all() and np.isfinite(v).all() and float(np.abs(u).max()) > 0
+
+
+def test_dump_outputs_whole_or_the_same_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy per plane; whole when the planes fit
+    the byte limit, else the same sorted, seeded sample of elements of each,
+    identical from call to call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(7)
+    u = torch.rand((3, 37, 53), generator=g)
+    v = torch.rand((3, 37, 53), generator=g, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"u": u, "v": v})
+    a_u, a_v = np.load(tmp_path / "a" / "u.npy"), np.load(tmp_path / "a" / "v.npy")
+    assert a_u.dtype == a_v.dtype == np.float32 and a_u.shape == (3, 37, 53)
+    assert np.array_equal(a_u, u.numpy()) and np.array_equal(a_v, v.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 4 * 1000)   # 1000 elements per plane
+    bench.dump_outputs(str(tmp_path / "b"), {"u": u, "v": v})
+    bench.dump_outputs(str(tmp_path / "c"), {"u": u, "v": v})
+    b_u, b_v = np.load(tmp_path / "b" / "u.npy"), np.load(tmp_path / "b" / "v.npy")
+    assert b_u.dtype == np.float32 and b_u.shape == b_v.shape == (500,)
+    assert b_u.nbytes + b_v.nbytes <= 2 * 4 * 1000
+    assert np.array_equal(b_u, np.load(tmp_path / "c" / "u.npy"))
+    assert np.array_equal(b_v, np.load(tmp_path / "c" / "v.npy"))
+    # the sample is elements of the planes, the same positions in each
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(u.numel(), 500, replace=False))
+    assert np.array_equal(b_u, u.numpy().reshape(-1)[idx])
+    assert np.array_equal(b_v, v.numpy().astype(np.float32).reshape(-1)[idx])
+
+
+def test_dump_outputs_is_refused_outside_resident_mode():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "bands",
+                          "--dump-outputs", "unused"], cwd=ROOT, capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 2 and "--dump-outputs" in out.stderr
+    assert not os.path.exists(os.path.join(ROOT, "unused"))
 
 
 def test_bench_refuses_diagnostic_environment():
