@@ -568,9 +568,10 @@ PyrLayout pyr_layout(int rows, int cols, int batch, int levels) {
     return L;
 }
 
-int pyramid_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
-                 int cols, int batch, int levels, int window, int iters, float alpha,
-                 float *u, float *v, void *ws, size_t ws_bytes, hipStream_t s) {
+// Arguments of a pyramid solve (plain or warped), checked before any device work.
+int check_pyramid_args(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                       int cols, int batch, int levels, const float *u, const float *v,
+                       const void *ws, size_t ws_bytes) {
     if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
         return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
                     HSFLOW_MAX_LEVELS);
@@ -580,30 +581,46 @@ int pyramid_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
         return fail(ctx, HSFLOW_ERR_ARG, "device input dtype must be U8, F16, F32 or F64");
     if (!I0 || !I1 || !u || !v || !ws)
         return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    const size_t need = pyr_layout(rows, cols, batch, levels).bytes;
+    if (ws_bytes < need)
+        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, need);
+    return HSFLOW_OK;
+}
+
+// Levels 1..levels-1 of both frames into the workspace (layout L).
+int build_levels(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                 int cols, int batch, const PyrLayout &L, void *ws, hipStream_t s) {
+    if (L.levels <= 1) return HSFLOW_OK;
+    char *base = (char *)ws;
+    // integrality of each pair (K1's flag at level 0) decides the rounding
+    // of every level; saved because each level's K1 rewrites the flags
+    int rc = gradients_impl(ctx, I0, I1, dtype_in, rows, cols, batch, nullptr, nullptr,
+                            nullptr, ws, L.jac_bytes, s);
+    if (rc) return rc;
+    uint32_t *intf = (uint32_t *)(base + L.flags_off);
+    HIP_TRY(ctx, hipMemcpyAsync(intf, carve(ws, rows, cols, batch).flags, (size_t)batch * 4,
+                                hipMemcpyDeviceToDevice, s));
+    for (int l = 1; l < L.levels; ++l)
+        for (int k = 0; k < 2; ++k) {
+            const void *src = l == 1 ? (k ? I1 : I0) : base + L.off[l - 1][k];
+            hipError_t e = hsflow::launch_pyrdown(
+                src, l == 1 ? dtype_in : HSFLOW_F32, L.R[l - 1], L.C[l - 1], batch,
+                (float *)(base + L.off[l][k]), intf, s);
+            if (e != hipSuccess) return hip_fail(ctx, e, "pyrdown launch");
+        }
+    return HSFLOW_OK;
+}
+
+int pyramid_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                 int cols, int batch, int levels, int window, int iters, float alpha,
+                 float *u, float *v, void *ws, size_t ws_bytes, hipStream_t s) {
+    int rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, u, v, ws,
+                                ws_bytes);
+    if (rc) return rc;
     const PyrLayout L = pyr_layout(rows, cols, batch, levels);
-    if (ws_bytes < L.bytes)
-        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, L.bytes);
     const bool maybe_f32 = dtype_in != HSFLOW_U8;
     char *base = (char *)ws;
-    int rc;
-    if (levels > 1) {
-        // integrality of each pair (K1's flag at level 0) decides the rounding
-        // of every level; saved because each level's K1 rewrites the flags
-        rc = gradients_impl(ctx, I0, I1, dtype_in, rows, cols, batch, nullptr, nullptr,
-                            nullptr, ws, L.jac_bytes, s);
-        if (rc) return rc;
-        uint32_t *intf = (uint32_t *)(base + L.flags_off);
-        HIP_TRY(ctx, hipMemcpyAsync(intf, carve(ws, rows, cols, batch).flags,
-                                    (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
-        for (int l = 1; l < levels; ++l)
-            for (int k = 0; k < 2; ++k) {
-                const void *src = l == 1 ? (k ? I1 : I0) : base + L.off[l - 1][k];
-                hipError_t e = hsflow::launch_pyrdown(
-                    src, l == 1 ? dtype_in : HSFLOW_F32, L.R[l - 1], L.C[l - 1], batch,
-                    (float *)(base + L.off[l][k]), intf, s);
-                if (e != hipSuccess) return hip_fail(ctx, e, "pyrdown launch");
-            }
-    }
+    if ((rc = build_levels(ctx, I0, I1, dtype_in, rows, cols, batch, L, ws, s))) return rc;
     for (int l = levels - 1; l >= 0; --l) {
         float *ul = l ? (float *)(base + L.off[l][2]) : u;
         float *vl = l ? (float *)(base + L.off[l][3]) : v;
@@ -622,6 +639,125 @@ int pyramid_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
         rc = jacobi_impl(ctx, L.R[l], L.C[l], batch, window, iters, alpha, warm, maybe_f32,
                          ul, vl, ws, L.jac_bytes, s);
         if (rc) return rc;
+    }
+    return HSFLOW_OK;
+}
+
+// ---- warped coarse-to-fine solve -------------------------------------------
+// KW: one level's gradients linearised around (u0, v0), into the Jacobi
+// workspace's f32 planes (flags[pair] = 1: the passes read the planes).
+int warp_gradients_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
+                        int rows, int cols, int batch, const float *u0, const float *v0,
+                        float *gx, float *gy, float *gt, void *workspace, size_t ws_bytes,
+                        hipStream_t s) {
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!device_dtype_ok(dtype_in))
+        return fail(ctx, HSFLOW_ERR_ARG, "device input dtype must be U8, F16, F32 or F64");
+    if (!I0 || !I1 || !u0 || !v0 || !workspace)
+        return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    Workspace w = carve(workspace, rows, cols, batch);
+    if (ws_bytes < w.bytes)
+        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, w.bytes);
+    hipError_t e = hsflow::launch_warp_gradients(I0, I1, dtype_in, rows, cols, batch, u0, v0,
+                                                 w.gx, w.gy, w.gt, w.flags, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "warp gradients launch");
+    const size_t n = (size_t)rows * cols * batch;
+    if (gx) HIP_TRY(ctx, hipMemcpyAsync(gx, w.gx, n * 4, hipMemcpyDeviceToDevice, s));
+    if (gy) HIP_TRY(ctx, hipMemcpyAsync(gy, w.gy, n * 4, hipMemcpyDeviceToDevice, s));
+    if (gt) HIP_TRY(ctx, hipMemcpyAsync(gt, w.gt, n * 4, hipMemcpyDeviceToDevice, s));
+    return HSFLOW_OK;
+}
+
+constexpr int kMaxWarps = 16;
+
+int check_warped_args(hsflow_ctx *ctx, int warps, int window, int iters) {
+    if (warps < 1 || warps > kMaxWarps)
+        return fail(ctx, HSFLOW_ERR_ARG, "warps %d outside [1, %d]", warps, kMaxWarps);
+    if (window < 1 || window > HSFLOW_MAX_WINDOW)
+        return fail(ctx, HSFLOW_ERR_ARG, "windowSize %d outside [1, %d]", window,
+                    HSFLOW_MAX_WINDOW);
+    if (iters < 0) return fail(ctx, HSFLOW_ERR_ARG, "maxIterations %d < 0", iters);
+    return HSFLOW_OK;
+}
+
+// The pyramid of pyramid_impl; per level, coarsest first: (u, v) = 0 or the
+// coarser result projected up, then `warps` times KW around the current
+// (u, v) and `iters` Jacobi iterations warm-started from it.
+int warped_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                int cols, int batch, int levels, int warps, int window, int iters,
+                float alpha, float *u, float *v, void *ws, size_t ws_bytes, hipStream_t s) {
+    int rc = check_warped_args(ctx, warps, window, iters);
+    if (rc) return rc;
+    rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, u, v, ws,
+                            ws_bytes);
+    if (rc) return rc;
+    const PyrLayout L = pyr_layout(rows, cols, batch, levels);
+    char *base = (char *)ws;
+    if ((rc = build_levels(ctx, I0, I1, dtype_in, rows, cols, batch, L, ws, s))) return rc;
+    for (int l = levels - 1; l >= 0; --l) {
+        float *ul = l ? (float *)(base + L.off[l][2]) : u;
+        float *vl = l ? (float *)(base + L.off[l][3]) : v;
+        const size_t n = (size_t)L.R[l] * L.C[l] * batch;
+        if (l == levels - 1) {
+            HIP_TRY(ctx, hipMemsetAsync(ul, 0, n * 4, s));
+            HIP_TRY(ctx, hipMemsetAsync(vl, 0, n * 4, s));
+        } else {
+            hipError_t e = hsflow::launch_upflow(
+                (const float *)(base + L.off[l + 1][2]), (const float *)(base + L.off[l + 1][3]),
+                L.R[l + 1], L.C[l + 1], ul, vl, L.R[l], L.C[l], batch, s);
+            if (e != hipSuccess) return hip_fail(ctx, e, "upflow launch");
+        }
+        for (int k = 0; k < warps; ++k) {
+            rc = warp_gradients_impl(ctx, l ? (const void *)(base + L.off[l][0]) : I0,
+                                     l ? (const void *)(base + L.off[l][1]) : I1,
+                                     l ? HSFLOW_F32 : dtype_in, L.R[l], L.C[l], batch, ul, vl,
+                                     nullptr, nullptr, nullptr, ws, L.jac_bytes, s);
+            if (rc) return rc;
+            // need_f32: the planes are f32 for every pair
+            rc = jacobi_impl(ctx, L.R[l], L.C[l], batch, window, iters, alpha, true, true, ul,
+                             vl, ws, L.jac_bytes, s);
+            if (rc) return rc;
+        }
+    }
+    return HSFLOW_OK;
+}
+
+// The host-buffer form of both pyramid solves: warps = 0 is hsflow_flow_pyramid,
+// warps >= 1 hsflow_flow_warped (same upload, download, f64 widening and
+// huge-page advice).
+int pyramid_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                 int cols, size_t in_step0, size_t in_step1, int levels, int warps, int window,
+                 int iters, double alpha, void *u, void *v, int dtype_out, size_t out_step) {
+    int rc = check_host_args(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1,
+                             dtype_out, out_step);
+    if (rc) return rc;
+    if (!u || !v) return fail(ctx, HSFLOW_ERR_ARG, "null output");
+    if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
+        return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
+                    HSFLOW_MAX_LEVELS);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)rows * cols;
+    const size_t in_es = (size_t)dev_elem_size(dtype_in);
+    if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * in_es) * 2))) return rc;
+    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, align_up(n * 4) * 3))) return rc;
+    const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels);
+    if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
+    char *in0 = (char *)ctx->d_in, *in1 = in0 + align_up(n * in_es);
+    float *du = (float *)ctx->d_out, *dv = (float *)((char *)du + align_up(n * 4));
+    if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
+        return rc;
+    const int dt0 = dtype_in;
+    rc = warps ? warped_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, warps, window, iters,
+                             (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream)
+               : pyramid_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, window, iters,
+                              (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
+    if (rc) return rc;
+    {
+        const float *srcs[2] = {du, dv};
+        void *dsts[2] = {u, v};
+        if ((rc = download_planes(ctx, srcs, dsts, 2, rows, cols, dtype_out, out_step)))
+            return rc;
     }
     return HSFLOW_OK;
 }
@@ -1000,35 +1136,37 @@ int hsflow_flow_pyramid(hsflow_ctx *ctx, const void *I0, const void *I1, int dty
                         int rows, int cols, size_t in_step0, size_t in_step1, int levels,
                         int window, int iters, double alpha, void *u, void *v,
                         int dtype_out, size_t out_step) {
-    int rc = check_host_args(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1,
-                             dtype_out, out_step);
+    return pyramid_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, 0,
+                        window, iters, alpha, u, v, dtype_out, out_step);
+}
+
+int hsflow_warp_gradients_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                 int cols, int batch, const float *u0, const float *v0,
+                                 float *gx, float *gy, float *gt, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return warp_gradients_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, u0, v0, gx, gy,
+                               gt, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_warped_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                              int batch, int levels, int warps, int window, int iters,
+                              float alpha, float *u, float *v, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return warped_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, window,
+                       iters, alpha, u, v, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_warped(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                       int cols, size_t in_step0, size_t in_step1, int levels, int warps,
+                       int window, int iters, double alpha, void *u, void *v, int dtype_out,
+                       size_t out_step) {
+    if (!ctx) return HSFLOW_ERR_ARG;
+    int rc = check_warped_args(ctx, warps, window, iters);
     if (rc) return rc;
-    if (!u || !v) return fail(ctx, HSFLOW_ERR_ARG, "null output");
-    if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
-        return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
-                    HSFLOW_MAX_LEVELS);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)rows * cols;
-    const size_t in_es = (size_t)dev_elem_size(dtype_in);
-    if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * in_es) * 2))) return rc;
-    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, align_up(n * 4) * 3))) return rc;
-    const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels);
-    if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
-    char *in0 = (char *)ctx->d_in, *in1 = in0 + align_up(n * in_es);
-    float *du = (float *)ctx->d_out, *dv = (float *)((char *)du + align_up(n * 4));
-    if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
-        return rc;
-    const int dt0 = dtype_in;
-    rc = pyramid_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, window, iters,
-                      (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
-    if (rc) return rc;
-    {
-        const float *srcs[2] = {du, dv};
-        void *dsts[2] = {u, v};
-        if ((rc = download_planes(ctx, srcs, dsts, 2, rows, cols, dtype_out, out_step)))
-            return rc;
-    }
-    return HSFLOW_OK;
+    return pyramid_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
+                        window, iters, alpha, u, v, dtype_out, out_step);
 }
 
 int hsflow_bgr_to_gray_device(const uint8_t *bgr, int rows, int cols, int batch,

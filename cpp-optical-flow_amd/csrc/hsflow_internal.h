@@ -40,6 +40,13 @@ hipError_t launch_bgr2gray(const uint8_t *bgr, int rows, int cols, int batch,
                            uint8_t *gray, hipStream_t s);
 hipError_t launch_upflow(const float *uc, const float *vc, int rc, int cc, float *u,
                          float *v, int rows, int cols, int batch, hipStream_t s);
+// KW (hsflow_warp.hip): one level's gradients linearised around (u0, v0) into
+// the f32 planes -- gx, gy as K1's, gt' = (I1 warped by 8 (u0, v0)) - I0 -
+// gx u0 - gy v0 -- and flags[pair] = 1 (the Jacobi passes read the planes)
+hipError_t launch_warp_gradients(const void *I0, const void *I1, int dtype_in, int rows,
+                                 int cols, int batch, const float *u0, const float *v0,
+                                 float *gx, float *gy, float *gt, uint32_t *flags,
+                                 hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

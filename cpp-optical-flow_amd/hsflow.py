@@ -39,6 +39,11 @@ HSFLOW_ERR_NODEV = -4
 HSFLOW_ERR_SIZE = -5
 U8, F32, F64, F16 = 0, 1, 2, 3
 MAX_LEVELS = 8
+MAX_WARPS = 16
+SOBEL_GAIN = 8.0
+"""Pixels of displacement per unit of (u, v): the reference's Ix, Iy are
+unnormalised 3x3 Sobel sums (hornSchunck.cpp:27-28, gain 8), so multiply
+(u, v) by SOBEL_GAIN for the motion in pixels."""
 
 # every symbol include/hsflow.h declares
 EXPORTS = (
@@ -53,7 +58,8 @@ EXPORTS = (
     "hsflow_set_jacobi_kernel", "hsflow_build_flags", "hsflow_flow_multi",
     "hsflow_download_device", "hsflow_jacobi_kernel_name", "hsflow_set_strip_rows",
     "hsflow_max_streams", "hsflow_set_output_hugepages", "hsflow_strip_seg_rows",
-    "hsflow_flow_multi_release",
+    "hsflow_flow_multi_release", "hsflow_warp_gradients_device",
+    "hsflow_flow_warped_device", "hsflow_flow_warped",
 )
 
 
@@ -128,6 +134,12 @@ def lib():
                                              ctypes.c_float, _vp, _vp, _vp, _sz, _vp]
     L.hsflow_flow_pyramid.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i,
                                       ctypes.c_double, _vp, _vp, i, _sz]
+    L.hsflow_warp_gradients_device.argtypes = [_vp, _vp, i, i, i, i, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _sz, _vp]
+    L.hsflow_flow_warped_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i,
+                                            ctypes.c_float, _vp, _vp, _vp, _sz, _vp]
+    L.hsflow_flow_warped.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i,
+                                     ctypes.c_double, _vp, _vp, i, _sz]
     L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               _vp, _sz, _vp]
@@ -268,6 +280,27 @@ class Context:
                                        _dtype_code(a), rows, cols, a.strides[0],
                                        b.strides[0], int(levels), int(window), int(iters), float(alpha),
                                        u.ctypes.data, v.ctypes.data, code, u.strides[0])
+        _check(rc, self._p)
+        return u, v
+
+    def flow_warped(self, I0, I1, levels: int, warps: int, window: int, iters: int,
+                    alpha: float, out_dtype=np.float64):
+        """Warped coarse-to-fine solve for large displacements (`warps`
+        re-linearisations per level, `iters` iterations each), see
+        hsflow_flow_warped in include/hsflow.h.  (u, v) * SOBEL_GAIN is the
+        motion in pixels."""
+        a, b = _as_image(I0), _as_image(I1)
+        if a.shape != b.shape:
+            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
+        a, b = _common_dtype(a, b)
+        rows, cols = a.shape
+        u = np.empty((rows, cols), out_dtype)
+        v = np.empty((rows, cols), out_dtype)
+        code = F64 if u.dtype == np.float64 else F32
+        rc = lib().hsflow_flow_warped(self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a),
+                                      rows, cols, a.strides[0], b.strides[0], int(levels),
+                                      int(warps), int(window), int(iters), float(alpha),
+                                      u.ctypes.data, v.ctypes.data, code, u.strides[0])
         _check(rc, self._p)
         return u, v
 
@@ -414,10 +447,18 @@ class hornSchunck:  # noqa: N801  (reference class name, hornSchunck.cpp:8)
         return uu, vv
 
 
-def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int = 1):
+def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int = 1,
+            warps: int = 0):
     """compute(I0, I1, alpha, nIter) -> (u, v): the north-star convenience
     wrapper over hornSchunck(windowSize, nIter, alpha).getFlow; levels > 1
-    runs the config-5 coarse-to-fine warm start (nIter per level)."""
+    runs the config-5 coarse-to-fine warm start (nIter per level).  warps >= 1
+    runs the warped coarse-to-fine solve instead (large displacements:
+    `warps` re-linearisations per level, nIter iterations each); warps = 0
+    keeps the behaviour above."""
+    if warps:
+        if not 1 <= int(warps) <= MAX_WARPS:
+            raise HsflowError(HSFLOW_ERR_ARG, f"warps {warps} outside [1, {MAX_WARPS}]")
+        return default_context().flow_warped(I0, I1, levels, warps, windowSize, nIter, alpha)
     if levels > 1:
         return default_context().flow_pyramid(I0, I1, levels, windowSize, nIter, alpha)
     return hornSchunck(windowSize, nIter, alpha).getFlow(I0, I1)
@@ -566,6 +607,64 @@ def flow_pyramid_device(I0, I1, levels: int, window: int, iters: int, alpha: flo
                                               workspace.numel(), _stream_ptr(stream, I0.device))
     _check(rc)
     return u, v
+
+
+def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
+                       alpha: float, u=None, v=None, workspace=None, stream=None):
+    """Warped coarse-to-fine solve on torch CUDA tensors [B, H, W] (uint8 /
+    float16 / float32 / float64): per level `warps` times the gradients
+    linearised around the current flow and `iters` Jacobi iterations.
+    `workspace`: pyramid_workspace_bytes(rows, cols, batch, levels) bytes.
+    (u, v) * SOBEL_GAIN is the motion in pixels.  Stream-ordered."""
+    rows, cols = I0.shape[-2:]
+    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
+    _check_dense(I0, (rows, cols), "I0")
+    _check_dense(I1, (rows, cols), "I1")
+    if I1.dtype != I0.dtype or I1.shape != I0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
+    if u is None:
+        u = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
+    if v is None:
+        v = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
+    _check_plane(u, (rows, cols), batch, "u")
+    _check_plane(v, (rows, cols), batch, "v")
+    if workspace is None:
+        n = pyramid_workspace_bytes(rows, cols, batch, levels)
+        workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
+    with _on(I0.device):
+        rc = lib().hsflow_flow_warped_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0),
+                                             rows, cols, batch, int(levels), int(warps),
+                                             int(window), int(iters), float(alpha),
+                                             u.data_ptr(), v.data_ptr(), workspace.data_ptr(),
+                                             workspace.numel(), _stream_ptr(stream, I0.device))
+    _check(rc)
+    return u, v
+
+
+def warp_gradients_device(I0, I1, u0, v0, workspace, gx=None, gy=None, gt=None, stream=None):
+    """Gradients linearised around the flow (u0, v0) (float32 tensors of the
+    frames' shape) into the workspace's f32 planes, optionally also into
+    gx/gy/gt; jacobi_device(warm_start=True) on (u0, v0) then runs one warp's
+    iterations.  gx, gy equal gradients_device's planes bit for bit."""
+    rows, cols = I0.shape[-2:]
+    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
+    _check_dense(I0, (rows, cols), "I0")
+    _check_dense(I1, (rows, cols), "I1")
+    if I1.dtype != I0.dtype or I1.shape != I0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
+    _check_plane(u0, (rows, cols), batch, "u0")
+    _check_plane(v0, (rows, cols), batch, "v0")
+    for t, name in ((gx, "gx"), (gy, "gy"), (gt, "gt")):
+        if t is not None:
+            _check_plane(t, (rows, cols), batch, name)
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    with _on(I0.device):
+        rc = lib().hsflow_warp_gradients_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0),
+                                                rows, cols, batch, u0.data_ptr(), v0.data_ptr(),
+                                                ptr(gx), ptr(gy), ptr(gt), workspace.data_ptr(),
+                                                workspace.numel(),
+                                                _stream_ptr(stream, I0.device))
+    _check(rc)
 
 
 def pyramid_build_device(I0, I1, levels: int, workspace=None, stream=None):

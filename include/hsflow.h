@@ -253,6 +253,53 @@ int hsflow_pyramid_build_device(const void *I0, const void *I1, int dtype_in, in
 int hsflow_upflow_device(const float *uc, const float *vc, int rc, int cc, float *u,
                          float *v, int rows, int cols, int batch, void *stream);
 
+/* ---- warped coarse-to-fine solve (large displacements) -------------------
+ * Every solve above linearises brightness constancy once, around zero flow
+ * (the pyramid's coarser result only moves the Jacobi iteration's starting
+ * point, not its fixed point), so a motion of more than about a pixel is not
+ * recovered.  The warped solve re-linearises around the current flow
+ * (u0, v0) at every level:
+ *   I1w(y, x) = I1 sampled bilinearly at (y + 8 v0, x + 8 u0)
+ *   It'       = (I1w - I0) - Ix u0 - Iy v0
+ *   the getFlow loop (hornSchunck.cpp:56-74) from (u0, v0) with It' for It.
+ * Units: Ix, Iy are the reference's unnormalised 3x3 Sobel sums (gain 8,
+ * hornSchunck.cpp:27-28), so one unit of (u, v) is 8 px: multiply (u, v) by
+ * 8 for displacements in pixels.  Each displacement is clamped to [-cols,
+ * cols] / [-rows, rows] before it is split into integer and fraction (NaN
+ * counts as the lower bound), and the four taps are clamped to the plane
+ * (border replicated); zero flow gives It' = I1 - I0 bit for bit.  Ix, Iy
+ * equal hsflow_gradients_device's planes bit for bit.
+ * The pyramid (levels, rounding) is hsflow_flow_pyramid_device's.  Per level,
+ * coarsest first: (u, v) = 0 or 2 (u, v)_coarse(y/2, x/2), then `warps`
+ * (1..16) times { gradients around (u, v); `iters` Jacobi iterations
+ * warm-started from (u, v) }.  levels = 1, warps = 1 computes what
+ * hsflow_flow_device computes (from f32 gradient planes: same values within
+ * rounding, not the same bits).  `workspace`: at least
+ * hsflow_pyramid_workspace_bytes(rows, cols, batch, levels) bytes -- the warped
+ * solve needs nothing beyond the pyramid's, so there is no size function of
+ * its own.  All arguments are checked before any device work. */
+#define HSFLOW_HAS_WARPED 1
+
+/* Gradients of one level linearised around (u0, v0) (dense f32, batch planes)
+ * into the workspace's f32 planes (hsflow_workspace_bytes(rows, cols, batch))
+ * and optionally to gx/gy/gt (may be NULL); then
+ * hsflow_jacobi_device(warm_start = 1) on (u, v) = (u0, v0) is one warp's
+ * solve.  u0/v0 may be the solve's own u/v; they must not overlap the
+ * workspace or gx/gy/gt. */
+int hsflow_warp_gradients_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                 int cols, int batch, const float *u0, const float *v0,
+                                 float *gx, float *gy, float *gt, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int hsflow_flow_warped_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                              int batch, int levels, int warps, int window, int iters,
+                              float alpha, float *u, float *v, void *workspace,
+                              size_t workspace_bytes, void *stream);
+/* Host-buffer, blocking form (same conventions as hsflow_flow_pyramid). */
+int hsflow_flow_warped(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                       int cols, size_t in_step0, size_t in_step1, int levels, int warps,
+                       int window, int iters, double alpha, void *u, void *v, int dtype_out,
+                       size_t out_step);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

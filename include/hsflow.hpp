@@ -109,6 +109,25 @@ class HornSchunck {
                     (size_t)imagePrev.cols * 8);
     }
 
+    // Warped coarse-to-fine solve for motions beyond a pixel (hsflow.h,
+    // hsflow_flow_warped): `levels` pyramid levels, per level `warps`
+    // re-linearisations around the current flow with maxIterations
+    // iterations each.  u, v as getFlow; 8 (u, v) is the motion in pixels.
+    void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
+                       int warps, std::vector<double> &u, std::vector<double> &v) {
+        check_pair(imagePrev, imageNext);
+        const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
+        u.resize(n);
+        v.resize(n);
+        std::vector<double> ha, hb;
+        const ImageView a = common_type(imagePrev, imageNext, ha);
+        const ImageView b = common_type(imageNext, imagePrev, hb);
+        Context &c = ctx();
+        c.check(hsflow_flow_warped(c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step,
+                                   b.step, levels, warps, windowSize, maxIterations, alpha,
+                                   u.data(), v.data(), HSFLOW_F64, (size_t)a.cols * 8));
+    }
+
     // Raw form for callers that own output rows (cv::Mat adapter): dtype_out
     // HSFLOW_F64 or HSFLOW_F32, out_step in bytes.  Each frame keeps its own
     // row step; frames of different element types are both widened to
