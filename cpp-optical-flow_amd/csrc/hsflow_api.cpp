@@ -723,6 +723,78 @@ int warped_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, i
     return HSFLOW_OK;
 }
 
+// ---- bidirectional warped solve + forward-backward check -------------------
+// thresholds of the check: finite and >= 0 (negated, so NaN fails)
+int check_thresholds(hsflow_ctx *ctx, float rel, float abs_thr) {
+    if (!(rel >= 0.0f && rel <= 3.0e38f) || !(abs_thr >= 0.0f && abs_thr <= 3.0e38f))
+        return fail(ctx, HSFLOW_ERR_ARG, "thresholds rel %g, abs %g must be finite and >= 0",
+                    (double)rel, (double)abs_thr);
+    return HSFLOW_OK;
+}
+
+int check_consistency_args(hsflow_ctx *ctx, const float *uf, const float *vf, const float *ub,
+                           const float *vb, int rows, int cols, int batch, float rel,
+                           float abs_thr) {
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!uf || !vf || !ub || !vb) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    return check_thresholds(ctx, rel, abs_thr);
+}
+
+// KC on checked arguments: counts zeroed stream-ordered, then one launch
+int consistency_run(hsflow_ctx *ctx, const float *uf, const float *vf, const float *ub,
+                    const float *vb, int rows, int cols, int batch, float rel, float abs_thr,
+                    float *err, uint8_t *mask, uint32_t *counts, hipStream_t s) {
+    if (counts) HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)batch * 3 * 4, s));
+    hipError_t e = hsflow::launch_consistency(uf, vf, ub, vb, rows, cols, batch, rel, abs_thr,
+                                              err, mask, counts, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "consistency launch");
+    return HSFLOW_OK;
+}
+
+int consistency_impl(hsflow_ctx *ctx, const float *uf, const float *vf, const float *ub,
+                     const float *vb, int rows, int cols, int batch, float rel, float abs_thr,
+                     float *err, uint8_t *mask, uint32_t *counts, hipStream_t s) {
+    int rc = check_consistency_args(ctx, uf, vf, ub, vb, rows, cols, batch, rel, abs_thr);
+    if (rc) return rc;
+    if (!err && !mask && !counts)
+        return fail(ctx, HSFLOW_ERR_ARG, "no output: err, mask and counts are all null");
+    return consistency_run(ctx, uf, vf, ub, vb, rows, cols, batch, rel, abs_thr, err, mask,
+                           counts, s);
+}
+
+// Both directions one after the other on the caller's stream, each the
+// warped solve itself (so the flows are hsflow_flow_warped_device's bits by
+// construction) in the one pyramid workspace, then KC per direction asked for.
+int bidir_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+               int cols, int batch, int levels, int warps, int window, int iters, float alpha,
+               float rel, float abs_thr, float *uf, float *vf, float *ub, float *vb,
+               float *err_f, uint8_t *mask_f, uint32_t *counts_f, float *err_b,
+               uint8_t *mask_b, uint32_t *counts_b, void *ws, size_t ws_bytes, hipStream_t s) {
+    int rc = check_warped_args(ctx, warps, window, iters);
+    if (rc) return rc;
+    rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, uf, vf, ws,
+                            ws_bytes);
+    if (rc) return rc;
+    if (!ub || !vb) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
+    rc = warped_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, window, iters,
+                     alpha, uf, vf, ws, ws_bytes, s);
+    if (rc) return rc;
+    rc = warped_impl(ctx, I1, I0, dtype_in, rows, cols, batch, levels, warps, window, iters,
+                     alpha, ub, vb, ws, ws_bytes, s);
+    if (rc) return rc;
+    if (err_f || mask_f || counts_f) {
+        rc = consistency_run(ctx, uf, vf, ub, vb, rows, cols, batch, rel, abs_thr, err_f,
+                             mask_f, counts_f, s);
+        if (rc) return rc;
+    }
+    if (err_b || mask_b || counts_b)
+        rc = consistency_run(ctx, ub, vb, uf, vf, rows, cols, batch, rel, abs_thr, err_b,
+                             mask_b, counts_b, s);
+    return rc;
+}
+
 // The host-buffer form of both pyramid solves: warps = 0 is hsflow_flow_pyramid,
 // warps >= 1 hsflow_flow_warped (same upload, download, f64 widening and
 // huge-page advice).
@@ -760,6 +832,65 @@ int pyramid_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
             return rc;
     }
     return HSFLOW_OK;
+}
+
+// The host-buffer form of the bidirectional solve: pyramid_host's upload and
+// download around bidir_impl; the masks and counts come down on the same
+// stream ahead of the flows, whose download drains it.
+int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+               int cols, size_t in_step0, size_t in_step1, int levels, int warps, int window,
+               int iters, double alpha, float rel, float abs_thr, void *u, void *v, void *ub,
+               void *vb, int dtype_out, size_t out_step, uint8_t *mask_f, uint8_t *mask_b,
+               size_t mask_step, uint32_t *counts) {
+    int rc = check_host_args(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1,
+                             dtype_out, out_step);
+    if (rc) return rc;
+    if (!u || !v) return fail(ctx, HSFLOW_ERR_ARG, "null output");
+    if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
+        return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
+                    HSFLOW_MAX_LEVELS);
+    if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
+    if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
+    if ((mask_f || mask_b) && mask_step < (size_t)cols)
+        return fail(ctx, HSFLOW_ERR_ARG, "mask step %zu < row bytes %d", mask_step, cols);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)rows * cols;
+    const size_t in_es = (size_t)dev_elem_size(dtype_in);
+    // d_out: uf, vf, ub, vb (f32), the two masks (u8), counts (2 x 3 words)
+    const size_t fb = align_up(n * 4), mb = align_up(n);
+    if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * in_es) * 2))) return rc;
+    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, fb * 4 + mb * 2 + kAlign))) return rc;
+    const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels);
+    if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
+    char *in0 = (char *)ctx->d_in, *in1 = in0 + align_up(n * in_es);
+    char *out = (char *)ctx->d_out;
+    float *d[4] = {(float *)out, (float *)(out + fb), (float *)(out + 2 * fb),
+                   (float *)(out + 3 * fb)};
+    uint8_t *dmf = (uint8_t *)(out + 4 * fb), *dmb = dmf + mb;
+    uint32_t *dc = (uint32_t *)(dmb + mb);
+    if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
+        return rc;
+    rc = bidir_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, window, iters,
+                    (float)alpha, rel, abs_thr, d[0], d[1], d[2], d[3], nullptr,
+                    mask_f ? dmf : nullptr, counts ? dc : nullptr, nullptr,
+                    mask_b ? dmb : nullptr, counts ? dc + 3 : nullptr, ctx->d_ws,
+                    ctx->d_ws_bytes, ctx->stream);
+    if (rc) return rc;
+    if (mask_f)
+        HIP_TRY(ctx, hipMemcpy2DAsync(mask_f, mask_step, dmf, (size_t)cols, (size_t)cols, rows,
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    if (mask_b)
+        HIP_TRY(ctx, hipMemcpy2DAsync(mask_b, mask_step, dmb, (size_t)cols, (size_t)cols, rows,
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    if (counts)
+        HIP_TRY(ctx, hipMemcpyAsync(counts, dc, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    const float *srcs[4] = {d[0], d[1], nullptr, nullptr};
+    void *dsts[4] = {u, v, nullptr, nullptr};
+    int np = 2;
+    if (ub) srcs[np] = d[2], dsts[np++] = ub;
+    if (vb) srcs[np] = d[3], dsts[np++] = vb;
+    return download_planes(ctx, srcs, dsts, np, rows, cols, dtype_out, out_step);
 }
 
 // hsflow_flow_multi's kept contexts: one per (device, slot), each behind its
@@ -1167,6 +1298,43 @@ int hsflow_flow_warped(hsflow_ctx *ctx, const void *I0, const void *I1, int dtyp
     if (rc) return rc;
     return pyramid_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
                         window, iters, alpha, u, v, dtype_out, out_step);
+}
+
+size_t hsflow_flow_bidir_workspace_bytes(int rows, int cols, int batch, int levels) {
+    // both directions run in the one pyramid workspace, one after the other
+    return hsflow_pyramid_workspace_bytes(rows, cols, batch, levels);
+}
+
+int hsflow_flow_consistency_device(const float *uf, const float *vf, const float *ub,
+                                   const float *vb, int rows, int cols, int batch, float rel,
+                                   float abs_thr, float *err, uint8_t *mask, uint32_t *counts,
+                                   void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return consistency_impl(nullptr, uf, vf, ub, vb, rows, cols, batch, rel, abs_thr, err, mask,
+                            counts, (hipStream_t)stream);
+}
+
+int hsflow_flow_bidir_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                             int batch, int levels, int warps, int window, int iters,
+                             float alpha, float rel, float abs_thr, float *uf, float *vf, float *ub,
+                             float *vb, float *err_f, uint8_t *mask_f, uint32_t *counts_f,
+                             float *err_b, uint8_t *mask_b, uint32_t *counts_b, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return bidir_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, window,
+                      iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f, err_b,
+                      mask_b, counts_b, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_bidir(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                      int cols, size_t in_step0, size_t in_step1, int levels, int warps,
+                      int window, int iters, double alpha, float rel, float abs_thr, void *u,
+                      void *v, void *ub, void *vb, int dtype_out, size_t out_step,
+                      uint8_t *mask_f, uint8_t *mask_b, size_t mask_step, uint32_t *counts) {
+    if (!ctx) return HSFLOW_ERR_ARG;
+    return bidir_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
+                      window, iters, alpha, rel, abs_thr, u, v, ub, vb, dtype_out, out_step, mask_f,
+                      mask_b, mask_step, counts);
 }
 
 int hsflow_bgr_to_gray_device(const uint8_t *bgr, int rows, int cols, int batch,

@@ -47,6 +47,14 @@ hipError_t launch_warp_gradients(const void *I0, const void *I1, int dtype_in, i
                                  int cols, int batch, const float *u0, const float *v0,
                                  float *gx, float *gy, float *gt, uint32_t *flags,
                                  hipStream_t s);
+// KC (hsflow_consistency.hip): forward-backward check of (uf, vf) against
+// (ub, vb), dense f32 batch planes -> err (f32, px), mask (u8: 0 consistent,
+// 1 inconsistent, 2 out of frame) and counts[batch][3]; each output may be
+// null.  counts must be zero before the launch (the kernel adds).
+hipError_t launch_consistency(const float *uf, const float *vf, const float *ub,
+                              const float *vb, int rows, int cols, int batch, float rel,
+                              float abs_thr, float *err, uint8_t *mask, uint32_t *counts,
+                              hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

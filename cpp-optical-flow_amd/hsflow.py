@@ -16,6 +16,7 @@ If the library is missing or no gfx950 device is present, calls raise.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import subprocess
@@ -45,6 +46,11 @@ SOBEL_GAIN = 8.0
 unnormalised 3x3 Sobel sums (hornSchunck.cpp:27-28, gain 8), so multiply
 (u, v) by SOBEL_GAIN for the motion in pixels."""
 
+# classes of the forward-backward check (HSFLOW_CONSISTENT, ...) and its
+# default thresholds (Sundaram, Brox and Keutzer, ECCV 2010)
+CONSISTENT, INCONSISTENT, OUT_OF_FRAME = 0, 1, 2
+CONSISTENCY_REL, CONSISTENCY_ABS = 0.01, 0.5
+
 # every symbol include/hsflow.h declares
 EXPORTS = (
     "hsflow_version", "hsflow_status_string", "hsflow_create", "hsflow_destroy",
@@ -60,7 +66,14 @@ EXPORTS = (
     "hsflow_max_streams", "hsflow_set_output_hugepages", "hsflow_strip_seg_rows",
     "hsflow_flow_multi_release", "hsflow_warp_gradients_device",
     "hsflow_flow_warped_device", "hsflow_flow_warped",
+    "hsflow_flow_consistency_device", "hsflow_flow_bidir_workspace_bytes",
+    "hsflow_flow_bidir_device", "hsflow_flow_bidir",
 )
+
+
+BidirHost = collections.namedtuple("BidirHost", "u v ub vb mask_f mask_b counts")
+BidirDevice = collections.namedtuple(
+    "BidirDevice", "uf vf ub vb err_f mask_f counts_f err_b mask_b counts_b")
 
 
 class HsflowError(RuntimeError):
@@ -140,6 +153,17 @@ def lib():
                                             ctypes.c_float, _vp, _vp, _vp, _sz, _vp]
     L.hsflow_flow_warped.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i,
                                      ctypes.c_double, _vp, _vp, i, _sz]
+    f = ctypes.c_float
+    L.hsflow_flow_consistency_device.argtypes = [_vp, _vp, _vp, _vp, i, i, i, f, f, _vp, _vp,
+                                                 _vp, _vp]
+    L.hsflow_flow_bidir_workspace_bytes.argtypes = [i, i, i, i]
+    L.hsflow_flow_bidir_workspace_bytes.restype = _sz
+    L.hsflow_flow_bidir_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _sz, _vp]
+    L.hsflow_flow_bidir.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i,
+                                    ctypes.c_double, f, f, _vp, _vp, _vp, _vp, i, _sz, _vp,
+                                    _vp, _sz, _vp]
     L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               _vp, _sz, _vp]
@@ -303,6 +327,51 @@ class Context:
                                       u.ctypes.data, v.ctypes.data, code, u.strides[0])
         _check(rc, self._p)
         return u, v
+
+    def flow_bidir(self, I0, I1, levels: int, warps: int, window: int, iters: int,
+                   alpha: float, rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
+                   out_dtype=np.float64, backward: bool = True, masks: bool = True,
+                   counts: bool = True, out=None, mask_out=None):
+        """Warped solve in both directions with the forward-backward check
+        (hsflow_flow_bidir in include/hsflow.h).  Returns a BidirHost: u, v
+        (I0 -> I1), ub, vb (I1 -> I0, None unless `backward`), mask_f, mask_b
+        (uint8: CONSISTENT / INCONSISTENT / OUT_OF_FRAME, None unless `masks`)
+        and counts (uint32 [2, 3], forward then backward, None unless
+        `counts`).  `out`: an array [4, rows, >= cols] of out_dtype whose
+        planes' first `cols` columns receive u, v, ub, vb (a padded row step);
+        `mask_out`: likewise uint8 [2, rows, >= cols] for the masks."""
+        a, b = _as_image(I0), _as_image(I1)
+        if a.shape != b.shape:
+            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
+        a, b = _common_dtype(a, b)
+        rows, cols = a.shape
+        if out is None:
+            out = np.empty((4, rows, cols), out_dtype)
+        if mask_out is None:
+            mask_out = np.empty((2, rows, cols), np.uint8)
+        if out.ndim != 3 or out.shape[0] != 4 or out.shape[1] != rows or \
+                out.shape[2] < cols or out.dtype not in (np.float32, np.float64) or \
+                out.strides[2] != out.itemsize:
+            raise HsflowError(HSFLOW_ERR_ARG, f"out: need float32/float64 [4, {rows}, >= {cols}]")
+        if mask_out.ndim != 3 or mask_out.shape[0] != 2 or mask_out.shape[1] != rows or \
+                mask_out.shape[2] < cols or mask_out.dtype != np.uint8 or \
+                mask_out.strides[2] != 1:
+            raise HsflowError(HSFLOW_ERR_ARG, f"mask_out: need uint8 [2, {rows}, >= {cols}]")
+        u, v, ub, vb = (out[k, :, :cols] for k in range(4))
+        mf, mb = mask_out[0, :, :cols], mask_out[1, :, :cols]
+        cnt = np.zeros((2, 3), np.uint32) if counts else None
+        code = F64 if out.dtype == np.float64 else F32
+        rc = lib().hsflow_flow_bidir(
+            self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
+            b.strides[0], int(levels), int(warps), int(window), int(iters), float(alpha),
+            float(rel), float(abs), u.ctypes.data, v.ctypes.data,
+            ub.ctypes.data if backward else None, vb.ctypes.data if backward else None, code,
+            out.strides[1], mf.ctypes.data if masks else None,
+            mb.ctypes.data if masks else None, mask_out.strides[1],
+            cnt.ctypes.data if counts else None)
+        _check(rc, self._p)
+        return BidirHost(u, v, ub if backward else None, vb if backward else None,
+                         mf if masks else None, mb if masks else None, cnt)
 
     def flow_bgr(self, bgr0, bgr1, window: int, iters: int, alpha: float,
                  out_dtype=np.float64):
@@ -639,6 +708,99 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
                                              workspace.numel(), _stream_ptr(stream, I0.device))
     _check(rc)
     return u, v
+
+
+def _check_output(want, shape, dtype, device, name):
+    """An optional output of the consistency check: None / False = not asked
+    for, True = allocate, else a contiguous CUDA tensor of `shape`, `dtype`."""
+    if want is None or want is False:
+        return None
+    if want is True:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not want.is_cuda or want.dtype != dtype or not want.is_contiguous() or \
+            tuple(want.shape) != tuple(shape):
+        raise HsflowError(HSFLOW_ERR_ARG, f"{name}: need a contiguous {dtype} CUDA tensor "
+                          f"{tuple(shape)}")
+    return want
+
+
+def consistency_device(uf, vf, ub, vb, rel: float = CONSISTENCY_REL,
+                       abs: float = CONSISTENCY_ABS, err=None, mask=None, counts=None,
+                       stream=None):
+    """Forward-backward check of the flow (uf, vf) against the opposite flow
+    (ub, vb), float32 CUDA tensors [B, H, W] (or [H, W]) in solver units
+    (hsflow_flow_consistency_device in include/hsflow.h).  err / mask / counts:
+    True to allocate, or a tensor to fill -- float32 like uf (pixels), uint8
+    like uf (CONSISTENT / INCONSISTENT / OUT_OF_FRAME), int32 [B, 3] (pixels
+    per class; the library's uint32 words); at least one.  Returns (err, mask,
+    counts), None for those not asked for.  Stream-ordered."""
+    rows, cols = uf.shape[-2:]
+    batch = int(np.prod(uf.shape[:-2])) if uf.dim() > 2 else 1
+    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
+        _check_plane(t, (rows, cols), batch, name)
+    err = _check_output(err, uf.shape, torch.float32, uf.device, "err")
+    mask = _check_output(mask, uf.shape, torch.uint8, uf.device, "mask")
+    counts = _check_output(counts, (batch, 3), torch.int32, uf.device, "counts")
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    with _on(uf.device):
+        rc = lib().hsflow_flow_consistency_device(
+            uf.data_ptr(), vf.data_ptr(), ub.data_ptr(), vb.data_ptr(), rows, cols, batch,
+            float(rel), float(abs), ptr(err), ptr(mask), ptr(counts),
+            _stream_ptr(stream, uf.device))
+    _check(rc)
+    return err, mask, counts
+
+
+def bidir_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -> int:
+    return int(lib().hsflow_flow_bidir_workspace_bytes(rows, cols, batch, levels))
+
+
+def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, alpha: float,
+                      rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
+                      uf=None, vf=None, ub=None, vb=None, err_f=None, mask_f=True,
+                      counts_f=None, err_b=None, mask_b=None, counts_b=None, workspace=None,
+                      stream=None):
+    """Warped solve of I0 -> I1 (uf, vf) and I1 -> I0 (ub, vb) on torch CUDA
+    tensors [B, H, W], then the forward-backward check each way
+    (hsflow_flow_bidir_device in include/hsflow.h).  The flows equal
+    flow_warped_device's bit for bit.  The six check outputs are as in
+    consistency_device (True / tensor / None); a direction with none runs no
+    check.  Returns a BidirDevice, None for outputs not asked for.
+    `workspace`: bidir_workspace_bytes(rows, cols, batch, levels) bytes.
+    Stream-ordered."""
+    rows, cols = I0.shape[-2:]
+    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
+    _check_dense(I0, (rows, cols), "I0")
+    _check_dense(I1, (rows, cols), "I1")
+    if I1.dtype != I0.dtype or I1.shape != I0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
+    flows = []
+    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
+        if t is None:
+            t = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
+        _check_plane(t, (rows, cols), batch, name)
+        flows.append(t)
+    outs = []
+    for want, name in ((err_f, "err_f"), (mask_f, "mask_f"), (counts_f, "counts_f"),
+                       (err_b, "err_b"), (mask_b, "mask_b"), (counts_b, "counts_b")):
+        if name.startswith("counts"):
+            outs.append(_check_output(want, (batch, 3), torch.int32, I0.device, name))
+        else:
+            outs.append(_check_output(
+                want, I0.shape, torch.float32 if name.startswith("err") else torch.uint8,
+                I0.device, name))
+    if workspace is None:
+        n = bidir_workspace_bytes(rows, cols, batch, levels)
+        workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    with _on(I0.device):
+        rc = lib().hsflow_flow_bidir_device(
+            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
+            int(warps), int(window), int(iters), float(alpha), float(rel), float(abs),
+            *[t.data_ptr() for t in flows], *[ptr(t) for t in outs], workspace.data_ptr(),
+            workspace.numel(), _stream_ptr(stream, I0.device))
+    _check(rc)
+    return BidirDevice(*flows, *outs)
 
 
 def warp_gradients_device(I0, I1, u0, v0, workspace, gx=None, gy=None, gt=None, stream=None):

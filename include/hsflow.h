@@ -300,6 +300,75 @@ int hsflow_flow_warped(hsflow_ctx *ctx, const void *I0, const void *I1, int dtyp
                        int window, int iters, double alpha, void *u, void *v, int dtype_out,
                        size_t out_step);
 
+/* ---- bidirectional warped solve + forward-backward consistency -----------
+ * Horn-Schunck returns a smooth flow at every pixel, also where none exists
+ * (ground the next frame covers, the strip that leaves the frame, motion
+ * beyond the pyramid's reach, a scene cut).  The forward-backward check
+ * marks where a flow can be trusted: solve I0 -> I1 (uf, vf) and I1 -> I0
+ * (ub, vb); following uf then ub must lead back to the start.  Per pixel
+ * (y, x) of a pair, flows in solver units (8 px per unit, as above):
+ *   dx = clamp(8 uf, -cols, cols), dy = clamp(8 vf, -rows, rows)   (NaN -> lower
+ *        bound, as hsflow_warp_gradients_device splits its displacements)
+ *   ubw, vbw = ub, vb sampled bilinearly at (y + dy, x + dx), taps clamped
+ *        to the pair's plane (exact where dx, dy are whole)
+ *   d2  = 64 ((uf + ubw)^2 + (vf + vbw)^2)                    px^2
+ *   mag = 64 ((uf^2 + vf^2) + (ubw^2 + vbw^2))
+ *   err = sqrt(d2)                                             px
+ *   out = !(x + dx >= -0.5 && x + dx <= cols - 0.5 &&
+ *           y + dy >= -0.5 && y + dy <= rows - 0.5)
+ *   mask = out ? HSFLOW_OUT_OF_FRAME
+ *              : !(d2 <= rel mag + abs) ? HSFLOW_INCONSISTENT : HSFLOW_CONSISTENT
+ * The comparisons are negated: a NaN anywhere gives a non-zero mask, and a NaN
+ * or infinite uf/vf is out of frame by the clamp; a d2 beyond f32's range is
+ * inconsistent, as it is in exact arithmetic.  The half-pixel rim keeps a
+ * zero flow at a border pixel in the frame whatever its last bit says.
+ * rel, abs: finite, >= 0; 0.01 and 0.5 are Sundaram, Brox and Keutzer's (ECCV
+ * 2010).  No index leaves a pair's plane, whatever the flows hold. */
+#define HSFLOW_HAS_CONSISTENCY 1
+#define HSFLOW_CONSISTENT 0
+#define HSFLOW_INCONSISTENT 1
+#define HSFLOW_OUT_OF_FRAME 2
+#define HSFLOW_CONSISTENCY_REL 0.01f
+#define HSFLOW_CONSISTENCY_ABS 0.5f
+
+/* The check alone: (uf, vf) against (ub, vb), dense f32 [batch][rows][cols].
+ * Outputs, each may be NULL but not all three: err (f32 plane, px), mask (u8
+ * plane, values above), counts (uint32[batch][3], pixels per class; zeroed
+ * stream-ordered by the call, integer sums: the same bytes every run).  The
+ * outputs must not overlap the inputs.  Stream-ordered, no workspace. */
+int hsflow_flow_consistency_device(const float *uf, const float *vf, const float *ub,
+                                   const float *vb, int rows, int cols, int batch, float rel,
+                                   float abs_thr, float *err, uint8_t *mask, uint32_t *counts,
+                                   void *stream);
+
+/* Both directions and both checks in one call.  (uf, vf) is
+ * hsflow_flow_warped_device(I0, I1, ...) and (ub, vb) is
+ * hsflow_flow_warped_device(I1, I0, ...), bit for bit; all four are required.
+ * Then the check runs forward (uf, vf against ub, vb -> err_f, mask_f,
+ * counts_f) and backward (roles swapped -> err_b, mask_b, counts_b); the six
+ * are optional, and a direction with none given launches no check.
+ * `workspace`: at least hsflow_flow_bidir_workspace_bytes(rows, cols, batch,
+ * levels) bytes, 256-byte aligned.  Stream-ordered, never allocates or
+ * synchronises, capturable; all arguments are checked before any device work. */
+size_t hsflow_flow_bidir_workspace_bytes(int rows, int cols, int batch, int levels);
+int hsflow_flow_bidir_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                             int batch, int levels, int warps, int window, int iters,
+                             float alpha, float rel, float abs_thr, float *uf, float *vf,
+                             float *ub, float *vb, float *err_f, uint8_t *mask_f,
+                             uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                             uint32_t *counts_b, void *workspace, size_t workspace_bytes,
+                             void *stream);
+/* Host-buffer, blocking form (same conventions as hsflow_flow_warped).  u, v:
+ * the forward flow; ub, vb: the backward flow (same dtype_out and out_step);
+ * mask_f, mask_b: rows x cols u8 with row step mask_step bytes; counts: host
+ * uint32[6], forward classes then backward.  ub, vb, the masks and counts may
+ * each be NULL. */
+int hsflow_flow_bidir(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                      int cols, size_t in_step0, size_t in_step1, int levels, int warps,
+                      int window, int iters, double alpha, float rel, float abs_thr, void *u,
+                      void *v, void *ub, void *vb, int dtype_out, size_t out_step,
+                      uint8_t *mask_f, uint8_t *mask_b, size_t mask_step, uint32_t *counts);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

@@ -128,6 +128,29 @@ class HornSchunck {
                                    u.data(), v.data(), HSFLOW_F64, (size_t)a.cols * 8));
     }
 
+    // getFlowWarped plus where its answer can be trusted (hsflow.h,
+    // hsflow_flow_bidir): the solve also runs next -> prev, and `mask` gets
+    // the forward check per pixel -- HSFLOW_CONSISTENT, HSFLOW_INCONSISTENT or
+    // HSFLOW_OUT_OF_FRAME -- at the default thresholds.
+    void getFlowBidir(const ImageView &imagePrev, const ImageView &imageNext, int levels,
+                      int warps, std::vector<double> &u, std::vector<double> &v,
+                      std::vector<uint8_t> &mask) {
+        check_pair(imagePrev, imageNext);
+        const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
+        u.resize(n);
+        v.resize(n);
+        mask.resize(n);
+        std::vector<double> ha, hb;
+        const ImageView a = common_type(imagePrev, imageNext, ha);
+        const ImageView b = common_type(imageNext, imagePrev, hb);
+        Context &c = ctx();
+        c.check(hsflow_flow_bidir(c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step,
+                                  b.step, levels, warps, windowSize, maxIterations, alpha,
+                                  HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS, u.data(),
+                                  v.data(), nullptr, nullptr, HSFLOW_F64, (size_t)a.cols * 8,
+                                  mask.data(), nullptr, (size_t)a.cols, nullptr));
+    }
+
     // Raw form for callers that own output rows (cv::Mat adapter): dtype_out
     // HSFLOW_F64 or HSFLOW_F32, out_step in bytes.  Each frame keeps its own
     // row step; frames of different element types are both widened to
