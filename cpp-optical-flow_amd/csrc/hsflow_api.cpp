@@ -681,14 +681,61 @@ int check_warped_args(hsflow_ctx *ctx, int warps, int window, int iters) {
     return HSFLOW_OK;
 }
 
+// ---- median filtering of the flow between warps ----------------------------
+// `median` of the *_median solves: 0 = none, else KM's size
+int check_median_arg(hsflow_ctx *ctx, int median) {
+    if (median != 0 && median != 3 && median != 5)
+        return fail(ctx, HSFLOW_ERR_ARG, "median %d is not 0, 3 or 5", median);
+    return HSFLOW_OK;
+}
+
+bool ranges_overlap(const float *a, const float *b, size_t n) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + n * 4 && pb < pa + n * 4;
+}
+
+int median_impl(hsflow_ctx *ctx, const float *u, const float *v, int rows, int cols, int batch,
+                int ksize, float *u_out, float *v_out, hipStream_t s) {
+    if (ksize != 3 && ksize != 5)
+        return fail(ctx, HSFLOW_ERR_ARG, "median size %d is not 3 or 5", ksize);
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!u || !v || !u_out || !v_out) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    const size_t n = (size_t)rows * cols * batch;
+    if (ranges_overlap(u_out, u, n) || ranges_overlap(u_out, v, n) ||
+        ranges_overlap(v_out, u, n) || ranges_overlap(v_out, v, n) ||
+        ranges_overlap(u_out, v_out, n))
+        return fail(ctx, HSFLOW_ERR_ARG, "median outputs overlap the inputs or each other");
+    hipError_t e = hsflow::launch_median(u, v, rows, cols, batch, ksize, u_out, v_out, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "median launch");
+    return HSFLOW_OK;
+}
+
+// KM on a level's (u, v) in place: into the Jacobi workspace's second u/v
+// planes -- scratch of the passes, idle between solves (run_passes rewrites
+// them before it reads them) -- and back with two device copies.
+int median_in_place(hsflow_ctx *ctx, float *u, float *v, int rows, int cols, int batch,
+                    int ksize, void *ws, hipStream_t s) {
+    const Workspace w = carve(ws, rows, cols, batch);
+    const size_t n = (size_t)rows * cols * batch;
+    hipError_t e = hsflow::launch_median(u, v, rows, cols, batch, ksize, w.u2, w.v2, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "median launch");
+    HIP_TRY(ctx, hipMemcpyAsync(u, w.u2, n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(v, w.v2, n * 4, hipMemcpyDeviceToDevice, s));
+    return HSFLOW_OK;
+}
+
 // The pyramid of pyramid_impl; per level, coarsest first: (u, v) = 0 or the
 // coarser result projected up, then `warps` times KW around the current
-// (u, v) and `iters` Jacobi iterations warm-started from it.
+// (u, v), `iters` Jacobi iterations warm-started from it and, for median != 0,
+// KM (median x median) on the level's (u, v).  median = 0 launches exactly
+// what the solve without the filter always has.
 int warped_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
-                int cols, int batch, int levels, int warps, int window, int iters,
+                int cols, int batch, int levels, int warps, int median, int window, int iters,
                 float alpha, float *u, float *v, void *ws, size_t ws_bytes, hipStream_t s) {
     int rc = check_warped_args(ctx, warps, window, iters);
     if (rc) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
     rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, u, v, ws,
                             ws_bytes);
     if (rc) return rc;
@@ -718,6 +765,10 @@ int warped_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, i
             rc = jacobi_impl(ctx, L.R[l], L.C[l], batch, window, iters, alpha, true, true, ul,
                              vl, ws, L.jac_bytes, s);
             if (rc) return rc;
+            if (median) {
+                rc = median_in_place(ctx, ul, vl, L.R[l], L.C[l], batch, median, ws, s);
+                if (rc) return rc;
+            }
         }
     }
     return HSFLOW_OK;
@@ -767,22 +818,24 @@ int consistency_impl(hsflow_ctx *ctx, const float *uf, const float *vf, const fl
 // warped solve itself (so the flows are hsflow_flow_warped_device's bits by
 // construction) in the one pyramid workspace, then KC per direction asked for.
 int bidir_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
-               int cols, int batch, int levels, int warps, int window, int iters, float alpha,
+               int cols, int batch, int levels, int warps, int median, int window, int iters,
+               float alpha,
                float rel, float abs_thr, float *uf, float *vf, float *ub, float *vb,
                float *err_f, uint8_t *mask_f, uint32_t *counts_f, float *err_b,
                uint8_t *mask_b, uint32_t *counts_b, void *ws, size_t ws_bytes, hipStream_t s) {
     int rc = check_warped_args(ctx, warps, window, iters);
     if (rc) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
     rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, uf, vf, ws,
                             ws_bytes);
     if (rc) return rc;
     if (!ub || !vb) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
-    rc = warped_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, window, iters,
-                     alpha, uf, vf, ws, ws_bytes, s);
+    rc = warped_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
+                     iters, alpha, uf, vf, ws, ws_bytes, s);
     if (rc) return rc;
-    rc = warped_impl(ctx, I1, I0, dtype_in, rows, cols, batch, levels, warps, window, iters,
-                     alpha, ub, vb, ws, ws_bytes, s);
+    rc = warped_impl(ctx, I1, I0, dtype_in, rows, cols, batch, levels, warps, median, window,
+                     iters, alpha, ub, vb, ws, ws_bytes, s);
     if (rc) return rc;
     if (err_f || mask_f || counts_f) {
         rc = consistency_run(ctx, uf, vf, ub, vb, rows, cols, batch, rel, abs_thr, err_f,
@@ -796,11 +849,12 @@ int bidir_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
 }
 
 // The host-buffer form of both pyramid solves: warps = 0 is hsflow_flow_pyramid,
-// warps >= 1 hsflow_flow_warped (same upload, download, f64 widening and
-// huge-page advice).
+// warps >= 1 hsflow_flow_warped[_median] (same upload, download, f64 widening
+// and huge-page advice).
 int pyramid_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
-                 int cols, size_t in_step0, size_t in_step1, int levels, int warps, int window,
-                 int iters, double alpha, void *u, void *v, int dtype_out, size_t out_step) {
+                 int cols, size_t in_step0, size_t in_step1, int levels, int warps, int median,
+                 int window, int iters, double alpha, void *u, void *v, int dtype_out,
+                 size_t out_step) {
     int rc = check_host_args(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1,
                              dtype_out, out_step);
     if (rc) return rc;
@@ -820,8 +874,9 @@ int pyramid_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
     if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
         return rc;
     const int dt0 = dtype_in;
-    rc = warps ? warped_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, warps, window, iters,
-                             (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream)
+    rc = warps ? warped_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, warps, median, window,
+                             iters, (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes,
+                             ctx->stream)
                : pyramid_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, window, iters,
                               (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
@@ -838,10 +893,10 @@ int pyramid_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
 // download around bidir_impl; the masks and counts come down on the same
 // stream ahead of the flows, whose download drains it.
 int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
-               int cols, size_t in_step0, size_t in_step1, int levels, int warps, int window,
-               int iters, double alpha, float rel, float abs_thr, void *u, void *v, void *ub,
-               void *vb, int dtype_out, size_t out_step, uint8_t *mask_f, uint8_t *mask_b,
-               size_t mask_step, uint32_t *counts) {
+               int cols, size_t in_step0, size_t in_step1, int levels, int warps, int median,
+               int window, int iters, double alpha, float rel, float abs_thr, void *u, void *v,
+               void *ub, void *vb, int dtype_out, size_t out_step, uint8_t *mask_f,
+               uint8_t *mask_b, size_t mask_step, uint32_t *counts) {
     int rc = check_host_args(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1,
                              dtype_out, out_step);
     if (rc) return rc;
@@ -850,6 +905,7 @@ int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
         return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
                     HSFLOW_MAX_LEVELS);
     if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
     if ((mask_f || mask_b) && mask_step < (size_t)cols)
         return fail(ctx, HSFLOW_ERR_ARG, "mask step %zu < row bytes %d", mask_step, cols);
@@ -870,7 +926,7 @@ int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
     uint32_t *dc = (uint32_t *)(dmb + mb);
     if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
         return rc;
-    rc = bidir_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, window, iters,
+    rc = bidir_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, median, window, iters,
                     (float)alpha, rel, abs_thr, d[0], d[1], d[2], d[3], nullptr,
                     mask_f ? dmf : nullptr, counts ? dc : nullptr, nullptr,
                     mask_b ? dmb : nullptr, counts ? dc + 3 : nullptr, ctx->d_ws,
@@ -1267,7 +1323,7 @@ int hsflow_flow_pyramid(hsflow_ctx *ctx, const void *I0, const void *I1, int dty
                         int rows, int cols, size_t in_step0, size_t in_step1, int levels,
                         int window, int iters, double alpha, void *u, void *v,
                         int dtype_out, size_t out_step) {
-    return pyramid_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, 0,
+    return pyramid_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, 0, 0,
                         window, iters, alpha, u, v, dtype_out, out_step);
 }
 
@@ -1280,24 +1336,51 @@ int hsflow_warp_gradients_device(const void *I0, const void *I1, int dtype_in, i
                                gt, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int hsflow_flow_warped_median_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                     int cols, int batch, int levels, int warps, int median,
+                                     int window, int iters, float alpha, float *u, float *v,
+                                     void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return warped_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                       window, iters, alpha, u, v, workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+
 int hsflow_flow_warped_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                               int batch, int levels, int warps, int window, int iters,
                               float alpha, float *u, float *v, void *workspace,
                               size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    return warped_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, window,
-                       iters, alpha, u, v, workspace, workspace_bytes, (hipStream_t)stream);
+    return hsflow_flow_warped_median_device(I0, I1, dtype_in, rows, cols, batch, levels, warps,
+                                            0, window, iters, alpha, u, v, workspace,
+                                            workspace_bytes, stream);
+}
+
+int hsflow_flow_warped_median(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
+                              int rows, int cols, size_t in_step0, size_t in_step1, int levels,
+                              int warps, int median, int window, int iters, double alpha,
+                              void *u, void *v, int dtype_out, size_t out_step) {
+    if (!ctx) return HSFLOW_ERR_ARG;
+    int rc = check_warped_args(ctx, warps, window, iters);
+    if (rc) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
+    return pyramid_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
+                        median, window, iters, alpha, u, v, dtype_out, out_step);
 }
 
 int hsflow_flow_warped(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
                        int cols, size_t in_step0, size_t in_step1, int levels, int warps,
                        int window, int iters, double alpha, void *u, void *v, int dtype_out,
                        size_t out_step) {
-    if (!ctx) return HSFLOW_ERR_ARG;
-    int rc = check_warped_args(ctx, warps, window, iters);
-    if (rc) return rc;
-    return pyramid_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
-                        window, iters, alpha, u, v, dtype_out, out_step);
+    return hsflow_flow_warped_median(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1,
+                                     levels, warps, 0, window, iters, alpha, u, v, dtype_out,
+                                     out_step);
+}
+
+int hsflow_flow_median_device(const float *u, const float *v, int rows, int cols, int batch,
+                              int ksize, float *u_out, float *v_out, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return median_impl(nullptr, u, v, rows, cols, batch, ksize, u_out, v_out,
+                       (hipStream_t)stream);
 }
 
 size_t hsflow_flow_bidir_workspace_bytes(int rows, int cols, int batch, int levels) {
@@ -1314,16 +1397,41 @@ int hsflow_flow_consistency_device(const float *uf, const float *vf, const float
                             counts, (hipStream_t)stream);
 }
 
+int hsflow_flow_bidir_median_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                    int cols, int batch, int levels, int warps, int median,
+                                    int window, int iters, float alpha, float rel, float abs_thr,
+                                    float *uf, float *vf, float *ub, float *vb, float *err_f,
+                                    uint8_t *mask_f, uint32_t *counts_f, float *err_b,
+                                    uint8_t *mask_b, uint32_t *counts_b, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return bidir_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
+                      iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f, err_b,
+                      mask_b, counts_b, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int hsflow_flow_bidir_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                              int batch, int levels, int warps, int window, int iters,
                              float alpha, float rel, float abs_thr, float *uf, float *vf, float *ub,
                              float *vb, float *err_f, uint8_t *mask_f, uint32_t *counts_f,
                              float *err_b, uint8_t *mask_b, uint32_t *counts_b, void *workspace,
                              size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    return bidir_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, window,
-                      iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f, err_b,
-                      mask_b, counts_b, workspace, workspace_bytes, (hipStream_t)stream);
+    return hsflow_flow_bidir_median_device(I0, I1, dtype_in, rows, cols, batch, levels, warps, 0,
+                                           window, iters, alpha, rel, abs_thr, uf, vf, ub, vb,
+                                           err_f, mask_f, counts_f, err_b, mask_b, counts_b,
+                                           workspace, workspace_bytes, stream);
+}
+
+int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
+                             int rows, int cols, size_t in_step0, size_t in_step1, int levels,
+                             int warps, int median, int window, int iters, double alpha,
+                             float rel, float abs_thr, void *u, void *v, void *ub, void *vb,
+                             int dtype_out, size_t out_step, uint8_t *mask_f, uint8_t *mask_b,
+                             size_t mask_step, uint32_t *counts) {
+    if (!ctx) return HSFLOW_ERR_ARG;
+    return bidir_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
+                      median, window, iters, alpha, rel, abs_thr, u, v, ub, vb, dtype_out,
+                      out_step, mask_f, mask_b, mask_step, counts);
 }
 
 int hsflow_flow_bidir(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
@@ -1331,10 +1439,9 @@ int hsflow_flow_bidir(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype
                       int window, int iters, double alpha, float rel, float abs_thr, void *u,
                       void *v, void *ub, void *vb, int dtype_out, size_t out_step,
                       uint8_t *mask_f, uint8_t *mask_b, size_t mask_step, uint32_t *counts) {
-    if (!ctx) return HSFLOW_ERR_ARG;
-    return bidir_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
-                      window, iters, alpha, rel, abs_thr, u, v, ub, vb, dtype_out, out_step, mask_f,
-                      mask_b, mask_step, counts);
+    return hsflow_flow_bidir_median(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels,
+                                    warps, 0, window, iters, alpha, rel, abs_thr, u, v, ub, vb,
+                                    dtype_out, out_step, mask_f, mask_b, mask_step, counts);
 }
 
 int hsflow_bgr_to_gray_device(const uint8_t *bgr, int rows, int cols, int batch,

@@ -55,6 +55,11 @@ hipError_t launch_consistency(const float *uf, const float *vf, const float *ub,
                               const float *vb, int rows, int cols, int batch, float rel,
                               float abs_thr, float *err, uint8_t *mask, uint32_t *counts,
                               hipStream_t s);
+// KM (hsflow_median.hip): ksize x ksize (3 or 5) median of u and of v, each
+// on its own, dense f32 batch planes, out of place; border replicated, IEEE
+// total order of the bit patterns (the result is one of the taps)
+hipError_t launch_median(const float *u, const float *v, int rows, int cols, int batch, int ksize,
+                         float *u_out, float *v_out, hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

@@ -50,6 +50,8 @@ unnormalised 3x3 Sobel sums (hornSchunck.cpp:27-28, gain 8), so multiply
 # default thresholds (Sundaram, Brox and Keutzer, ECCV 2010)
 CONSISTENT, INCONSISTENT, OUT_OF_FRAME = 0, 1, 2
 CONSISTENCY_REL, CONSISTENCY_ABS = 0.01, 0.5
+# sizes of the median filter between warps (median=; 0 = none)
+MEDIAN_SIZES = (3, 5)
 
 # every symbol include/hsflow.h declares
 EXPORTS = (
@@ -68,6 +70,9 @@ EXPORTS = (
     "hsflow_flow_warped_device", "hsflow_flow_warped",
     "hsflow_flow_consistency_device", "hsflow_flow_bidir_workspace_bytes",
     "hsflow_flow_bidir_device", "hsflow_flow_bidir",
+    "hsflow_flow_median_device", "hsflow_flow_warped_median_device",
+    "hsflow_flow_warped_median", "hsflow_flow_bidir_median_device",
+    "hsflow_flow_bidir_median",
 )
 
 
@@ -164,6 +169,17 @@ def lib():
     L.hsflow_flow_bidir.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i,
                                     ctypes.c_double, f, f, _vp, _vp, _vp, _vp, i, _sz, _vp,
                                     _vp, _sz, _vp]
+    L.hsflow_flow_median_device.argtypes = [_vp, _vp, i, i, i, i, _vp, _vp, _vp]
+    L.hsflow_flow_warped_median_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f,
+                                                   _vp, _vp, _vp, _sz, _vp]
+    L.hsflow_flow_warped_median.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
+                                            ctypes.c_double, _vp, _vp, i, _sz]
+    L.hsflow_flow_bidir_median_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _sz, _vp]
+    L.hsflow_flow_bidir_median.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
+                                           ctypes.c_double, f, f, _vp, _vp, _vp, _vp, i, _sz,
+                                           _vp, _vp, _sz, _vp]
     L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               _vp, _sz, _vp]
@@ -308,11 +324,13 @@ class Context:
         return u, v
 
     def flow_warped(self, I0, I1, levels: int, warps: int, window: int, iters: int,
-                    alpha: float, out_dtype=np.float64):
+                    alpha: float, out_dtype=np.float64, median: int = 0):
         """Warped coarse-to-fine solve for large displacements (`warps`
         re-linearisations per level, `iters` iterations each), see
         hsflow_flow_warped in include/hsflow.h.  (u, v) * SOBEL_GAIN is the
-        motion in pixels."""
+        motion in pixels.  median = 3 or 5 filters (u, v) with a median of
+        that size after every warp's iterations (hsflow_flow_warped_median);
+        0 = none."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -321,17 +339,17 @@ class Context:
         u = np.empty((rows, cols), out_dtype)
         v = np.empty((rows, cols), out_dtype)
         code = F64 if u.dtype == np.float64 else F32
-        rc = lib().hsflow_flow_warped(self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a),
-                                      rows, cols, a.strides[0], b.strides[0], int(levels),
-                                      int(warps), int(window), int(iters), float(alpha),
-                                      u.ctypes.data, v.ctypes.data, code, u.strides[0])
+        rc = lib().hsflow_flow_warped_median(
+            self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
+            b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
+            float(alpha), u.ctypes.data, v.ctypes.data, code, u.strides[0])
         _check(rc, self._p)
         return u, v
 
     def flow_bidir(self, I0, I1, levels: int, warps: int, window: int, iters: int,
                    alpha: float, rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                    out_dtype=np.float64, backward: bool = True, masks: bool = True,
-                   counts: bool = True, out=None, mask_out=None):
+                   counts: bool = True, out=None, mask_out=None, median: int = 0):
         """Warped solve in both directions with the forward-backward check
         (hsflow_flow_bidir in include/hsflow.h).  Returns a BidirHost: u, v
         (I0 -> I1), ub, vb (I1 -> I0, None unless `backward`), mask_f, mask_b
@@ -339,7 +357,8 @@ class Context:
         and counts (uint32 [2, 3], forward then backward, None unless
         `counts`).  `out`: an array [4, rows, >= cols] of out_dtype whose
         planes' first `cols` columns receive u, v, ub, vb (a padded row step);
-        `mask_out`: likewise uint8 [2, rows, >= cols] for the masks."""
+        `mask_out`: likewise uint8 [2, rows, >= cols] for the masks.  median
+        as in flow_warped, for both directions."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -361,9 +380,10 @@ class Context:
         mf, mb = mask_out[0, :, :cols], mask_out[1, :, :cols]
         cnt = np.zeros((2, 3), np.uint32) if counts else None
         code = F64 if out.dtype == np.float64 else F32
-        rc = lib().hsflow_flow_bidir(
+        rc = lib().hsflow_flow_bidir_median(
             self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
-            b.strides[0], int(levels), int(warps), int(window), int(iters), float(alpha),
+            b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
+            float(alpha),
             float(rel), float(abs), u.ctypes.data, v.ctypes.data,
             ub.ctypes.data if backward else None, vb.ctypes.data if backward else None, code,
             out.strides[1], mf.ctypes.data if masks else None,
@@ -517,17 +537,21 @@ class hornSchunck:  # noqa: N801  (reference class name, hornSchunck.cpp:8)
 
 
 def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int = 1,
-            warps: int = 0):
+            warps: int = 0, median: int = 0):
     """compute(I0, I1, alpha, nIter) -> (u, v): the north-star convenience
     wrapper over hornSchunck(windowSize, nIter, alpha).getFlow; levels > 1
     runs the config-5 coarse-to-fine warm start (nIter per level).  warps >= 1
     runs the warped coarse-to-fine solve instead (large displacements:
     `warps` re-linearisations per level, nIter iterations each); warps = 0
-    keeps the behaviour above."""
+    keeps the behaviour above.  median = 3 or 5 (MEDIAN_SIZES) filters the
+    flow after every warp's iterations and needs warps >= 1."""
+    if median and not warps:
+        raise HsflowError(HSFLOW_ERR_ARG, f"median {median} needs the warped solve (warps >= 1)")
     if warps:
         if not 1 <= int(warps) <= MAX_WARPS:
             raise HsflowError(HSFLOW_ERR_ARG, f"warps {warps} outside [1, {MAX_WARPS}]")
-        return default_context().flow_warped(I0, I1, levels, warps, windowSize, nIter, alpha)
+        return default_context().flow_warped(I0, I1, levels, warps, windowSize, nIter, alpha,
+                                             median=median)
     if levels > 1:
         return default_context().flow_pyramid(I0, I1, levels, windowSize, nIter, alpha)
     return hornSchunck(windowSize, nIter, alpha).getFlow(I0, I1)
@@ -679,12 +703,15 @@ def flow_pyramid_device(I0, I1, levels: int, window: int, iters: int, alpha: flo
 
 
 def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
-                       alpha: float, u=None, v=None, workspace=None, stream=None):
+                       alpha: float, u=None, v=None, workspace=None, stream=None,
+                       median: int = 0):
     """Warped coarse-to-fine solve on torch CUDA tensors [B, H, W] (uint8 /
     float16 / float32 / float64): per level `warps` times the gradients
     linearised around the current flow and `iters` Jacobi iterations.
     `workspace`: pyramid_workspace_bytes(rows, cols, batch, levels) bytes.
-    (u, v) * SOBEL_GAIN is the motion in pixels.  Stream-ordered."""
+    (u, v) * SOBEL_GAIN is the motion in pixels.  median = 3 or 5: a median
+    of that size over (u, v) after every warp's iterations
+    (hsflow_flow_warped_median_device); 0 = none.  Stream-ordered."""
     rows, cols = I0.shape[-2:]
     batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
     _check_dense(I0, (rows, cols), "I0")
@@ -701,11 +728,11 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
         n = pyramid_workspace_bytes(rows, cols, batch, levels)
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     with _on(I0.device):
-        rc = lib().hsflow_flow_warped_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0),
-                                             rows, cols, batch, int(levels), int(warps),
-                                             int(window), int(iters), float(alpha),
-                                             u.data_ptr(), v.data_ptr(), workspace.data_ptr(),
-                                             workspace.numel(), _stream_ptr(stream, I0.device))
+        rc = lib().hsflow_flow_warped_median_device(
+            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
+            int(warps), int(median), int(window), int(iters), float(alpha), u.data_ptr(),
+            v.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            _stream_ptr(stream, I0.device))
     _check(rc)
     return u, v
 
@@ -751,6 +778,29 @@ def consistency_device(uf, vf, ub, vb, rel: float = CONSISTENCY_REL,
     return err, mask, counts
 
 
+def median_device(u, v, ksize: int, u_out=None, v_out=None, stream=None):
+    """ksize x ksize (3 or 5, MEDIAN_SIZES) median of u and of v, each on its
+    own: float32 CUDA tensors [B, H, W] (or [H, W]), border replicated, IEEE
+    total order of the bit patterns, so each result is one of its taps bit
+    for bit (hsflow_flow_median_device in include/hsflow.h).  Out of place:
+    u_out, v_out are allocated unless given and must not overlap u or v.
+    Returns (u_out, v_out).  Stream-ordered."""
+    rows, cols = u.shape[-2:]
+    batch = int(np.prod(u.shape[:-2])) if u.dim() > 2 else 1
+    if u_out is None:
+        u_out = torch.empty(u.shape, dtype=torch.float32, device=u.device)
+    if v_out is None:
+        v_out = torch.empty(u.shape, dtype=torch.float32, device=u.device)
+    for t, name in ((u, "u"), (v, "v"), (u_out, "u_out"), (v_out, "v_out")):
+        _check_plane(t, (rows, cols), batch, name)
+    with _on(u.device):
+        rc = lib().hsflow_flow_median_device(u.data_ptr(), v.data_ptr(), rows, cols, batch,
+                                             int(ksize), u_out.data_ptr(), v_out.data_ptr(),
+                                             _stream_ptr(stream, u.device))
+    _check(rc)
+    return u_out, v_out
+
+
 def bidir_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -> int:
     return int(lib().hsflow_flow_bidir_workspace_bytes(rows, cols, batch, levels))
 
@@ -759,7 +809,7 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
                       rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                       uf=None, vf=None, ub=None, vb=None, err_f=None, mask_f=True,
                       counts_f=None, err_b=None, mask_b=None, counts_b=None, workspace=None,
-                      stream=None):
+                      stream=None, median: int = 0):
     """Warped solve of I0 -> I1 (uf, vf) and I1 -> I0 (ub, vb) on torch CUDA
     tensors [B, H, W], then the forward-backward check each way
     (hsflow_flow_bidir_device in include/hsflow.h).  The flows equal
@@ -767,7 +817,7 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
     consistency_device (True / tensor / None); a direction with none runs no
     check.  Returns a BidirDevice, None for outputs not asked for.
     `workspace`: bidir_workspace_bytes(rows, cols, batch, levels) bytes.
-    Stream-ordered."""
+    median as in flow_warped_device, for both directions.  Stream-ordered."""
     rows, cols = I0.shape[-2:]
     batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
     _check_dense(I0, (rows, cols), "I0")
@@ -794,9 +844,10 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     ptr = (lambda t: t.data_ptr() if t is not None else None)
     with _on(I0.device):
-        rc = lib().hsflow_flow_bidir_device(
+        rc = lib().hsflow_flow_bidir_median_device(
             I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
-            int(warps), int(window), int(iters), float(alpha), float(rel), float(abs),
+            int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
+            float(abs),
             *[t.data_ptr() for t in flows], *[ptr(t) for t in outs], workspace.data_ptr(),
             workspace.numel(), _stream_ptr(stream, I0.device))
     _check(rc)

@@ -369,6 +369,66 @@ int hsflow_flow_bidir(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype
                       void *v, void *ub, void *vb, int dtype_out, size_t out_step,
                       uint8_t *mask_f, uint8_t *mask_b, size_t mask_step, uint32_t *counts);
 
+/* ---- median filtering of the flow between warps --------------------------
+ * The quadratic smoothness term has to run at alpha ~ 400 to keep the warped
+ * solve stable, and at that alpha a moving object's flow is smeared across
+ * its boundary; at a lower alpha the solve develops isolated spikes.  A median
+ * filter of u and of v after every warp's iterations removes the spikes
+ * without moving edges (Wedel et al. 2008; Sun, Roth and Black, CVPR 2010) and
+ * makes alpha ~ 100 usable.  ksize = 3 or 5, each component on its own:
+ *   out(y, x) = the element of rank (ksize^2 - 1) / 2 of the ksize^2 taps
+ *               in[clamp(y + j, 0, rows - 1)][clamp(x + i, 0, cols - 1)],
+ *               |i|, |j| <= ksize / 2
+ * (border replicated, as the warp's and the check's taps; no tap leaves the
+ * pair's plane).  The order is the IEEE-754 total order of the f32 bit
+ * patterns:
+ *   key = bits ^ 0xFFFFFFFF if the sign bit is set, else bits | 0x80000000,
+ * compared as unsigned: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.  The
+ * result is one of the taps bit for bit and the choice is fixed whatever the
+ * planes hold (a NaN is an extreme value, not a poison: a lone one vanishes).
+ * The *_median solves are the warped and bidirectional solves above with `int
+ * median` after `warps`: 0, 3 or 5.  For median != 0 the schedule per level
+ * becomes `warps` times { gradients around (u, v); `iters` Jacobi iterations;
+ * median x median filter of the level's (u, v) } -- every level and every
+ * warp, the last warp of level 0 included, so the returned flow is filtered.
+ * median = 0 runs the launches of the solves above and returns their bits
+ * (those entry points are the median = 0 case of these).  hsflow_flow_bidir_median
+ * filters both directions, then runs the check unchanged.
+ * Workspace: the filter writes the Jacobi workspace's second (u, v) planes,
+ * idle between solves, and copies them back, so the *_median solves need
+ * nothing beyond hsflow_pyramid_workspace_bytes /
+ * hsflow_flow_bidir_workspace_bytes and there is no size function of their
+ * own. */
+#define HSFLOW_HAS_MEDIAN 1
+
+/* The filter alone: dense f32 [batch][rows][cols] planes u, v -> u_out, v_out.
+ * No output plane range may overlap an input plane range or the other output
+ * (HSFLOW_ERR_ARG).  Stream-ordered, no workspace, never allocates or
+ * synchronises, capturable; all arguments are checked before any device work. */
+int hsflow_flow_median_device(const float *u, const float *v, int rows, int cols, int batch,
+                              int ksize, float *u_out, float *v_out, void *stream);
+int hsflow_flow_warped_median_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                     int cols, int batch, int levels, int warps, int median,
+                                     int window, int iters, float alpha, float *u, float *v,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_warped_median(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
+                              int rows, int cols, size_t in_step0, size_t in_step1, int levels,
+                              int warps, int median, int window, int iters, double alpha,
+                              void *u, void *v, int dtype_out, size_t out_step);
+int hsflow_flow_bidir_median_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                    int cols, int batch, int levels, int warps, int median,
+                                    int window, int iters, float alpha, float rel, float abs_thr,
+                                    float *uf, float *vf, float *ub, float *vb, float *err_f,
+                                    uint8_t *mask_f, uint32_t *counts_f, float *err_b,
+                                    uint8_t *mask_b, uint32_t *counts_b, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
+                             int rows, int cols, size_t in_step0, size_t in_step1, int levels,
+                             int warps, int median, int window, int iters, double alpha,
+                             float rel, float abs_thr, void *u, void *v, void *ub, void *vb,
+                             int dtype_out, size_t out_step, uint8_t *mask_f, uint8_t *mask_b,
+                             size_t mask_step, uint32_t *counts);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

@@ -113,8 +113,12 @@ class HornSchunck {
     // hsflow_flow_warped): `levels` pyramid levels, per level `warps`
     // re-linearisations around the current flow with maxIterations
     // iterations each.  u, v as getFlow; 8 (u, v) is the motion in pixels.
+    // median = 3 or 5: a median x median filter of (u, v) after every warp's
+    // iterations (hsflow_flow_warped_median), which makes alpha ~ 100 usable
+    // and keeps a moving object's edges; 0 = none.
     void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
-                       int warps, std::vector<double> &u, std::vector<double> &v) {
+                       int warps, std::vector<double> &u, std::vector<double> &v,
+                       int median = 0) {
         check_pair(imagePrev, imageNext);
         const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
         u.resize(n);
@@ -123,18 +127,20 @@ class HornSchunck {
         const ImageView a = common_type(imagePrev, imageNext, ha);
         const ImageView b = common_type(imageNext, imagePrev, hb);
         Context &c = ctx();
-        c.check(hsflow_flow_warped(c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step,
-                                   b.step, levels, warps, windowSize, maxIterations, alpha,
-                                   u.data(), v.data(), HSFLOW_F64, (size_t)a.cols * 8));
+        c.check(hsflow_flow_warped_median(c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step,
+                                          b.step, levels, warps, median, windowSize,
+                                          maxIterations, alpha, u.data(), v.data(), HSFLOW_F64,
+                                          (size_t)a.cols * 8));
     }
 
     // getFlowWarped plus where its answer can be trusted (hsflow.h,
     // hsflow_flow_bidir): the solve also runs next -> prev, and `mask` gets
     // the forward check per pixel -- HSFLOW_CONSISTENT, HSFLOW_INCONSISTENT or
-    // HSFLOW_OUT_OF_FRAME -- at the default thresholds.
+    // HSFLOW_OUT_OF_FRAME -- at the default thresholds.  median as in
+    // getFlowWarped, for both directions.
     void getFlowBidir(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                       int warps, std::vector<double> &u, std::vector<double> &v,
-                      std::vector<uint8_t> &mask) {
+                      std::vector<uint8_t> &mask, int median = 0) {
         check_pair(imagePrev, imageNext);
         const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
         u.resize(n);
@@ -144,11 +150,11 @@ class HornSchunck {
         const ImageView a = common_type(imagePrev, imageNext, ha);
         const ImageView b = common_type(imageNext, imagePrev, hb);
         Context &c = ctx();
-        c.check(hsflow_flow_bidir(c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step,
-                                  b.step, levels, warps, windowSize, maxIterations, alpha,
-                                  HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS, u.data(),
-                                  v.data(), nullptr, nullptr, HSFLOW_F64, (size_t)a.cols * 8,
-                                  mask.data(), nullptr, (size_t)a.cols, nullptr));
+        c.check(hsflow_flow_bidir_median(
+            c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step, b.step, levels, warps, median,
+            windowSize, maxIterations, alpha, HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS,
+            u.data(), v.data(), nullptr, nullptr, HSFLOW_F64, (size_t)a.cols * 8, mask.data(),
+            nullptr, (size_t)a.cols, nullptr));
     }
 
     // Raw form for callers that own output rows (cv::Mat adapter): dtype_out
