@@ -253,31 +253,44 @@ SidePool *side_pool(int need) {
     return &pool;
 }
 
+// hsflow_set_first_pass_fusion: a cold K4 solve computes K1's outputs in its
+// first pass (1, default) or runs K1 in front of the passes (0)
+int g_first_fusion = 1;
+// hsflow_first_pass_launches: fused first passes launched so far
+std::atomic<long long> g_first_launches{0};
+
+// The frames of a cold solve whose first pass has K1 fused in (fuse_first);
+// null for every other solve: the workspace then holds K1's outputs already.
+struct Frames {
+    const void *I0, *I1;
+    int dtype;
+};
+
 int jacobi_one(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                float alpha, bool warm, bool maybe_f32, float *u, float *v,
-               void *workspace, size_t ws_bytes, hipStream_t s);
+               void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr = nullptr);
 int check_jacobi_args(hsflow_ctx *ctx, int rows, int cols, int batch, int window,
                       int iters, const float *u, const float *v, void *workspace,
                       size_t ws_bytes);
 int jacobi_sub(hsflow_ctx *ctx, int rows, int cols, int nb, int first, int batch,
                int window, int iters, float alpha, bool warm, bool maybe_f32, float *u,
-               float *v, const Workspace &w, hipStream_t s);
+               float *v, const Workspace &w, hipStream_t s, const Frames *fr = nullptr);
 
 int jacobi_impl(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                 float alpha, bool warm, bool maybe_f32, float *u, float *v,
-                void *workspace, size_t ws_bytes, hipStream_t s) {
+                void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr = nullptr) {
     int rc0 = check_jacobi_args(ctx, rows, cols, batch, window, iters, u, v, workspace,
                                 ws_bytes);
     if (rc0) return rc0;
     const int split = split_for(batch, s);
     if (split <= 1 || iters == 0)
         return jacobi_one(ctx, rows, cols, batch, window, iters, alpha, warm, maybe_f32, u,
-                          v, workspace, ws_bytes, s);
+                          v, workspace, ws_bytes, s, fr);
     Workspace w = carve(workspace, rows, cols, batch);
     SidePool *pool = side_pool(split);
     if (!pool)
         return jacobi_one(ctx, rows, cols, batch, window, iters, alpha, warm, maybe_f32, u,
-                          v, workspace, ws_bytes, s);
+                          v, workspace, ws_bytes, s, fr);
     const size_t plane = (size_t)rows * cols;
     HIP_TRY(ctx, hipEventRecord(pool->events[0], s));
     int first = 0, forked = 0, rc = HSFLOW_OK;
@@ -292,7 +305,7 @@ int jacobi_impl(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int 
         ++forked;
         // the sub-batch's slice of every workspace plane, as its own workspace
         rc = jacobi_sub(ctx, rows, cols, nb, first, batch, window, iters, alpha, warm,
-                        maybe_f32, u + first * plane, v + first * plane, w, sk);
+                        maybe_f32, u + first * plane, v + first * plane, w, sk, fr);
         first += nb;
     }
     // join every forked stream back, the error path included (a capture
@@ -309,13 +322,20 @@ int jacobi_impl(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int 
 // that may start at any pair of a larger workspace).
 int run_passes(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                float alpha, bool warm, bool maybe_f32, float *u, float *v,
-               const Workspace &w, hipStream_t s, int fill_batch) {
+               const Workspace &w, hipStream_t s, int fill_batch, const Frames *fr = nullptr) {
     const size_t n = (size_t)rows * cols * batch;
     if (iters == 0) {
         // hornSchunck.cpp:49-50: the loop does not run, u = v = 0
         if (!warm) {
             HIP_TRY(ctx, hipMemsetAsync(u, 0, n * 4, s));
             HIP_TRY(ctx, hipMemsetAsync(v, 0, n * 4, s));
+        }
+        if (fr) {  // the workspace still gets K1's outputs
+            if (fr->dtype != HSFLOW_U8)
+                HIP_TRY(ctx, hipMemsetAsync(w.flags, 0, (size_t)batch * 4, s));
+            hipError_t e = hsflow::launch_gradients(fr->I0, fr->I1, fr->dtype, rows, cols, batch,
+                                                    w.gpack, w.gx, w.gy, w.gt, w.flags, false, s);
+            if (e != hipSuccess) return hip_fail(ctx, e, "gradients launch");
         }
         return HSFLOW_OK;
     }
@@ -362,6 +382,20 @@ int run_passes(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int i
             src_v = v;
         }
     }
+    // `fr`: K1 has not run for these pairs.  Where this plan has a full-depth
+    // K4 pass it is fused into pass 0: this chain's flags zeroed, the fused
+    // pass, then K1f for the chain's pairs, whose planes pass 1 may read (it
+    // returns at once for the others).  Under any other plan (cold_solve
+    // hands the frames down only when it expects this one) the chain runs K1
+    // itself in front of its passes.
+    const bool fuse = fr && strip && !warm && iters >= kb;
+    if (fr && fr->dtype != HSFLOW_U8)
+        HIP_TRY(ctx, hipMemsetAsync(w.flags, 0, (size_t)batch * 4, s));
+    if (fr && !fuse) {
+        hipError_t e = hsflow::launch_gradients(fr->I0, fr->I1, fr->dtype, rows, cols, batch,
+                                                w.gpack, w.gx, w.gy, w.gt, w.flags, false, s);
+        if (e != hipSuccess) return hip_fail(ctx, e, "gradients launch");
+    }
     int done = 0;
     for (int pass = 0; pass < passes; ++pass) {
         a.iters = std::min(kb, iters - done);
@@ -369,6 +403,20 @@ int run_passes(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int i
         a.v_in = src_v;
         a.u_out = dst_is_user(pass) ? u : w.u2;
         a.v_out = dst_is_user(pass) ? v : w.v2;
+        if (fuse && pass == 0) {
+            const hsflow::FirstArgs f{fr->I0, fr->I1, w.gpack, w.flags, 0};
+            hipError_t e =
+                hsflow::launch_jacobi_strip_first(a, f, fr->dtype, window, kb, strip_rows, s);
+            if (e == hipSuccess)
+                e = hsflow::launch_gradients_f32(fr->I0, fr->I1, fr->dtype, rows, cols, batch,
+                                                 w.gx, w.gy, w.gt, w.flags, s);
+            if (e != hipSuccess) return hip_fail(ctx, e, "fused first pass launch");
+            g_first_launches.fetch_add(1, std::memory_order_relaxed);
+            src_u = a.u_out;
+            src_v = a.v_out;
+            done += a.iters;
+            continue;
+        }
         // a K2 pass (a shorter last pass of a K4 solve) takes a depth K2 is
         // built for: any depth >= its iterations gives the same bits
         int kb2 = kb;
@@ -408,18 +456,18 @@ int check_jacobi_args(hsflow_ctx *ctx, int rows, int cols, int batch, int window
 
 int jacobi_one(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                float alpha, bool warm, bool maybe_f32, float *u, float *v,
-               void *workspace, size_t ws_bytes, hipStream_t s) {
+               void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr) {
     int rc = check_jacobi_args(ctx, rows, cols, batch, window, iters, u, v, workspace,
                                ws_bytes);
     if (rc) return rc;
     return run_passes(ctx, rows, cols, batch, window, iters, alpha, warm, maybe_f32, u, v,
-                      carve(workspace, rows, cols, batch), s, batch);
+                      carve(workspace, rows, cols, batch), s, batch, fr);
 }
 
 // pairs [first, first + nb) of a `batch`-pair workspace w
 int jacobi_sub(hsflow_ctx *ctx, int rows, int cols, int nb, int first, int batch,
                int window, int iters, float alpha, bool warm, bool maybe_f32, float *u,
-               float *v, const Workspace &w, hipStream_t s) {
+               float *v, const Workspace &w, hipStream_t s, const Frames *fr) {
     const size_t off = (size_t)first * rows * cols;
     Workspace sub = w;
     sub.gpack = w.gpack + off;
@@ -430,8 +478,14 @@ int jacobi_sub(hsflow_ctx *ctx, int rows, int cols, int nb, int first, int batch
     sub.v2 = w.v2 + off;
     sub.flags = w.flags + first;
     // the split's halves run concurrently: the depth is chosen for the batch
+    // ... and the sub-batch's frames, for a fused first pass
+    Frames sf{};
+    if (fr) {
+        const size_t fo = off * (size_t)elem_size(fr->dtype);
+        sf = Frames{(const char *)fr->I0 + fo, (const char *)fr->I1 + fo, fr->dtype};
+    }
     return run_passes(ctx, rows, cols, nb, window, iters, alpha, warm, maybe_f32, u, v, sub,
-                      s, batch);
+                      s, batch, fr ? &sf : nullptr);
 }
 
 int gradients_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
@@ -456,6 +510,37 @@ int gradients_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in
     if (gy) HIP_TRY(ctx, hipMemcpyAsync(gy, w.gy, n * 4, hipMemcpyDeviceToDevice, s));
     if (gt) HIP_TRY(ctx, hipMemcpyAsync(gt, w.gt, n * 4, hipMemcpyDeviceToDevice, s));
     return HSFLOW_OK;
+}
+
+// A cold solve whose caller takes no gradient planes: K1, then the passes.
+// Where the plan is K4 with at least one full-depth pass and the frames are
+// u8, f16 or f32, K1 is fused into pass 0 instead (hsflow_strips.hip): the
+// fork moves in front of the prologue, and each chain zeroes its own flags,
+// runs the fused pass and K1f for its pairs on its side stream, so no kernel
+// of a split batch stays on the caller's stream between fork and join.
+// Same bits either way ((u, v), the packed plane and the flags).
+bool fuse_first(int dtype_in, bool maybe_f32, int rows, int cols, int batch, int window,
+                int iters) {
+    if (!g_first_fusion) return false;
+    if (dtype_in != HSFLOW_U8 && dtype_in != HSFLOW_F16 && dtype_in != HSFLOW_F32) return false;
+    if (window < 1 || window > HSFLOW_MAX_WINDOW || !sizes_ok(rows, cols, batch)) return false;
+    const PassPlan plan = plan_passes(window, maybe_f32, rows, cols, batch);
+    return plan.strip && iters >= plan.kb;
+}
+
+int cold_solve(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+               int cols, int batch, int window, int iters, float alpha, bool maybe_f32,
+               float *u, float *v, void *workspace, size_t ws_bytes, hipStream_t s) {
+    if (I0 && I1 && fuse_first(dtype_in, maybe_f32, rows, cols, batch, window, iters)) {
+        const Frames fr{I0, I1, dtype_in};
+        return jacobi_impl(ctx, rows, cols, batch, window, iters, alpha, false, maybe_f32, u, v,
+                           workspace, ws_bytes, s, &fr);
+    }
+    int rc = gradients_impl(ctx, I0, I1, dtype_in, rows, cols, batch, nullptr, nullptr, nullptr,
+                            workspace, ws_bytes, s);
+    if (rc) return rc;
+    return jacobi_impl(ctx, rows, cols, batch, window, iters, alpha, false, maybe_f32, u, v,
+                       workspace, ws_bytes, s);
 }
 
 int grow(hsflow_ctx *ctx, void **p, size_t *have, size_t need) {
@@ -631,10 +716,17 @@ int pyramid_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
                 L.R[l + 1], L.C[l + 1], ul, vl, L.R[l], L.C[l], batch, s);
             if (e != hipSuccess) return hip_fail(ctx, e, "upflow launch");
         }
-        rc = gradients_impl(ctx, l ? (const void *)(base + L.off[l][0]) : I0,
-                            l ? (const void *)(base + L.off[l][1]) : I1,
-                            l ? HSFLOW_F32 : dtype_in, L.R[l], L.C[l], batch, nullptr,
-                            nullptr, nullptr, ws, L.jac_bytes, s);
+        const void *f0 = l ? (const void *)(base + L.off[l][0]) : I0;
+        const void *f1 = l ? (const void *)(base + L.off[l][1]) : I1;
+        const int fdt = l ? HSFLOW_F32 : dtype_in;
+        if (!warm) {  // the coarsest level: a cold solve (K1 may fuse into pass 0)
+            rc = cold_solve(ctx, f0, f1, fdt, L.R[l], L.C[l], batch, window, iters, alpha,
+                            maybe_f32, ul, vl, ws, L.jac_bytes, s);
+            if (rc) return rc;
+            continue;
+        }
+        rc = gradients_impl(ctx, f0, f1, fdt, L.R[l], L.C[l], batch, nullptr, nullptr, nullptr,
+                            ws, L.jac_bytes, s);
         if (rc) return rc;
         rc = jacobi_impl(ctx, L.R[l], L.C[l], batch, window, iters, alpha, warm, maybe_f32,
                          ul, vl, ws, L.jac_bytes, s);
@@ -1091,6 +1183,17 @@ int hsflow_set_max_streams(int n) {
 
 int hsflow_max_streams(void) { return g_split_override; }
 
+int hsflow_set_first_pass_fusion(int on) {
+    g_first_fusion = on ? 1 : 0;
+    return HSFLOW_OK;
+}
+
+int hsflow_first_pass_fusion(void) { return g_first_fusion; }
+
+long long hsflow_first_pass_launches(void) {
+    return g_first_launches.load(std::memory_order_relaxed);
+}
+
 int hsflow_set_output_hugepages(int on) {
     return hsflow::g_output_hugepages.exchange(on ? 1 : 0);
 }
@@ -1123,17 +1226,15 @@ int hsflow_flow_device(const void *I0, const void *I1, int dtype_in, int rows, i
                        int batch, int window, int iters, float alpha, float *u, float *v,
                        void *workspace, size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
+    // K1 fused into the first pass where the plan allows (cold_solve); else
     // K1 for the whole batch, then the passes (split over the side streams).
-    // Running each half's K1 on its side stream instead measured 0.6 % slower
-    // (the halves' first passes start out of step; profiles/r05_k1_ab.txt)
-    int rc = gradients_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, nullptr,
-                            nullptr, nullptr, workspace, workspace_bytes,
-                            (hipStream_t)stream);
-    if (rc) return rc;
+    // Running each half's stand-alone K1 on its side stream instead measured
+    // 0.6 % slower (the halves' first passes start out of step;
+    // profiles/r05_k1_ab.txt).
     // 8-bit inputs always give exact packed gradients: skip the f32 variant
-    return jacobi_impl(nullptr, rows, cols, batch, window, iters, alpha, false,
-                       dtype_in != HSFLOW_U8, u, v, workspace, workspace_bytes,
-                       (hipStream_t)stream);
+    return cold_solve(nullptr, I0, I1, dtype_in, rows, cols, batch, window, iters, alpha,
+                      dtype_in != HSFLOW_U8, u, v, workspace, workspace_bytes,
+                      (hipStream_t)stream);
 }
 
 int hsflow_flow(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
@@ -1159,11 +1260,8 @@ int hsflow_flow(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, i
     if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
         return rc;
     const int dt0 = dtype_in;
-    rc = gradients_impl(ctx, in0, in1, dt0, rows, cols, 1, nullptr, nullptr, nullptr,
-                        ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
-    if (rc) return rc;
-    rc = jacobi_impl(ctx, rows, cols, 1, window, iters, (float)alpha, false,
-                     dt0 != HSFLOW_U8, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
+    rc = cold_solve(ctx, in0, in1, dt0, rows, cols, 1, window, iters, (float)alpha,
+                    dt0 != HSFLOW_U8, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
     {
         const float *srcs[2] = {du, dv};
@@ -1508,11 +1606,8 @@ int hsflow_flow_bgr(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, i
     hipError_t e = hsflow::launch_bgr2gray(db, rows, cols, 2, dg, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "bgr2gray launch");
     float *du = (float *)ctx->d_out, *dv = (float *)((char *)du + align_up(n * 4));
-    rc = gradients_impl(ctx, dg, dg + n, HSFLOW_U8, rows, cols, 1, nullptr, nullptr, nullptr,
-                        ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
-    if (rc) return rc;
-    rc = jacobi_impl(ctx, rows, cols, 1, window, iters, (float)alpha, false, false, du, dv,
-                     ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
+    rc = cold_solve(ctx, dg, dg + n, HSFLOW_U8, rows, cols, 1, window, iters, (float)alpha,
+                    false, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
     {
         const float *srcs[2] = {du, dv};

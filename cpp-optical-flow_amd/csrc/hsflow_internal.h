@@ -26,11 +26,27 @@ struct JacobiArgs {
                                // that do not fill the chip (fill_limited)
 };
 
+// What the fused first pass of a cold K4 solve takes besides JacobiArgs: the
+// frames it computes K1's gradients from, and K1's outputs, which it writes
+// (hsflow_strips.hip hs_jacobi_strip_first_kernel)
+struct FirstArgs {
+    const void *I0, *I1;  // the batch's frames (u8, f16 or f32), dense
+    uint32_t *gpack;      // packed gradients of every pixel
+    uint32_t *flags;      // per pair; zero before the launch unless the frames are u8
+    int wide;             // the frames' base addresses allow one load per column pair
+};
+
 // K1 (+ K1f): packed gradients and flags; the f32 planes for every pair
 // when `planes` (the gradients API), else only for the flagged pairs
 hipError_t launch_gradients(const void *I0, const void *I1, int dtype_in, int rows,
                             int cols, int batch, uint32_t *gpack, float *gx, float *gy,
                             float *gt, uint32_t *flags, bool planes, hipStream_t s);
+// K1f alone: the f32 planes of the pairs `flags` marks (after a fused first
+// pass, which writes the packed plane and the flags itself); nothing to do
+// for u8 frames
+hipError_t launch_gradients_f32(const void *I0, const void *I1, int dtype_in, int rows,
+                                int cols, int batch, float *gx, float *gy, float *gt,
+                                const uint32_t *flags, hipStream_t s);
 hipError_t launch_jacobi(JacobiArgs a, int W, int KB, hipStream_t s);
 // config 5 pyramid (hsflow_pyramid.hip); dtype as HSFLOW_U8/F32/F16
 hipError_t launch_pyrdown(const void *src, int dtype, int rows, int cols, int batch,
@@ -64,6 +80,10 @@ hipError_t launch_median(const float *u, const float *v, int rows, int cols, int
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);
 hipError_t launch_jacobi_strip(JacobiArgs a, int W, int KB, int seg_rows, hipStream_t s);
+// pass 0 of a cold solve with K1 fused in (a.u_in / a.v_in ignored: u = v = 0);
+// dtype_in HSFLOW_U8, F16 or F32
+hipError_t launch_jacobi_strip_first(JacobiArgs a, FirstArgs f, int dtype_in, int W, int KB,
+                                     int seg_rows, hipStream_t s);
 int strip_seg_rows(int W, int KB, int rows, int cols, int batch, int slots, int *nseg,
                    int *nstrips, int override_rows);
 bool strip_fills(int W, int KB, int rows, int cols, int batch, int slots);

@@ -1087,6 +1087,27 @@ hipError_t launch_gradients(const void *I0, const void *I1, int dtype_in, int ro
     return hipGetLastError();
 }
 
+template <typename T>
+static void launch_gradients_f32_t(const void *I0, const void *I1, int rows, int cols, int batch,
+                                   float *gx, float *gy, float *gt, const uint32_t *flags,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(hs_gradients_f32_kernel<T>, dim3(kK1fBlocks, batch), dim3(256), 0, s,
+                       (const T *)I0, (const T *)I1, rows, cols, gx, gy, gt, flags);
+}
+
+hipError_t launch_gradients_f32(const void *I0, const void *I1, int dtype_in, int rows,
+                                int cols, int batch, float *gx, float *gy, float *gt,
+                                const uint32_t *flags, hipStream_t s) {
+    if (dtype_in == 0) return hipSuccess;  // 8-bit frames: no pair is ever flagged
+    if (dtype_in == 2)
+        launch_gradients_f32_t<double>(I0, I1, rows, cols, batch, gx, gy, gt, flags, s);
+    else if (dtype_in == 3)
+        launch_gradients_f32_t<_Float16>(I0, I1, rows, cols, batch, gx, gy, gt, flags, s);
+    else
+        launch_gradients_f32_t<float>(I0, I1, rows, cols, batch, gx, gy, gt, flags, s);
+    return hipGetLastError();
+}
+
 template <int W, int KB>
 static hipError_t launch_jacobi_t(JacobiArgs a, hipStream_t s) {
     constexpr int OX = 64 - KB * (W - 1), OY = kRowsPacked - KB * (W - 1);

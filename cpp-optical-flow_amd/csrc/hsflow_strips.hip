@@ -202,14 +202,104 @@ __device__ __forceinline__ void hrow(f2v u, f2v v, f2v &hu, f2v &hv) {
     }
 }
 
+// ---- the fused first pass: frames in place of (u, v, g) ----
+// FT = the frames' element type (void: an ordinary pass).  A row of a frame
+// is kept as loaded (one or two raw words per lane) and converted where it
+// is used, so the load stays in flight for the D steps it runs ahead.
+template <typename FT> struct FrameElem { static constexpr int size = sizeof(FT); };
+template <> struct FrameElem<void> { static constexpr int size = 4; };
+
+struct FrameIn {
+    u2v i0, i1;  // I0 row t + dir (the Sobel's leading row), I1 row t
+};
+
+// the lane's column pair of one frame row; WIDE: one load (f32 8 bytes, f16
+// 4: even width and a base aligned to it)
+template <typename FT, bool WIDE>
+__device__ __forceinline__ u2v ldf(__amdgpu_buffer_rsrc_t r, int vo_e, int vo_o, int so) {
+    if constexpr (std::is_same<FT, float>::value) {
+        if constexpr (WIDE) return __builtin_amdgcn_raw_buffer_load_b64(r, vo_e, so, 0);
+        return u2v{__builtin_amdgcn_raw_buffer_load_b32(r, vo_e, so, 0),
+                   __builtin_amdgcn_raw_buffer_load_b32(r, vo_o, so, 0)};
+    } else if constexpr (std::is_same<FT, _Float16>::value) {
+        if constexpr (WIDE) return u2v{__builtin_amdgcn_raw_buffer_load_b32(r, vo_e, so, 0), 0u};
+        return u2v{__builtin_amdgcn_raw_buffer_load_b16(r, vo_e, so, 0),
+                   __builtin_amdgcn_raw_buffer_load_b16(r, vo_o, so, 0)};
+    } else {
+        return u2v{__builtin_amdgcn_raw_buffer_load_b8(r, vo_e, so, 0),
+                   __builtin_amdgcn_raw_buffer_load_b8(r, vo_o, so, 0)};
+    }
+}
+// K1's (F)p[x]; an out-of-range load's 0 converts to 0 in every type
+template <typename FT, bool WIDE> __device__ __forceinline__ f2v cvtf(u2v w) {
+    if constexpr (std::is_same<FT, float>::value) {
+        return f2v{__uint_as_float(w.x), __uint_as_float(w.y)};
+    } else if constexpr (std::is_same<FT, _Float16>::value) {
+        const uint32_t e = w.x & 0xFFFFu, o = WIDE ? w.x >> 16 : w.y & 0xFFFFu;
+        return f2v{(float)__builtin_bit_cast(_Float16, (unsigned short)e),
+                   (float)__builtin_bit_cast(_Float16, (unsigned short)o)};
+    } else {
+        return f2v{(float)(w.x & 0xFFu), (float)(w.y & 0xFFu)};
+    }
+}
+
+// The Sobel's column neighbours come from the neighbouring lanes (from_left,
+// from_right).  Reflect-101 at the image's first and last column (K1's
+// reflect101 for an overshoot of 1) needs no select: the lane that holds
+// column -1, and the one that holds column `cols`, load I0's reflected
+// column there (column 1 and cols - 2; a one-column image: column 0) -- a
+// per-lane load offset, set once.  What those lanes compute for their own
+// columns is outside the image and zeroed with every other outside column.
+// A strip's outermost lanes have no neighbour in the wave and read 0: a
+// wrong operator in strip column 0 or 127 spreads by W / 2 columns per
+// iteration from the second on, so after KB of them it has reached column
+// (KB - 1) W / 2 <= HLc - W / 2 from either end at most (w = 5, KB 6: 10 of
+// the 12 halo columns) -- halo columns, which are never stored (NaN spreads
+// the same way, through the window sums only).
+//
+// hdiff: right minus left neighbour of the lane's two columns in row r;
+// vsobel: the Sobel's column sum (l + 2 c) + r of d, the difference of the
+// rows below and above (a neighbouring column's difference is the
+// neighbouring lane's: the same subtraction, the same bits).
+__device__ __forceinline__ f2v hdiff(f2v r) {
+    return f2v{r.y - from_left(r.y), from_right(r.x) - r.x};
+}
+__device__ __forceinline__ f2v vsobel(f2v d) {
+    const f2v t = f2v{2.f, 2.f} * d;
+    return f2v{(from_left(d.y) + t.x) + d.y, (d.x + t.y) + from_right(d.x)};
+}
+
+// K1's integrality test in three operations per pixel: x is an integer in
+// [0, 255] iff its clamp to that range, rounded to an integer, is x again
+// (NaN fails; the 0 of a pixel outside the image passes)
+__device__ __forceinline__ bool integral_u8(float x) {
+    return __builtin_rintf(__builtin_amdgcn_fmed3f(x, 0.f, 255.f)) == x;
+}
+
 }  // namespace
 
 // Segment body: rows [a, b) of strip columns [c0, c0 + 128) of one pair,
 // streamed downwards.  U = unroll period (multiple of the operator ring
 // KB*AR, of 2 and of D).
-template <int W, int KB, int D, int U, bool X2, bool G32, bool WT>
-__device__ __forceinline__ void strip_body(const JacobiArgs &p, size_t pbase, int plane_bytes,
-                                           int c0, int a, int b, int dir) {
+//
+// FT != void: the first pass of a cold solve with K1 fused in.  The input
+// state is u = v = 0 and the row's operator comes from the frames: the wave
+// streams I0 one row ahead of the ordinary prefetch and keeps the Sobel's
+// three-row neighbourhood in registers (rp, rz and the arriving row), forms
+// Ix, Iy, It with K1's arithmetic term for term (hsflow_kernels.hip
+// sobel_at) and builds the operator from these f32 values -- for integral
+// frames exactly the unpacked word's, else exactly K1f's planes, so the
+// pass gives the bits of an ordinary pass 0 either way.  It also writes
+// K1's outputs: the packed word of the rows and lanes it stores (every
+// pixel of the pair exactly once) and, returned for the kernel's one atomic
+// per wave, whether any of its pixels fails K1's integrality test.
+template <int W, int KB, int D, int U, bool X2, bool G32, bool WT, typename FT = void>
+__device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, int plane_bytes,
+                                           int c0, int a, int b, int dir,
+                                           const FirstArgs &fa = FirstArgs{}) {
+    constexpr bool FIRST = !std::is_void<FT>::value;
+    constexpr int ES = FrameElem<FT>::size;
+    static_assert(!(FIRST && G32), "the first pass builds its operator from the frames");
     constexpr int A = W - W / 2 - 1, AR = W / 2;
     static_assert(A == AR, "K4 is built for odd windows");
     constexpr int L = KB * AR;  // operator ring: the rows t - AR .. t - KB AR
@@ -252,6 +342,26 @@ __device__ __forceinline__ void strip_body(const JacobiArgs &p, size_t pbase, in
                                               0x00020000);
     rs.vo = __builtin_amdgcn_make_buffer_rsrc((void *)(p.v_out + pbase), 0, plane_bytes,
                                               0x00020000);
+    // first pass: the pair's frames (ES bytes per element) and its packed plane
+    const int fplane_bytes = plane_bytes / 4 * ES;
+    const __amdgpu_buffer_rsrc_t rs_i0 = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)((const char *)fa.I0 + pbase * ES), 0, FIRST ? fplane_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_i1 = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)((const char *)fa.I1 + pbase * ES), 0, FIRST ? fplane_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_go = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)(fa.gpack + pbase), 0, FIRST ? plane_bytes : 0, 0x00020000);
+    const int fl_e = ce ? gce * ES : kOOB;
+    const int fl_o = co ? (gce + 1) * ES : kOOB;
+    // I0: columns -1 and `cols` read their reflection (hdiff above).  With
+    // one load per column pair (ldf's WIDE: f16 / f32 at an even width) the
+    // pair that starts at column 0, or at cols - 2, has the reflected column
+    // in the right half
+    constexpr bool FW = X2 && !std::is_same<FT, uint8_t>::value;
+    const int refl_lo = cols > 1 ? 1 : 0, refl_hi = cols > 1 ? cols - 2 : 0;
+    int f0_e = fl_e, f0_o = fl_o;
+    if (gce == -2) (FW ? f0_e : f0_o) = (FW ? 0 : refl_lo) * ES;
+    if (gce == cols) f0_e = refl_hi * ES;
+    if (gce + 1 == cols) f0_o = refl_hi * ES;
 
     // The stream: rows a - KB A .. b - 1 + KB AR, downwards (dir = 1) from
     // an even first row (segment starts are even, and so is KB A) or upwards
@@ -280,9 +390,32 @@ __device__ __forceinline__ void strip_body(const JacobiArgs &p, size_t pbase, in
     };
     auto issue = [&](RowIn<G32> &d, int r) { load_row<X2, G32>(d, rs, ld_e, ld_o, row_off(r)); };
 
+    // first pass: the slot of row r holds I0's row r + dir and I1's row r;
+    // rp, rz = I0's rows r - dir and r, converted (the Sobel's ring)
+    const int frow_bytes = cols * ES;
+    auto frow_off = [&](int r) {
+        return (unsigned)r < (unsigned)rows ? r * frow_bytes : (int)0x80000000;
+    };
+    auto issue_f = [&](FrameIn &d, int r) {
+        d.i0 = ldf<FT, X2>(rs_i0, f0_e, f0_o, frow_off(r + dir));
+        d.i1 = ldf<FT, X2>(rs_i1, fl_e, fl_o, frow_off(r));
+    };
+
     RowIn<G32> buf[D];
+    FrameIn fbuf[D];
+    f2v rp, rz;
+    bool bad = false;
+    if constexpr (FIRST) {
+        const u2v w_p = ldf<FT, X2>(rs_i0, f0_e, f0_o, frow_off(t_first - dir));
+        const u2v w_z = ldf<FT, X2>(rs_i0, f0_e, f0_o, frow_off(t_first));
 #pragma unroll
-    for (int k = 0; k < D; ++k) issue(buf[k], t_first + dir * k);
+        for (int k = 0; k < D; ++k) issue_f(fbuf[k], t_first + dir * k);
+        rp = cvtf<FT, X2>(w_p);
+        rz = cvtf<FT, X2>(w_z);
+    } else {
+#pragma unroll
+        for (int k = 0; k < D; ++k) issue(buf[k], t_first + dir * k);
+    }
 
     const f2v z = {0.f, 0.f};
     f2v OX[L], OY[L], OT[L];
@@ -318,22 +451,40 @@ __device__ __forceinline__ void strip_body(const JacobiArgs &p, size_t pbase, in
     // interior blocks of every stream; round 6, a single 4K pair's lone
     // waves issue every instruction, SALU included)
     const int drb = dir * row_bytes;
+    const int fdrb = dir * frow_bytes;
     auto block = [&](int tb, auto rowe_c, auto fill_c, auto plain_c) {
         constexpr bool ROWE = decltype(rowe_c)::value;
         constexpr int FILL = decltype(fill_c)::value;
         constexpr bool PLAIN = decltype(plain_c)::value;
         // byte offset of the block's first stage-KB row (PLAIN blocks)
         const int ob = PLAIN ? (tb - dir * (KB * AR)) * row_bytes : 0;
+        const int fob = PLAIN ? (tb - dir * (KB * AR)) * frow_bytes : 0;  // the same, frames
 #pragma unroll
         for (int k = 0; k < U; ++k) {
             const int t = tb + dir * k;
             // 1. this row's input (loaded D steps ago), then the load of
             //    the row D steps ahead into the freed slot
-            const RowIn<G32> cur = buf[k % D];
-            if constexpr (PLAIN)
-                load_row<X2, G32>(buf[k % D], rs, ld_e, ld_o, ob + (k + KB * AR + D) * drb);
-            else
-                issue(buf[k % D], t + dir * D);
+            RowIn<G32> cur;
+            FrameIn fcur;
+            if constexpr (FIRST) {
+                fcur = fbuf[k % D];
+                cur.u = z;
+                cur.v = z;
+                if constexpr (PLAIN) {
+                    fbuf[k % D].i0 =
+                        ldf<FT, X2>(rs_i0, f0_e, f0_o, fob + (k + KB * AR + D + 1) * fdrb);
+                    fbuf[k % D].i1 =
+                        ldf<FT, X2>(rs_i1, fl_e, fl_o, fob + (k + KB * AR + D) * fdrb);
+                } else {
+                    issue_f(fbuf[k % D], t + dir * D);
+                }
+            } else {
+                cur = buf[k % D];
+                if constexpr (PLAIN)
+                    load_row<X2, G32>(buf[k % D], rs, ld_e, ld_o, ob + (k + KB * AR + D) * drb);
+                else
+                    issue(buf[k % D], t + dir * D);
+            }
             // 2. level-0 horizontal sums of row t
             f2v hu, hv;
             hrow<W>(cur.u, cur.v, hu, hv);
@@ -405,7 +556,59 @@ __device__ __forceinline__ void strip_body(const JacobiArgs &p, size_t pbase, in
                 }
             }
             // 4. operator of row t, into the slot stage KB has just read
-            row_op<G32>(a2c, cur, OX[k % L], OY[k % L], OT[k % L]);
+            if constexpr (FIRST) {
+                // K1 at row t: I0's rows t - 1, t, t + 1 (m, rz, q) and I1's row t
+                const f2v nx = cvtf<FT, X2>(fcur.i0), i1 = cvtf<FT, X2>(fcur.i1);
+                f2v m = dir > 0 ? rp : nx, q = dir > 0 ? nx : rp;
+                if constexpr (!PLAIN) {
+                    // reflect-101 at the image's first and last row (one row:
+                    // onto itself); rows outside the image: zero gradients
+                    // (rz and i1 are 0 there already)
+                    const f2v m0 = m, q0 = q;
+                    if (t == 0) m = rows > 1 ? q0 : rz;
+                    if (t == rows - 1) q = rows > 1 ? m0 : rz;
+                    if ((unsigned)t >= (unsigned)rows) {
+                        m = z;
+                        q = z;
+                    }
+                }
+                // sobel_at: dx = (m_p - m_m) + 2 (z_p - z_m) + (p_p - p_m),
+                // dy = (p_m - m_m) + 2 (p_0 - m_0) + (p_p - m_p), dt = nxt - z_0
+                const f2v dx = (hdiff(m) + f2v{2.f, 2.f} * hdiff(rz)) + hdiff(q);
+                const f2v dy = vsobel(q - m);
+                const f2v dt = i1 - rz;
+                RowIn<true> g;
+                // columns outside the image: zero gradients (the reflected
+                // columns and their neighbours are not)
+                g.gx = f2v{ce ? dx.x : 0.f, co ? dx.y : 0.f};
+                g.gy = f2v{ce ? dy.x : 0.f, co ? dy.y : 0.f};
+                g.gt = f2v{ce ? dt.x : 0.f, co ? dt.y : 0.f};
+                if constexpr (!std::is_same<FT, uint8_t>::value) {
+                    // K1's test on both frames (the reflected columns are
+                    // pixels of the pair too; 0 outside the image passes)
+                    // (no short-circuit: the step stays one basic block for
+                    // the scheduler)
+                    const bool k0 = integral_u8(rz.x), k1 = integral_u8(rz.y);
+                    const bool k2 = integral_u8(i1.x), k3 = integral_u8(i1.y);
+                    bad |= !(k0 & k1 & k2 & k3);
+                }
+                const bool tin = t >= a && t < b;
+                const int gso =
+                    PLAIN ? ob + (k + KB * AR) * drb : (tin ? t * row_bytes : (int)0x80000000);
+                const uint32_t ge = pack_grad((int)g.gx.x, (int)g.gy.x, (int)g.gt.x);
+                const uint32_t go = pack_grad((int)g.gx.y, (int)g.gy.y, (int)g.gt.y);
+                if constexpr (X2) {
+                    __builtin_amdgcn_raw_buffer_store_b64(u2v{ge, go}, rs_go, st_e, gso, 0);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b32(ge, rs_go, st_e, gso, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(go, rs_go, st_o, gso, 0);
+                }
+                row_op<true>(a2c, g, OX[k % L], OY[k % L], OT[k % L]);
+                rp = rz;
+                rz = nx;
+            } else {
+                row_op<G32>(a2c, cur, OX[k % L], OY[k % L], OT[k % L]);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -429,8 +632,11 @@ __device__ __forceinline__ void strip_body(const JacobiArgs &p, size_t pbase, in
     };
     auto plain = [&](int tb) {
         const int e = tb + dir * (U - 1);
-        return inside(tb) && within(tb + dir * D, e + dir * D, 0, rows) &&
-               within(tb - dir * (KB * AR), e - dir * (KB * AR), a, b);
+        // (first pass: I0 runs one row further ahead, and the rows whose
+        // packed word the block stores are its own, tb .. e)
+        return inside(tb) && within(tb + dir * D, e + dir * (D + (FIRST ? 1 : 0)), 0, rows) &&
+               within(tb - dir * (KB * AR), e - dir * (KB * AR), a, b) &&
+               (!FIRST || within(tb, e, a, b));
     };
     const int nblk = (nsteps + U - 1) / U;
     int tb = t_first, ib = 2;
@@ -446,6 +652,7 @@ __device__ __forceinline__ void strip_body(const JacobiArgs &p, size_t pbase, in
             block(tb, std::false_type{}, F0{}, std::true_type{});
     }
     for (; ib < nblk; tb += dir * U, ++ib) block(tb, std::true_type{}, F0{}, NP{});
+    return bad;
 }
 
 // ---------------------------------------------------------------- kernel
@@ -493,6 +700,46 @@ __global__ __launch_bounds__(64, WPE) void hs_jacobi_strip_kernel(const JacobiAr
     }
 }
 
+// Pass 0 of a cold solve with K1 fused in (strip_body, FT): the same waves
+// over the same segments and strips.  Besides (u, v) of iteration KB it
+// leaves the pair's packed gradients and its flag as K1 does: 8-bit frames a
+// plain 0 from one wave of the pair, the others one atomic OR per wave that
+// saw a non-integral pixel (the flags are zero before the launch).
+template <int W, int KB, int D, int U, int WPE, bool WT, typename FT>
+__global__ __launch_bounds__(64, WPE) void hs_jacobi_strip_first_kernel(const JacobiArgs p,
+                                                                        const FirstArgs f) {
+    const int nblk = gridDim.x;
+    const int lin = blockIdx.x;
+    const int qn = nblk >> 3, rem = nblk & 7, xcd = lin & 7;
+    const int logical = xcd * qn + min(xcd, rem) + (lin >> 3);
+    const int nstrips = p.tiles_x, nseg = p.tiles_y;
+    const int per_pair = nstrips * nseg;
+    const int pair = logical / per_pair;
+    if (pair >= p.batch) return;
+    const int r = logical - pair * per_pair;
+    const int seg = r / nstrips, sx = r - seg * nstrips;
+    constexpr int A = W - W / 2 - 1, AR = W / 2;
+    constexpr int HLc = KB * A + ((KB * A) & 1), HRc = KB * AR + ((KB * AR) & 1);
+    constexpr int OX = 128 - HLc - HRc;
+    const int c0 = sx * OX - HLc;
+    const int a = seg * p.seg_rows;
+    const int b = min(p.rows, a + p.seg_rows);
+    const size_t pbase = (size_t)pair * (size_t)p.rows * (size_t)p.cols;
+    const int plane_bytes = p.rows * p.cols * 4;
+    const int dir = (seg & 1) ? -1 : 1;
+    bool bad;
+    if ((p.cols & 1) == 0 && f.wide)
+        bad = strip_body<W, KB, D, U, true, false, WT, FT>(p, pbase, plane_bytes, c0, a, b, dir, f);
+    else
+        bad = strip_body<W, KB, D, U, false, false, WT, FT>(p, pbase, plane_bytes, c0, a, b, dir,
+                                                            f);
+    if constexpr (std::is_same<FT, uint8_t>::value) {
+        if (r == 0 && (threadIdx.x & 63) == 0) f.flags[pair] = 0u;
+    } else if (__any(bad) && (threadIdx.x & 63) == 0) {
+        atomicOr(&f.flags[pair], 1u);
+    }
+}
+
 // ------------------------------------------------------------- launcher
 namespace {
 // D rows of prefetch, U = KB AR steps per unrolled block, WPE waves per SIMD
@@ -512,6 +759,44 @@ void launch_cfg(const JacobiArgs &a, dim3 grd, bool wt, hipStream_t s) {
     else
         hipLaunchKernelGGL((hs_jacobi_strip_kernel<W, KB, C::D, C::U, C::WPE, false>), grd,
                            dim3(64), 0, s, a);
+}
+
+template <int W, int KB, typename FT>
+void launch_first_t(const JacobiArgs &a, const FirstArgs &f, dim3 grd, bool wt, hipStream_t s) {
+    using C = StripCfg<W, KB>;
+    if (wt)
+        hipLaunchKernelGGL((hs_jacobi_strip_first_kernel<W, KB, C::D, C::U, C::WPE, true, FT>),
+                           grd, dim3(64), 0, s, a, f);
+    else
+        hipLaunchKernelGGL((hs_jacobi_strip_first_kernel<W, KB, C::D, C::U, C::WPE, false, FT>),
+                           grd, dim3(64), 0, s, a, f);
+}
+
+template <int W, int KB>
+hipError_t launch_first_cfg(const JacobiArgs &a, const FirstArgs &f, int dtype_in, dim3 grd,
+                            bool wt, hipStream_t s) {
+    if (dtype_in == 0)  // HSFLOW_U8
+        launch_first_t<W, KB, uint8_t>(a, f, grd, wt, s);
+    else if (dtype_in == 3)  // HSFLOW_F16
+        launch_first_t<W, KB, _Float16>(a, f, grd, wt, s);
+    else if (dtype_in == 1)  // HSFLOW_F32
+        launch_first_t<W, KB, float>(a, f, grd, wt, s);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// the launch geometry of a K4 pass: fills a's segment and tile fields
+bool strip_grid(JacobiArgs &a, int W, int KB, int seg_rows, dim3 *grd) {
+    int nseg = 0, nstrips = 0;
+    a.seg_rows = strip_seg_rows(W, KB, a.rows, a.cols, a.batch, 1, &nseg, &nstrips,
+                                seg_rows > 0 ? seg_rows : 84);
+    a.tiles_x = nstrips;
+    a.tiles_y = nseg;
+    const long waves = (long)nstrips * nseg * a.batch;
+    if (waves <= 0 || waves > 0x7FFFFFFFL) return false;
+    *grd = dim3((unsigned)waves, 1, 1);
+    return true;
 }
 }  // namespace
 
@@ -631,14 +916,8 @@ bool strip_fills(int W, int KB, int rows, int cols, int batch, int slots) {
 // One K4 pass of `a.batch` pairs in segments of `seg_rows` rows (the
 // caller's choice: strip_seg_rows over every pair in flight).
 hipError_t launch_jacobi_strip(JacobiArgs a, int W, int KB, int seg_rows, hipStream_t s) {
-    int nseg = 0, nstrips = 0;
-    a.seg_rows = strip_seg_rows(W, KB, a.rows, a.cols, a.batch, 1, &nseg, &nstrips,
-                                seg_rows > 0 ? seg_rows : 84);
-    a.tiles_x = nstrips;
-    a.tiles_y = nseg;
-    const long waves = (long)nstrips * nseg * a.batch;
-    if (waves <= 0 || waves > 0x7FFFFFFFL) return hipErrorInvalidValue;
-    dim3 grd((unsigned)waves, 1, 1);
+    dim3 grd;
+    if (!strip_grid(a, W, KB, seg_rows, &grd)) return hipErrorInvalidValue;
     const bool wt = a.write_through != 0;
     if (W == 5 && KB == 6)
         launch_cfg<5, 6>(a, grd, wt, s);
@@ -651,6 +930,25 @@ hipError_t launch_jacobi_strip(JacobiArgs a, int W, int KB, int seg_rows, hipStr
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+// The same pass as the first of a cold solve, K1 fused in.  One load per
+// column pair of a frame row needs the pair's rows aligned to it: an even
+// width (the kernel's test) and frames that start at a multiple of two
+// elements; other frames take the body that loads column by column.
+hipError_t launch_jacobi_strip_first(JacobiArgs a, FirstArgs f, int dtype_in, int W, int KB,
+                                     int seg_rows, hipStream_t s) {
+    dim3 grd;
+    if (!strip_grid(a, W, KB, seg_rows, &grd)) return hipErrorInvalidValue;
+    a.u_in = a.v_in = nullptr;
+    const uintptr_t es2 = dtype_in == 0 ? 1 : (dtype_in == 3 ? 4 : 8);
+    f.wide = (((uintptr_t)f.I0 | (uintptr_t)f.I1) & (es2 - 1)) == 0 ? 1 : 0;
+    const bool wt = a.write_through != 0;
+    if (W == 5 && KB == 6) return launch_first_cfg<5, 6>(a, f, dtype_in, grd, wt, s);
+    if (W == 5 && KB == 5) return launch_first_cfg<5, 5>(a, f, dtype_in, grd, wt, s);
+    if (W == 5 && KB == 4) return launch_first_cfg<5, 4>(a, f, dtype_in, grd, wt, s);
+    if (W == 3 && KB == 8) return launch_first_cfg<3, 8>(a, f, dtype_in, grd, wt, s);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace hsflow

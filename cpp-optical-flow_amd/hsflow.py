@@ -73,6 +73,8 @@ EXPORTS = (
     "hsflow_flow_median_device", "hsflow_flow_warped_median_device",
     "hsflow_flow_warped_median", "hsflow_flow_bidir_median_device",
     "hsflow_flow_bidir_median",
+    "hsflow_set_first_pass_fusion", "hsflow_first_pass_fusion",
+    "hsflow_first_pass_launches",
 )
 
 
@@ -141,6 +143,10 @@ def lib():
     L.hsflow_set_output_hugepages.argtypes = [i]
     L.hsflow_set_output_hugepages.restype = i
     L.hsflow_max_streams.argtypes = []
+    L.hsflow_set_first_pass_fusion.argtypes = [i]
+    L.hsflow_first_pass_fusion.argtypes = []
+    L.hsflow_first_pass_launches.argtypes = []
+    L.hsflow_first_pass_launches.restype = ctypes.c_longlong
     L.hsflow_set_jacobi_kernel.argtypes = [i]
     L.hsflow_set_strip_rows.argtypes = [i]
     L.hsflow_jacobi_kernel_name.argtypes = [i, i, i, i]
@@ -974,6 +980,40 @@ class max_streams_as:
 
     def __exit__(self, *exc):
         set_max_streams(self.prev)
+        return False
+
+
+def set_first_pass_fusion(on: bool):
+    """A cold K4 solve computes its gradients inside its first pass (True,
+    the default) or in K1 in front of it (False); identical bits
+    (include/hsflow.h)."""
+    _check(lib().hsflow_set_first_pass_fusion(int(bool(on))))
+
+
+def first_pass_fusion() -> bool:
+    """The current set_first_pass_fusion setting."""
+    return bool(lib().hsflow_first_pass_fusion())
+
+
+def first_pass_launches() -> int:
+    """Fused first passes launched by this process so far (one per side-stream
+    chain of a fused solve); its difference across a call tells whether it fused."""
+    return int(lib().hsflow_first_pass_launches())
+
+
+class first_pass_fusion_as:
+    """Context manager: set_first_pass_fusion(on) inside, the previous setting after."""
+
+    def __init__(self, on: bool):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = first_pass_fusion()
+        set_first_pass_fusion(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_first_pass_fusion(self.prev)
         return False
 
 

@@ -130,7 +130,10 @@ int hsflow_gradients(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
  * hsflow_workspace_bytes(rows, cols, batch) bytes, 256-byte aligned. */
 size_t hsflow_workspace_bytes(int rows, int cols, int batch);
 
-/* Full solve: gradients + `iters` Jacobi iterations from u = v = 0. */
+/* Full solve: gradients + `iters` Jacobi iterations from u = v = 0.
+ * u, v and the workspace must not overlap the frames or each other: the
+ * first Jacobi pass may read the frames while it writes u and v
+ * (hsflow_set_first_pass_fusion). */
 int hsflow_flow_device(const void *I0, const void *I1, int dtype_in, int rows,
                        int cols, int batch, int window, int iters, float alpha,
                        float *u, float *v, void *workspace, size_t workspace_bytes,
@@ -188,6 +191,22 @@ int hsflow_strip_seg_rows(int rows, int cols, int batch, int window);
  * hsflow_max_streams returns the current setting. */
 int hsflow_set_max_streams(int n);
 int hsflow_max_streams(void);
+
+/* A cold solve that takes no gradient planes (hsflow_flow_device, the
+ * host-buffer hsflow_flow / hsflow_flow_bgr, the pyramid's coarsest level)
+ * whose passes run K4, with at least one full-depth pass, on u8, f16 or f32
+ * frames computes the gradients inside its first pass instead of in a
+ * kernel of their own in front of it (K1).  on = 1 (default) fuses, 0 runs
+ * K1 first.  (u, v), the workspace's packed gradients and its flags have
+ * identical bits either way.  Process-wide; not thread-safe against running
+ * solves.  hsflow_first_pass_fusion returns the current setting. */
+int hsflow_set_first_pass_fusion(int on);
+int hsflow_first_pass_fusion(void);
+/* Fused first passes this process has launched so far: one per stream-ordered
+ * chain of a solve that took the fused path (a batch split over n side
+ * streams counts n).  For tests and profiles: the difference across a call
+ * tells whether it fused. */
+long long hsflow_first_pass_launches(void);
 
 /* Huge-page advice on f64 outputs of the host-buffer calls (hsflow_flow,
  * hsflow_flow_bgr, hsflow_flow_pyramid, hsflow_flow_multi with
