@@ -1041,6 +1041,236 @@ int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
     return download_planes(ctx, srcs, dsts, np, rows, cols, dtype_out, out_step);
 }
 
+// ---- frame warp and frame interpolation ------------------------------------
+// byte ranges [a, a + na) and [b, b + nb) share a byte (a null range: none)
+bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+struct ByteRange {
+    const void *p;
+    size_t n;
+};
+
+// no output shares a byte with an input or with another output
+bool outputs_disjoint(const ByteRange *in, int n_in, const ByteRange *out, int n_out) {
+    for (int o = 0; o < n_out; ++o) {
+        for (int i = 0; i < n_in; ++i)
+            if (bytes_overlap(out[o].p, out[o].n, in[i].p, in[i].n)) return false;
+        for (int q = o + 1; q < n_out; ++q)
+            if (bytes_overlap(out[o].p, out[o].n, out[q].p, out[q].n)) return false;
+    }
+    return true;
+}
+
+int warp_image_impl(hsflow_ctx *ctx, const void *I, int dtype_in, int rows, int cols, int batch,
+                    const float *u, const float *v, float *out, uint8_t *oof, hipStream_t s) {
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!device_dtype_ok(dtype_in))
+        return fail(ctx, HSFLOW_ERR_ARG, "device input dtype must be U8, F16, F32 or F64");
+    if (!I || !u || !v || !out) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    const size_t n = (size_t)rows * cols * batch;
+    const ByteRange in[3] = {{I, n * elem_size(dtype_in)}, {u, n * 4}, {v, n * 4}};
+    const ByteRange outs[2] = {{out, n * 4}, {oof, n}};
+    if (!outputs_disjoint(in, 3, outs, 2))
+        return fail(ctx, HSFLOW_ERR_ARG, "warp outputs overlap the inputs or each other");
+    hipError_t e = hsflow::launch_warp_image(I, dtype_in, rows, cols, batch, u, v, out, oof, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "warp image launch");
+    return HSFLOW_OK;
+}
+
+// times (host), nt and the output type of an interpolation
+int check_interp_args(hsflow_ctx *ctx, const float *times, int nt, int dtype_out, bool host) {
+    if (nt < 1 || nt > HSFLOW_MAX_TIMES)
+        return fail(ctx, HSFLOW_ERR_ARG, "nt %d outside [1, %d]", nt, HSFLOW_MAX_TIMES);
+    if (!times) return fail(ctx, HSFLOW_ERR_ARG, "null times");
+    for (int k = 0; k < nt; ++k)
+        if (!(times[k] >= 0.0f && times[k] <= 1.0f))  // negated: NaN fails
+            return fail(ctx, HSFLOW_ERR_ARG, "time %d (%g) outside [0, 1]", k, (double)times[k]);
+    if (dtype_out != HSFLOW_F32 && dtype_out != HSFLOW_U8 && !(host && dtype_out == HSFLOW_F64))
+        return fail(ctx, HSFLOW_ERR_ARG, host ? "output dtype must be U8, F32 or F64"
+                                              : "device output dtype must be U8 or F32");
+    return HSFLOW_OK;
+}
+
+// KI on checked arguments: trusted zeroed stream-ordered, then one launch
+int frame_interp_run(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                     int cols, int batch, const float *uf, const float *vf, const float *ub,
+                     const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                     const float *times, int nt, void *out, int dtype_out, uint8_t *flags,
+                     uint32_t *trusted, hipStream_t s) {
+    if (trusted) HIP_TRY(ctx, hipMemsetAsync(trusted, 0, (size_t)batch * nt * 4, s));
+    hipError_t e = hsflow::launch_frame_interp(I0, I1, dtype_in, rows, cols, batch, uf, vf, ub, vb,
+                                               mask_f, mask_b, times, nt, out,
+                                               dtype_out == HSFLOW_U8, flags, trusted, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "frame interpolation launch");
+    return HSFLOW_OK;
+}
+
+int frame_interp_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                      int cols, int batch, const float *uf, const float *vf, const float *ub,
+                      const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                      const float *times, int nt, void *out, int dtype_out, uint8_t *flags,
+                      uint32_t *trusted, hipStream_t s) {
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!device_dtype_ok(dtype_in))
+        return fail(ctx, HSFLOW_ERR_ARG, "device input dtype must be U8, F16, F32 or F64");
+    if (!I0 || !I1 || !uf || !vf || !ub || !vb || !out)
+        return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    int rc = check_interp_args(ctx, times, nt, dtype_out, false);
+    if (rc) return rc;
+    const size_t n = (size_t)rows * cols * batch, fb = n * elem_size(dtype_in);
+    const ByteRange in[8] = {{I0, fb},    {I1, fb},    {uf, n * 4},  {vf, n * 4},
+                             {ub, n * 4}, {vb, n * 4}, {mask_f, n}, {mask_b, n}};
+    const ByteRange outs[3] = {{out, n * nt * elem_size(dtype_out)},
+                               {flags, n * nt},
+                               {trusted, (size_t)batch * nt * 4}};
+    if (!outputs_disjoint(in, 8, outs, 3))
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "interpolation outputs overlap the inputs or each other");
+    return frame_interp_run(ctx, I0, I1, dtype_in, rows, cols, batch, uf, vf, ub, vb, mask_f,
+                            mask_b, times, nt, out, dtype_out, flags, trusted, s);
+}
+
+// Workspace of the fused call: [the bidirectional solve's][uf][vf][ub][vb]
+// (f32 batch planes)[mask_f][mask_b] (u8 batch planes), each 256-byte aligned.
+struct InterpLayout {
+    size_t solve_bytes, flow[4], mask[2], bytes;
+};
+
+InterpLayout interp_layout(int rows, int cols, int batch, int levels) {
+    InterpLayout L{};
+    const size_t n = (size_t)rows * cols * batch;
+    L.solve_bytes = align_up(pyr_layout(rows, cols, batch, levels).bytes);
+    size_t off = L.solve_bytes;
+    for (int k = 0; k < 4; ++k) L.flow[k] = off, off += align_up(n * 4);
+    for (int k = 0; k < 2; ++k) L.mask[k] = off, off += align_up(n);
+    L.bytes = off;
+    return L;
+}
+
+// hsflow_flow_bidir_median_device into the workspace's planes (the masks only
+// when flags or trusted needs them), then KI: the two public calls one after
+// the other, so the bits are theirs by construction.
+int flow_interp_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                     int cols, int batch, int levels, int warps, int median, int window,
+                     int iters, float alpha, float rel, float abs_thr, const float *times, int nt,
+                     void *out, int dtype_out, uint8_t *flags, uint32_t *trusted, void *ws,
+                     size_t ws_bytes, hipStream_t s) {
+    int rc = check_warped_args(ctx, warps, window, iters);
+    if (rc) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
+    if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
+        return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
+                    HSFLOW_MAX_LEVELS);
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!device_dtype_ok(dtype_in))
+        return fail(ctx, HSFLOW_ERR_ARG, "device input dtype must be U8, F16, F32 or F64");
+    if (!I0 || !I1 || !out || !ws) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
+    if ((rc = check_interp_args(ctx, times, nt, dtype_out, false))) return rc;
+    const InterpLayout L = interp_layout(rows, cols, batch, levels);
+    if (ws_bytes < L.bytes)
+        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, L.bytes);
+    const size_t n = (size_t)rows * cols * batch, fb = n * elem_size(dtype_in);
+    const ByteRange in[3] = {{I0, fb}, {I1, fb}, {ws, L.bytes}};
+    const ByteRange outs[3] = {{out, n * nt * elem_size(dtype_out)},
+                               {flags, n * nt},
+                               {trusted, (size_t)batch * nt * 4}};
+    if (!outputs_disjoint(in, 3, outs, 3))
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "interpolation outputs overlap the frames, the workspace or each other");
+    char *base = (char *)ws;
+    float *f[4];
+    for (int k = 0; k < 4; ++k) f[k] = (float *)(base + L.flow[k]);
+    const bool masks = flags || trusted;
+    uint8_t *mf = masks ? (uint8_t *)(base + L.mask[0]) : nullptr;
+    uint8_t *mb = masks ? (uint8_t *)(base + L.mask[1]) : nullptr;
+    rc = bidir_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window, iters,
+                    alpha, rel, abs_thr, f[0], f[1], f[2], f[3], nullptr, mf, nullptr, nullptr, mb,
+                    nullptr, ws, L.solve_bytes, s);
+    if (rc) return rc;
+    return frame_interp_run(ctx, I0, I1, dtype_in, rows, cols, batch, f[0], f[1], f[2], f[3], mf,
+                            mb, times, nt, out, dtype_out, flags, trusted, s);
+}
+
+// The host-buffer form: bidir_host's upload, flow_interp_impl on the context's
+// buffers, then flags and trusted down on the same stream ahead of the frames,
+// whose download drains it.
+int flow_interp_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                     int cols, size_t in_step0, size_t in_step1, int levels, int warps,
+                     int median, int window, int iters, double alpha, float rel, float abs_thr,
+                     const float *times, int nt, void *const *out, int dtype_out,
+                     size_t out_step, uint8_t *const *flags, size_t flags_step,
+                     uint32_t *trusted) {
+    if (!ctx) return HSFLOW_ERR_ARG;
+    int rc = check_interp_args(ctx, times, nt, dtype_out, true);
+    if (rc) return rc;
+    // the frames, sizes and input steps (the output type is checked above)
+    rc = check_host_args(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, HSFLOW_F32,
+                         (size_t)cols * 4);
+    if (rc) return rc;
+    if (out_step < (size_t)cols * elem_size(dtype_out))
+        return fail(ctx, HSFLOW_ERR_ARG, "output step %zu < row bytes", out_step);
+    if (!out) return fail(ctx, HSFLOW_ERR_ARG, "null output");
+    for (int k = 0; k < nt; ++k)
+        if (!out[k] || (flags && !flags[k]))
+            return fail(ctx, HSFLOW_ERR_ARG, "null output plane %d", k);
+    if (flags && flags_step < (size_t)cols)
+        return fail(ctx, HSFLOW_ERR_ARG, "flags step %zu < row bytes %d", flags_step, cols);
+    if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
+        return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
+                    HSFLOW_MAX_LEVELS);
+    if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)rows * cols;
+    const size_t in_es = (size_t)dev_elem_size(dtype_in);
+    const int dev_out = dtype_out == HSFLOW_U8 ? HSFLOW_U8 : HSFLOW_F32;
+    // d_out: the nt frames (f32 or u8), the nt flag planes, trusted
+    const size_t ob = align_up(n * nt * elem_size(dev_out)), flb = align_up(n * nt);
+    if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * in_es) * 2))) return rc;
+    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, ob + flb + kAlign))) return rc;
+    const size_t wsb = hsflow_flow_interp_workspace_bytes(rows, cols, 1, levels);
+    if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
+    char *in0 = (char *)ctx->d_in, *in1 = in0 + align_up(n * in_es);
+    char *dout = (char *)ctx->d_out;
+    uint8_t *dfl = (uint8_t *)(dout + ob);
+    uint32_t *dtr = (uint32_t *)(dout + ob + flb);
+    if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
+        return rc;
+    rc = flow_interp_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, median, window,
+                          iters, (float)alpha, rel, abs_thr, times, nt, dout, dev_out,
+                          flags ? dfl : nullptr, trusted ? dtr : nullptr, ctx->d_ws,
+                          ctx->d_ws_bytes, ctx->stream);
+    if (rc) return rc;
+    if (flags)
+        for (int k = 0; k < nt; ++k)
+            HIP_TRY(ctx, hipMemcpy2DAsync(flags[k], flags_step, dfl + k * n, (size_t)cols,
+                                          (size_t)cols, rows, hipMemcpyDeviceToHost,
+                                          ctx->stream));
+    if (trusted)
+        HIP_TRY(ctx, hipMemcpyAsync(trusted, dtr, (size_t)nt * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (dev_out == HSFLOW_U8) {
+        for (int k = 0; k < nt; ++k)
+            HIP_TRY(ctx, hipMemcpy2DAsync(out[k], out_step, dout + k * n, (size_t)cols,
+                                          (size_t)cols, rows, hipMemcpyDeviceToHost,
+                                          ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return HSFLOW_OK;
+    }
+    const float *srcs[HSFLOW_MAX_TIMES];
+    for (int k = 0; k < nt; ++k) srcs[k] = (const float *)dout + k * n;
+    return download_planes(ctx, srcs, out, nt, rows, cols, dtype_out, out_step);
+}
+
 // hsflow_flow_multi's kept contexts: one per (device, slot), each behind its
 // own lock (calls that list disjoint devices run concurrently); the registry
 // lock only guards the table's shape.  Slots are never freed (stable
@@ -1540,6 +1770,53 @@ int hsflow_flow_bidir(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype
     return hsflow_flow_bidir_median(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels,
                                     warps, 0, window, iters, alpha, rel, abs_thr, u, v, ub, vb,
                                     dtype_out, out_step, mask_f, mask_b, mask_step, counts);
+}
+
+int hsflow_warp_image_device(const void *I, int dtype_in, int rows, int cols, int batch,
+                             const float *u, const float *v, float *out, uint8_t *oof,
+                             void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return warp_image_impl(nullptr, I, dtype_in, rows, cols, batch, u, v, out, oof,
+                           (hipStream_t)stream);
+}
+
+int hsflow_frame_interp_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                               int batch, const float *uf, const float *vf, const float *ub,
+                               const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                               const float *times, int nt, void *out, int dtype_out,
+                               uint8_t *flags, uint32_t *trusted, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return frame_interp_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, uf, vf, ub, vb, mask_f,
+                             mask_b, times, nt, out, dtype_out, flags, trusted,
+                             (hipStream_t)stream);
+}
+
+size_t hsflow_flow_interp_workspace_bytes(int rows, int cols, int batch, int levels) {
+    if (!sizes_ok(rows, cols, batch) || levels < 1 || levels > HSFLOW_MAX_LEVELS) return 0;
+    return interp_layout(rows, cols, batch, levels).bytes;
+}
+
+int hsflow_flow_interp_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                              int batch, int levels, int warps, int median, int window,
+                              int iters, float alpha, float rel, float abs_thr,
+                              const float *times, int nt, void *out, int dtype_out,
+                              uint8_t *flags, uint32_t *trusted, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return flow_interp_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                            window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out, flags,
+                            trusted, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_interp(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                       int cols, size_t in_step0, size_t in_step1, int levels, int warps,
+                       int median, int window, int iters, double alpha, float rel, float abs_thr,
+                       const float *times, int nt, void *const *out, int dtype_out,
+                       size_t out_step, uint8_t *const *flags, size_t flags_step,
+                       uint32_t *trusted) {
+    return flow_interp_host(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1, levels, warps,
+                            median, window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out,
+                            out_step, flags, flags_step, trusted);
 }
 
 int hsflow_bgr_to_gray_device(const uint8_t *bgr, int rows, int cols, int batch,

@@ -76,6 +76,23 @@ hipError_t launch_consistency(const float *uf, const float *vf, const float *ub,
 // total order of the bit patterns (the result is one of the taps)
 hipError_t launch_median(const float *u, const float *v, int rows, int cols, int batch, int ksize,
                          float *u_out, float *v_out, hipStream_t s);
+// KR (hsflow_interp.hip): out (f32) = I sampled bilinearly at (y + 8 v, x + 8 u),
+// KW's arithmetic; oof (u8, may be null): 1 where the target leaves the frame
+// by more than half a pixel
+hipError_t launch_warp_image(const void *I, int dtype_in, int rows, int cols, int batch,
+                             const float *u, const float *v, float *out, uint8_t *oof,
+                             hipStream_t s);
+// KI (hsflow_interp.hip): the frames at `nt` (1..kInterpMaxTimes) times between
+// I0 and I1 from the flows both ways -> out [batch][nt] planes (f32, or u8 when
+// out_u8), flags (u8, may be null) and trusted[batch][nt] (may be null; must be
+// zero before the launch: the kernel adds).  mask_f / mask_b: KC's masks, each
+// may be null.  `times` is read on the host at launch.
+constexpr int kInterpMaxTimes = 16;
+hipError_t launch_frame_interp(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                               int batch, const float *uf, const float *vf, const float *ub,
+                               const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                               const float *times, int nt, void *out, bool out_u8,
+                               uint8_t *flags, uint32_t *trusted, hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

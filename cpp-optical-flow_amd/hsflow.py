@@ -52,6 +52,11 @@ CONSISTENT, INCONSISTENT, OUT_OF_FRAME = 0, 1, 2
 CONSISTENCY_REL, CONSISTENCY_ABS = 0.01, 0.5
 # sizes of the median filter between warps (median=; 0 = none)
 MEDIAN_SIZES = (3, 5)
+# frame interpolation: times per call and the bits of its flags plane
+# (HSFLOW_INTERP_*): a target outside I0 / I1, a source that fails the forward /
+# backward check; flags == 0 marks a pixel both of whose sources pass
+MAX_TIMES = 16
+FLAG_I0_OUT, FLAG_I1_OUT, FLAG_FWD_FAILED, FLAG_BWD_FAILED = 1, 2, 4, 8
 
 # every symbol include/hsflow.h declares
 EXPORTS = (
@@ -73,6 +78,8 @@ EXPORTS = (
     "hsflow_flow_median_device", "hsflow_flow_warped_median_device",
     "hsflow_flow_warped_median", "hsflow_flow_bidir_median_device",
     "hsflow_flow_bidir_median",
+    "hsflow_warp_image_device", "hsflow_frame_interp_device",
+    "hsflow_flow_interp_workspace_bytes", "hsflow_flow_interp_device", "hsflow_flow_interp",
     "hsflow_set_first_pass_fusion", "hsflow_first_pass_fusion",
     "hsflow_first_pass_launches",
 )
@@ -186,6 +193,17 @@ def lib():
     L.hsflow_flow_bidir_median.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
                                            ctypes.c_double, f, f, _vp, _vp, _vp, _vp, i, _sz,
                                            _vp, _vp, _sz, _vp]
+    fp = ctypes.POINTER(f)
+    L.hsflow_warp_image_device.argtypes = [_vp, i, i, i, i, _vp, _vp, _vp, _vp, _vp]
+    L.hsflow_frame_interp_device.argtypes = [_vp, _vp, i, i, i, i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             fp, i, _vp, i, _vp, _vp, _vp]
+    L.hsflow_flow_interp_workspace_bytes.argtypes = [i, i, i, i]
+    L.hsflow_flow_interp_workspace_bytes.restype = _sz
+    L.hsflow_flow_interp_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f, fp, i,
+                                            _vp, i, _vp, _vp, _vp, _sz, _vp]
+    L.hsflow_flow_interp.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
+                                     ctypes.c_double, f, f, fp, i, ctypes.POINTER(_vp), i, _sz,
+                                     ctypes.POINTER(_vp), _sz, _vp]
     L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               _vp, _sz, _vp]
@@ -398,6 +416,39 @@ class Context:
         _check(rc, self._p)
         return BidirHost(u, v, ub if backward else None, vb if backward else None,
                          mf if masks else None, mb if masks else None, cnt)
+
+    def interpolate(self, I0, I1, times, levels: int, warps: int, window: int, iters: int,
+                    alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
+                    abs: float = CONSISTENCY_ABS, out_dtype=np.float32,
+                    with_flags: bool = False):
+        """The frames at `times` (each in [0, 1]; at most MAX_TIMES) between I0
+        and I1: the bidirectional warped solve, then the motion-compensated
+        blend (hsflow_flow_interp in include/hsflow.h).  Returns an array
+        [len(times), rows, cols] of out_dtype (uint8, float32 or float64), or
+        with_flags: (frames, flags, trusted) -- flags uint8 like frames (FLAG_*
+        bits; 0 = both sources pass the forward-backward check), trusted uint32
+        [len(times)], the pixels per frame with flags == 0."""
+        a, b = _as_image(I0), _as_image(I1)
+        if a.shape != b.shape:
+            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
+        a, b = _common_dtype(a, b)
+        rows, cols = a.shape
+        tm = _times_array(times)
+        nt = len(tm)
+        out = np.empty((nt, rows, cols), out_dtype)
+        if out.dtype not in (np.uint8, np.float32, np.float64):
+            raise HsflowError(HSFLOW_ERR_ARG, "out_dtype: need uint8, float32 or float64")
+        flags = np.empty((nt, rows, cols), np.uint8) if with_flags else None
+        trusted = np.zeros(nt, np.uint32) if with_flags else None
+        planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
+        fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
+        rc = lib().hsflow_flow_interp(
+            self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
+            b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
+            float(alpha), float(rel), float(abs), tm, nt, planes, _dtype_code(out),
+            out.strides[1], fplanes, cols, trusted.ctypes.data if with_flags else None)
+        _check(rc, self._p)
+        return (out, flags, trusted) if with_flags else out
 
     def flow_bgr(self, bgr0, bgr1, window: int, iters: int, alpha: float,
                  out_dtype=np.float64):
@@ -858,6 +909,130 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
             workspace.numel(), _stream_ptr(stream, I0.device))
     _check(rc)
     return BidirDevice(*flows, *outs)
+
+
+def _times_array(times):
+    """`times` (a number or a sequence) as the C float array the library reads
+    at call time; the library checks the count and the range."""
+    t = [float(x) for x in np.atleast_1d(np.asarray(times, np.float64))]
+    return (ctypes.c_float * len(t))(*t)
+
+
+def warp_image_device(I, u, v, out=None, oof=None, stream=None):
+    """Backward warp of the frames I (CUDA tensor [B, H, W] or [H, W], uint8 /
+    float16 / float32 / float64) by the flow (u, v) (float32, solver units):
+    out(y, x) = I sampled bilinearly at (y + 8 v, x + 8 u), the I1w of
+    warp_gradients_device bit for bit (hsflow_warp_image_device in
+    include/hsflow.h).  oof: True / a uint8 tensor like I to get 1 where the
+    target leaves the frame by more than half a pixel.  Returns out (float32),
+    or (out, oof) when oof was asked for.  Stream-ordered."""
+    rows, cols = I.shape[-2:]
+    batch = int(np.prod(I.shape[:-2])) if I.dim() > 2 else 1
+    _check_dense(I, (rows, cols), "I")
+    _check_plane(u, (rows, cols), batch, "u")
+    _check_plane(v, (rows, cols), batch, "v")
+    if out is None:
+        out = torch.empty(I.shape, dtype=torch.float32, device=I.device)
+    _check_plane(out, (rows, cols), batch, "out")
+    oof = _check_output(oof, I.shape, torch.uint8, I.device, "oof")
+    with _on(I.device):
+        rc = lib().hsflow_warp_image_device(
+            I.data_ptr(), _tensor_dtype(I), rows, cols, batch, u.data_ptr(), v.data_ptr(),
+            out.data_ptr(), oof.data_ptr() if oof is not None else None,
+            _stream_ptr(stream, I.device))
+    _check(rc)
+    return out if oof is None else (out, oof)
+
+
+def _interp_outputs(I0, nt, out, out_dtype, flags, trusted):
+    """out / flags / trusted of an interpolation of `nt` times of the frames
+    I0 ([B, H, W] or [H, W]): [B, nt, H, W] ([nt, H, W]) and [B, nt]."""
+    rows, cols = I0.shape[-2:]
+    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
+    shape = tuple(I0.shape[:-2]) + (nt, rows, cols)
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=I0.device)
+    if out.dtype not in (torch.float32, torch.uint8):
+        raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
+    out = _check_output(out, shape, out.dtype, I0.device, "out")
+    flags = _check_output(flags, shape, torch.uint8, I0.device, "flags")
+    trusted = _check_output(trusted, (batch, nt), torch.int32, I0.device, "trusted")
+    return out, flags, trusted
+
+
+def frame_interp_device(I0, I1, uf, vf, ub, vb, times, mask_f=None, mask_b=None, out=None,
+                        out_dtype=None, flags=None, trusted=None, stream=None):
+    """The frames at `times` (each in [0, 1]; at most MAX_TIMES) between I0 and
+    I1 -- CUDA tensors [B, H, W] or [H, W], uint8 / float16 / float32 / float64
+    -- from the flows I0 -> I1 (uf, vf) and I1 -> I0 (ub, vb), float32 in solver
+    units (hsflow_frame_interp_device in include/hsflow.h).  mask_f, mask_b: the
+    uint8 masks of consistency_device / flow_bidir_device, or None.  out:
+    float32 (default) or uint8, [B, len(times), H, W]; flags (True / tensor):
+    uint8 like out, FLAG_* bits; trusted (True / tensor): int32 [B, len(times)]
+    (the library's uint32 words), pixels with flags == 0.  Returns (out, flags,
+    trusted), None for those not asked for.  Stream-ordered."""
+    if out_dtype is None:
+        out_dtype = torch.float32
+    rows, cols = I0.shape[-2:]
+    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
+    _check_dense(I0, (rows, cols), "I0")
+    _check_dense(I1, (rows, cols), "I1")
+    if I1.dtype != I0.dtype or I1.shape != I0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
+    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
+        _check_plane(t, (rows, cols), batch, name)
+    for t, name in ((mask_f, "mask_f"), (mask_b, "mask_b")):
+        if t is not None:
+            _check_output(t, I0.shape, torch.uint8, I0.device, name)
+    tm = _times_array(times)
+    out, flags, trusted = _interp_outputs(I0, len(tm), out, out_dtype, flags, trusted)
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    with _on(I0.device):
+        rc = lib().hsflow_frame_interp_device(
+            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, uf.data_ptr(),
+            vf.data_ptr(), ub.data_ptr(), vb.data_ptr(), ptr(mask_f), ptr(mask_b), tm, len(tm),
+            out.data_ptr(), U8 if out.dtype == torch.uint8 else F32, ptr(flags), ptr(trusted),
+            _stream_ptr(stream, I0.device))
+    _check(rc)
+    return out, flags, trusted
+
+
+def flow_interp_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -> int:
+    return int(lib().hsflow_flow_interp_workspace_bytes(rows, cols, batch, levels))
+
+
+def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iters: int,
+                       alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
+                       abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
+                       trusted=None, workspace=None, stream=None):
+    """flow_bidir_device(median=...) into planes of the workspace, then
+    frame_interp_device with both masks: one call, the same bits
+    (hsflow_flow_interp_device in include/hsflow.h).  `workspace`:
+    flow_interp_workspace_bytes(rows, cols, batch, levels) bytes.  Returns
+    (out, flags, trusted) as frame_interp_device.  Stream-ordered."""
+    if out_dtype is None:
+        out_dtype = torch.float32
+    rows, cols = I0.shape[-2:]
+    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
+    _check_dense(I0, (rows, cols), "I0")
+    _check_dense(I1, (rows, cols), "I1")
+    if I1.dtype != I0.dtype or I1.shape != I0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
+    tm = _times_array(times)
+    out, flags, trusted = _interp_outputs(I0, len(tm), out, out_dtype, flags, trusted)
+    if workspace is None:
+        n = flow_interp_workspace_bytes(rows, cols, batch, levels)
+        workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    with _on(I0.device):
+        rc = lib().hsflow_flow_interp_device(
+            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
+            int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
+            float(abs), tm, len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32,
+            ptr(flags), ptr(trusted), workspace.data_ptr(), workspace.numel(),
+            _stream_ptr(stream, I0.device))
+    _check(rc)
+    return out, flags, trusted
 
 
 def warp_gradients_device(I0, I1, u0, v0, workspace, gx=None, gy=None, gt=None, stream=None):

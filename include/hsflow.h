@@ -448,6 +448,94 @@ int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, in
                              int dtype_out, size_t out_step, uint8_t *mask_f, uint8_t *mask_b,
                              size_t mask_step, uint32_t *counts);
 
+/* ---- frame warp and motion-compensated frame interpolation --------------
+ * What the bidirectional solve is for: the frame at a time t between I0
+ * (t = 0) and I1 (t = 1).  Flows are f32 planes in solver units (8 px per
+ * unit); (uf, vf) is the flow I0 -> I1, (ub, vb) the flow I1 -> I0, all four
+ * read at the output pixel (y, x) (Jiang et al., CVPR 2018, eq. 4):
+ *   s = 1 - t;  a = s t;  b = t t;  c = s s                        (f32)
+ *   u0 = b ub - a uf;  v0 = b vb - a vf     flow from time t back to frame 0
+ *   u1 = c uf - a ub;  v1 = c vf - a vb     flow from time t on to frame 1
+ *   s0 = I0 at (y + 8 v0, x + 8 u0);  s1 = I1 at (y + 8 v1, x + 8 u1)
+ *   in0, in1 = the targets lie within half a pixel of the frame (the check's
+ *        rim test, negated comparisons: NaN -> out)
+ *   wt  = t where in0 == in1;  0 where only in0;  1 where only in1
+ *   out = (1 - wt) s0 + wt s1     (the bits of s0 where wt = 0, of s1 where 1)
+ *   flags = !in0 * HSFLOW_INTERP_I0_OUT | !in1 * HSFLOW_INTERP_I1_OUT |
+ *           (mask_f[n0] != 0) * HSFLOW_INTERP_FWD_FAILED |
+ *           (mask_b[n1] != 0) * HSFLOW_INTERP_BWD_FAILED
+ * The sampler is hsflow_warp_gradients_device's: each displacement clamped as
+ * a float to [-cols, cols] / [-rows, rows] (NaN -> lower bound), floor split,
+ * the four taps clamped to the pair's plane, top and bottom rows first, then
+ * vertical; f64 frames are sampled in f64 and rounded once.  n0, n1 are the
+ * source pixels nearest to the two targets (integer part, plus one where the
+ * fraction >= 0.5, clamped to the plane); mask_f, mask_b are the u8 planes of
+ * hsflow_flow_consistency_device (forward: uf, vf against ub, vb).  A pure
+ * translation uf = d, ub = -d gives u0 = -t d and u1 = (1 - t) d; t = 0
+ * returns I0 and t = 1 returns I1 bit for bit (f32 frames, finite flows).  The
+ * masks are not blending weights -- that made the border strip and the
+ * occlusion ring worse -- but flags == 0 marks the pixels whose
+ * two sources both pass the check, which carry a far lower error than the
+ * rest.  No index leaves a pair's plane, whatever the flows hold. */
+#define HSFLOW_HAS_INTERP 1
+#define HSFLOW_MAX_TIMES 16
+#define HSFLOW_INTERP_I0_OUT 1     /* the target in I0 leaves the frame         */
+#define HSFLOW_INTERP_I1_OUT 2     /* the target in I1 leaves the frame         */
+#define HSFLOW_INTERP_FWD_FAILED 4 /* the I0 source fails the forward check     */
+#define HSFLOW_INTERP_BWD_FAILED 8 /* the I1 source fails the backward check    */
+
+/* Backward warp of a frame by a flow: out(y, x) = I at (y + 8 v, x + 8 u), the
+ * I1w of hsflow_warp_gradients_device bit for bit.  I: dense [batch][rows][cols]
+ * of dtype_in (U8, F16, F32, F64); u, v, out: f32; oof (u8, may be NULL): 1
+ * where the target leaves the frame by more than half a pixel, else 0.  The
+ * outputs must not overlap the inputs or each other.  Stream-ordered, no
+ * workspace, never allocates or synchronises, capturable. */
+int hsflow_warp_image_device(const void *I, int dtype_in, int rows, int cols, int batch,
+                             const float *u, const float *v, float *out, uint8_t *oof,
+                             void *stream);
+
+/* The frames at `nt` (1..HSFLOW_MAX_TIMES) times, each in [0, 1], in one
+ * launch.  `times` is a host array read at call time (the values travel in the
+ * kernel arguments).  mask_f, mask_b may each be NULL: its flag bit is then
+ * never set.  out: [batch][nt][rows][cols] of dtype_out, HSFLOW_F32 or
+ * HSFLOW_U8 (floorf(out + 0.5f) clamped to 0..255, NaN -> 0); flags (may be
+ * NULL): u8 [batch][nt][rows][cols]; trusted (may be NULL): uint32[batch][nt],
+ * the number of pixels with flags == 0 (zeroed stream-ordered by the call,
+ * integer sums).  The outputs must not overlap the inputs or each other.
+ * Stream-ordered, no workspace, never allocates or synchronises, capturable;
+ * all arguments are checked before any device work. */
+int hsflow_frame_interp_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                               int batch, const float *uf, const float *vf, const float *ub,
+                               const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                               const float *times, int nt, void *out, int dtype_out,
+                               uint8_t *flags, uint32_t *trusted, void *stream);
+
+/* Solve and interpolate in one call: hsflow_flow_bidir_median_device into
+ * planes of the workspace (both masks only when flags or trusted is asked
+ * for), then hsflow_frame_interp_device -- bit for bit what the two calls give
+ * one after the other.  `workspace`: at least
+ * hsflow_flow_interp_workspace_bytes(rows, cols, batch, levels) bytes (the
+ * bidirectional solve's, four f32 flow planes and two u8 mask planes),
+ * 256-byte aligned. */
+size_t hsflow_flow_interp_workspace_bytes(int rows, int cols, int batch, int levels);
+int hsflow_flow_interp_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                              int batch, int levels, int warps, int median, int window,
+                              int iters, float alpha, float rel, float abs_thr,
+                              const float *times, int nt, void *out, int dtype_out,
+                              uint8_t *flags, uint32_t *trusted, void *workspace,
+                              size_t workspace_bytes, void *stream);
+/* Host-buffer, blocking form (same conventions as hsflow_flow_bidir_median).
+ * out: `nt` host planes rows x cols of dtype_out (HSFLOW_U8, HSFLOW_F32, or
+ * HSFLOW_F64: the f32 result widened), row step out_step bytes; flags (may be
+ * NULL): `nt` u8 planes, row step flags_step; trusted (may be NULL): host
+ * uint32[nt]. */
+int hsflow_flow_interp(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                       int cols, size_t in_step0, size_t in_step1, int levels, int warps,
+                       int median, int window, int iters, double alpha, float rel, float abs_thr,
+                       const float *times, int nt, void *const *out, int dtype_out,
+                       size_t out_step, uint8_t *const *flags, size_t flags_step,
+                       uint32_t *trusted);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

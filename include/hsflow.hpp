@@ -157,6 +157,44 @@ class HornSchunck {
             nullptr, (size_t)a.cols, nullptr));
     }
 
+    // The frames at `times` (each in [0, 1], at most HSFLOW_MAX_TIMES) between
+    // imagePrev (t = 0) and imageNext (t = 1): getFlowBidir's solve, then the
+    // motion-compensated blend (hsflow.h, hsflow_flow_interp).  planes[k]: the
+    // frame at times[k] as rows*cols float32 grey levels; flags[k]: per pixel
+    // the HSFLOW_INTERP_* bits, 0 where both source pixels pass the
+    // forward-backward check at the default thresholds.
+    void getFrameInterp(const ImageView &imagePrev, const ImageView &imageNext,
+                        const std::vector<float> &times, int levels, int warps, int median,
+                        std::vector<std::vector<float>> &planes,
+                        std::vector<std::vector<uint8_t>> *flags = nullptr) {
+        check_pair(imagePrev, imageNext);
+        const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
+        planes.resize(times.size());
+        if (flags) flags->resize(times.size());
+        std::vector<void *> out(times.size());
+        std::vector<uint8_t *> fl(times.size());
+        for (size_t k = 0; k < times.size(); ++k) {
+            planes[k].resize(n);
+            out[k] = planes[k].data();
+            if (flags) (*flags)[k].resize(n), fl[k] = (*flags)[k].data();
+        }
+        std::vector<double> ha, hb;
+        const ImageView a = common_type(imagePrev, imageNext, ha);
+        const ImageView b = common_type(imageNext, imagePrev, hb);
+        Context &c = ctx();
+        c.check(hsflow_flow_interp(
+            c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step, b.step, levels, warps, median,
+            windowSize, maxIterations, alpha, HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS,
+            times.data(), (int)times.size(), out.data(), HSFLOW_F32, (size_t)a.cols * 4,
+            flags ? fl.data() : nullptr, (size_t)a.cols, nullptr));
+    }
+    void getFrameInterp(const ImageView &imagePrev, const ImageView &imageNext,
+                        const std::vector<float> &times, int levels, int warps, int median,
+                        std::vector<std::vector<float>> &planes,
+                        std::vector<std::vector<uint8_t>> &flags) {
+        getFrameInterp(imagePrev, imageNext, times, levels, warps, median, planes, &flags);
+    }
+
     // Raw form for callers that own output rows (cv::Mat adapter): dtype_out
     // HSFLOW_F64 or HSFLOW_F32, out_step in bytes.  Each frame keeps its own
     // row step; frames of different element types are both widened to
