@@ -1271,6 +1271,215 @@ int flow_interp_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
     return download_planes(ctx, srcs, out, nt, rows, cols, dtype_out, out_step);
 }
 
+// ---- colour (BGR) frame warp and frame interpolation ------------------------
+int check_bgr_out_dtype(hsflow_ctx *ctx, int dtype_out) {
+    if (dtype_out != HSFLOW_F32 && dtype_out != HSFLOW_U8)
+        return fail(ctx, HSFLOW_ERR_ARG, "BGR output dtype must be U8 or F32");
+    return HSFLOW_OK;
+}
+
+int warp_image_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr, int rows, int cols, int batch,
+                        const float *u, const float *v, void *out, int dtype_out, uint8_t *oof,
+                        hipStream_t s) {
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!bgr || !u || !v || !out) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    int rc = check_bgr_out_dtype(ctx, dtype_out);
+    if (rc) return rc;
+    const size_t n = (size_t)rows * cols * batch;
+    const ByteRange in[3] = {{bgr, n * 3}, {u, n * 4}, {v, n * 4}};
+    const ByteRange outs[2] = {{out, n * 3 * elem_size(dtype_out)}, {oof, n}};
+    if (!outputs_disjoint(in, 3, outs, 2))
+        return fail(ctx, HSFLOW_ERR_ARG, "warp outputs overlap the inputs or each other");
+    hipError_t e = hsflow::launch_warp_image_bgr(bgr, rows, cols, batch, u, v, out,
+                                                 dtype_out == HSFLOW_U8, oof, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "BGR warp image launch");
+    return HSFLOW_OK;
+}
+
+// KIC on checked arguments: trusted zeroed stream-ordered, then one launch
+int frame_interp_bgr_run(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                         int cols, int batch, const float *uf, const float *vf, const float *ub,
+                         const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                         const float *times, int nt, void *out, int dtype_out, uint8_t *flags,
+                         uint32_t *trusted, hipStream_t s) {
+    if (trusted) HIP_TRY(ctx, hipMemsetAsync(trusted, 0, (size_t)batch * nt * 4, s));
+    hipError_t e = hsflow::launch_frame_interp_bgr(bgr0, bgr1, rows, cols, batch, uf, vf, ub, vb,
+                                                   mask_f, mask_b, times, nt, out,
+                                                   dtype_out == HSFLOW_U8, flags, trusted, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "BGR frame interpolation launch");
+    return HSFLOW_OK;
+}
+
+int frame_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                          int cols, int batch, const float *uf, const float *vf, const float *ub,
+                          const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                          const float *times, int nt, void *out, int dtype_out, uint8_t *flags,
+                          uint32_t *trusted, hipStream_t s) {
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!bgr0 || !bgr1 || !uf || !vf || !ub || !vb || !out)
+        return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    int rc = check_interp_args(ctx, times, nt, dtype_out, false);
+    if (rc) return rc;
+    const size_t n = (size_t)rows * cols * batch;
+    const ByteRange in[8] = {{bgr0, n * 3}, {bgr1, n * 3}, {uf, n * 4},  {vf, n * 4},
+                             {ub, n * 4},   {vb, n * 4},   {mask_f, n}, {mask_b, n}};
+    const ByteRange outs[3] = {{out, n * nt * 3 * elem_size(dtype_out)},
+                               {flags, n * nt},
+                               {trusted, (size_t)batch * nt * 4}};
+    if (!outputs_disjoint(in, 8, outs, 3))
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "interpolation outputs overlap the inputs or each other");
+    return frame_interp_bgr_run(ctx, bgr0, bgr1, rows, cols, batch, uf, vf, ub, vb, mask_f, mask_b,
+                                times, nt, out, dtype_out, flags, trusted, s);
+}
+
+// Workspace of the fused BGR call: [the grey interpolation's (InterpLayout)]
+// [grey I0][grey I1] (u8 batch planes), each 256-byte aligned.
+struct InterpBgrLayout {
+    InterpLayout grey;
+    size_t gray[2], bytes;
+};
+
+InterpBgrLayout interp_bgr_layout(int rows, int cols, int batch, int levels) {
+    InterpBgrLayout L{};
+    const size_t n = (size_t)rows * cols * batch;
+    L.grey = interp_layout(rows, cols, batch, levels);
+    size_t off = L.grey.bytes;
+    for (int k = 0; k < 2; ++k) L.gray[k] = off, off += align_up(n);
+    L.bytes = off;
+    return L;
+}
+
+// hsflow_bgr_to_gray_device of both frames into the workspace,
+// hsflow_flow_bidir_median_device on the grey planes (the masks only when
+// flags or trusted needs them), then KIC on the BGR frames: three public
+// calls one after the other, so the bits are theirs by construction.
+int flow_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                         int cols, int batch, int levels, int warps, int median, int window,
+                         int iters, float alpha, float rel, float abs_thr, const float *times,
+                         int nt, void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
+                         void *ws, size_t ws_bytes, hipStream_t s) {
+    int rc = check_warped_args(ctx, warps, window, iters);
+    if (rc) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
+    if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
+        return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
+                    HSFLOW_MAX_LEVELS);
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!bgr0 || !bgr1 || !out || !ws) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
+    if ((rc = check_interp_args(ctx, times, nt, dtype_out, false))) return rc;
+    const InterpBgrLayout L = interp_bgr_layout(rows, cols, batch, levels);
+    if (ws_bytes < L.bytes)
+        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, L.bytes);
+    const size_t n = (size_t)rows * cols * batch;
+    const ByteRange in[3] = {{bgr0, n * 3}, {bgr1, n * 3}, {ws, L.bytes}};
+    const ByteRange outs[3] = {{out, n * nt * 3 * elem_size(dtype_out)},
+                               {flags, n * nt},
+                               {trusted, (size_t)batch * nt * 4}};
+    if (!outputs_disjoint(in, 3, outs, 3))
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "interpolation outputs overlap the frames, the workspace or each other");
+    // the frames must not overlap the workspace either: the grey planes are
+    // written while the BGR frames are still to be read
+    if (bytes_overlap(bgr0, n * 3, ws, L.bytes) || bytes_overlap(bgr1, n * 3, ws, L.bytes))
+        return fail(ctx, HSFLOW_ERR_ARG, "the frames overlap the workspace");
+    char *base = (char *)ws;
+    uint8_t *g0 = (uint8_t *)(base + L.gray[0]), *g1 = (uint8_t *)(base + L.gray[1]);
+    float *f[4];
+    for (int k = 0; k < 4; ++k) f[k] = (float *)(base + L.grey.flow[k]);
+    const bool masks = flags || trusted;
+    uint8_t *mf = masks ? (uint8_t *)(base + L.grey.mask[0]) : nullptr;
+    uint8_t *mb = masks ? (uint8_t *)(base + L.grey.mask[1]) : nullptr;
+    hipError_t e = hsflow::launch_bgr2gray(bgr0, rows, cols, batch, g0, s);
+    if (e == hipSuccess) e = hsflow::launch_bgr2gray(bgr1, rows, cols, batch, g1, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "bgr2gray launch");
+    rc = bidir_impl(ctx, g0, g1, HSFLOW_U8, rows, cols, batch, levels, warps, median, window,
+                    iters, alpha, rel, abs_thr, f[0], f[1], f[2], f[3], nullptr, mf, nullptr,
+                    nullptr, mb, nullptr, ws, L.grey.solve_bytes, s);
+    if (rc) return rc;
+    return frame_interp_bgr_run(ctx, bgr0, bgr1, rows, cols, batch, f[0], f[1], f[2], f[3], mf, mb,
+                                times, nt, out, dtype_out, flags, trusted, s);
+}
+
+// The host-buffer form: the frames go up as 3 B/px (hsflow_flow_bgr's upload),
+// flow_interp_bgr_impl on the context's buffers, then flags and trusted down on
+// the same stream ahead of the frames, whose download drains it.
+int flow_interp_bgr_host(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                         int cols, size_t bgr_step0, size_t bgr_step1, int levels, int warps,
+                         int median, int window, int iters, double alpha, float rel,
+                         float abs_thr, const float *times, int nt, void *const *out,
+                         int dtype_out, size_t out_step, uint8_t *const *flags,
+                         size_t flags_step, uint32_t *trusted) {
+    // the arguments first (a null context fails after them, so that they can
+    // be checked where there is no device)
+    int rc = check_interp_args(ctx, times, nt, dtype_out, false);
+    if (rc) return rc;
+    if (!bgr0 || !bgr1) return fail(ctx, HSFLOW_ERR_ARG, "null image");
+    if (!sizes_ok(rows, cols, 1)) return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d", rows, cols);
+    if (bgr_step0 < (size_t)cols * 3 || bgr_step1 < (size_t)cols * 3)
+        return fail(ctx, HSFLOW_ERR_ARG, "BGR steps %zu, %zu < row bytes", bgr_step0,
+                    bgr_step1);
+    const size_t es = (size_t)elem_size(dtype_out);
+    if (out_step < (size_t)cols * 3 * es)
+        return fail(ctx, HSFLOW_ERR_ARG, "output step %zu < row bytes", out_step);
+    if (!out) return fail(ctx, HSFLOW_ERR_ARG, "null output");
+    for (int k = 0; k < nt; ++k)
+        if (!out[k] || (flags && !flags[k]))
+            return fail(ctx, HSFLOW_ERR_ARG, "null output plane %d", k);
+    if (flags && flags_step < (size_t)cols)
+        return fail(ctx, HSFLOW_ERR_ARG, "flags step %zu < row bytes %d", flags_step, cols);
+    if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
+        return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
+                    HSFLOW_MAX_LEVELS);
+    if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)rows * cols;
+    // d_out: the nt frames (f32 or u8 BGR), the nt flag planes, trusted
+    const size_t ob = align_up(n * nt * 3 * es), flb = align_up(n * nt);
+    if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * 3) * 2))) return rc;
+    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, ob + flb + kAlign))) return rc;
+    const size_t wsb = interp_bgr_layout(rows, cols, 1, levels).bytes;
+    if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
+    uint8_t *in0 = (uint8_t *)ctx->d_in, *in1 = in0 + align_up(n * 3);
+    char *dout = (char *)ctx->d_out;
+    uint8_t *dfl = (uint8_t *)(dout + ob);
+    uint32_t *dtr = (uint32_t *)(dout + ob + flb);
+    if ((rc = upload_pair(ctx, bgr0, bgr1, 3, rows, cols, bgr_step0, bgr_step1, in0, in1)))
+        return rc;
+    rc = flow_interp_bgr_impl(ctx, in0, in1, rows, cols, 1, levels, warps, median, window, iters,
+                              (float)alpha, rel, abs_thr, times, nt, dout, dtype_out,
+                              flags ? dfl : nullptr, trusted ? dtr : nullptr, ctx->d_ws,
+                              ctx->d_ws_bytes, ctx->stream);
+    if (rc) return rc;
+    if (flags)
+        for (int k = 0; k < nt; ++k)
+            HIP_TRY(ctx, hipMemcpy2DAsync(flags[k], flags_step, dfl + k * n, (size_t)cols,
+                                          (size_t)cols, rows, hipMemcpyDeviceToHost,
+                                          ctx->stream));
+    if (trusted)
+        HIP_TRY(ctx, hipMemcpyAsync(trusted, dtr, (size_t)nt * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (dtype_out == HSFLOW_U8) {
+        for (int k = 0; k < nt; ++k)
+            HIP_TRY(ctx, hipMemcpy2DAsync(out[k], out_step, dout + k * n * 3, (size_t)cols * 3,
+                                          (size_t)cols * 3, rows, hipMemcpyDeviceToHost,
+                                          ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return HSFLOW_OK;
+    }
+    // f32: a BGR plane is rows x 3 cols floats
+    const float *srcs[HSFLOW_MAX_TIMES];
+    for (int k = 0; k < nt; ++k) srcs[k] = (const float *)dout + k * n * 3;
+    return download_planes(ctx, srcs, out, nt, rows, cols * 3, HSFLOW_F32, out_step);
+}
+
 // hsflow_flow_multi's kept contexts: one per (device, slot), each behind its
 // own lock (calls that list disjoint devices run concurrently); the registry
 // lock only guards the table's shape.  Slots are never freed (stable
@@ -1818,6 +2027,55 @@ int hsflow_flow_interp(hsflow_ctx *ctx, const void *I0, const void *I1, int dtyp
                             median, window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out,
                             out_step, flags, flags_step, trusted);
 }
+
+int hsflow_warp_image_bgr_device(const uint8_t *bgr, int rows, int cols, int batch, const float *u,
+                                 const float *v, void *out, int dtype_out, uint8_t *oof,
+                                 void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return warp_image_bgr_impl(nullptr, bgr, rows, cols, batch, u, v, out, dtype_out, oof,
+                               (hipStream_t)stream);
+}
+
+int hsflow_frame_interp_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                   int batch, const float *uf, const float *vf, const float *ub,
+                                   const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                                   const float *times, int nt, void *out, int dtype_out,
+                                   uint8_t *flags, uint32_t *trusted, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return frame_interp_bgr_impl(nullptr, bgr0, bgr1, rows, cols, batch, uf, vf, ub, vb, mask_f,
+                                 mask_b, times, nt, out, dtype_out, flags, trusted,
+                                 (hipStream_t)stream);
+}
+
+size_t hsflow_flow_interp_bgr_workspace_bytes(int rows, int cols, int batch, int levels) {
+    if (!sizes_ok(rows, cols, batch) || levels < 1 || levels > HSFLOW_MAX_LEVELS) return 0;
+    return interp_bgr_layout(rows, cols, batch, levels).bytes;
+}
+
+int hsflow_flow_interp_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                  int batch, int levels, int warps, int median, int window,
+                                  int iters, float alpha, float rel, float abs_thr,
+                                  const float *times, int nt, void *out, int dtype_out,
+                                  uint8_t *flags, uint32_t *trusted, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return flow_interp_bgr_impl(nullptr, bgr0, bgr1, rows, cols, batch, levels, warps, median,
+                                window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out,
+                                flags, trusted, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_interp_bgr(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                           int cols, size_t bgr_step0, size_t bgr_step1, int levels, int warps,
+                           int median, int window, int iters, double alpha, float rel,
+                           float abs_thr, const float *times, int nt, void *const *out,
+                           int dtype_out, size_t out_step, uint8_t *const *flags,
+                           size_t flags_step, uint32_t *trusted) {
+    return flow_interp_bgr_host(ctx, bgr0, bgr1, rows, cols, bgr_step0, bgr_step1, levels, warps,
+                                median, window, iters, alpha, rel, abs_thr, times, nt, out,
+                                dtype_out, out_step, flags, flags_step, trusted);
+}
+
+int hsflow_set_interp_bgr_loads(int wide) { return hsflow::set_interp_bgr_wide_loads(wide); }
 
 int hsflow_bgr_to_gray_device(const uint8_t *bgr, int rows, int cols, int batch,
                               uint8_t *gray, void *stream) {

@@ -93,6 +93,21 @@ hipError_t launch_frame_interp(const void *I0, const void *I1, int dtype_in, int
                                const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
                                const float *times, int nt, void *out, bool out_u8,
                                uint8_t *flags, uint32_t *trusted, hipStream_t s);
+// KRC, KIC (hsflow_interp_bgr.hip): KR and KI on dense 8-bit interleaved BGR
+// frames [batch][rows][cols][3] -> out [..][rows][cols][3] (f32, or u8 when
+// out_u8); oof, flags, trusted as KR's and KI's, one value per pixel
+hipError_t launch_warp_image_bgr(const uint8_t *I, int rows, int cols, int batch, const float *u,
+                                 const float *v, void *out, bool out_u8, uint8_t *oof,
+                                 hipStream_t s);
+hipError_t launch_frame_interp_bgr(const uint8_t *I0, const uint8_t *I1, int rows, int cols,
+                                   int batch, const float *uf, const float *vf, const float *ub,
+                                   const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                                   const float *times, int nt, void *out, bool out_u8,
+                                   uint8_t *flags, uint32_t *trusted, hipStream_t s);
+// how KRC and KIC fetch the two adjacent taps of a row: as six bytes (on == 0,
+// default) or as one unaligned dword and halfword; same bits.  Returns the
+// previous setting.
+int set_interp_bgr_wide_loads(int on);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

@@ -47,51 +47,31 @@
 #include <algorithm>
 
 #include "hsflow_internal.h"
+#include "hsflow_sampler.h"
 
 namespace hsflow {
 namespace {
+
+using namespace sampler;
 
 // double for CV_64FC1 frames (sampled in float64, one rounding), else float
 template <typename T> struct SampleMath { using type = float; };
 template <> struct SampleMath<double> { using type = double; };
 
-// KW's displacement split as KC restates it (the clamped float comes back for
-// the rim test): d (pixels) along an axis of length n is clamped to [-n, n]
-// while still a float, so NaN (-> -n), +-inf and huge flows never reach the
-// float -> int conversion and every tap index stays in the plane.
-__device__ __forceinline__ int split_disp(float &d, int n, float &frac) {
-    d = fminf(fmaxf(d, -(float)n), (float)n);
-    const float fl = floorf(d);
-    frac = d - fl;
-    return (int)fl;
-}
-
-__device__ __forceinline__ int clampi(int p, int len) { return min(max(p, 0), len - 1); }
-
-// img (one pair's plane) at (y + 8 v, x + 8 u): KW's sample.  in: the target
-// is within half a pixel of the frame (KC's test); nearest: index in the
-// plane of the source pixel nearest to the target.
+// img (one pair's plane) at (y + 8 v, x + 8 u): KW's sample, the positions,
+// weights and lerps of hsflow_sampler.h (shared with the colour kernels of
+// hsflow_interp_bgr.hip).  in: the target is within half a pixel of the frame
+// (KC's test); nearest: index in the plane of the source pixel nearest to the
+// target.
 template <typename T>
 __device__ __forceinline__ float sample(const T *__restrict__ img, int rows, int cols, int x,
                                         int y, float u, float v, bool &in, int &nearest) {
     using F = typename SampleMath<T>::type;
-    float dx = 8.0f * u, dy = 8.0f * v, fx, fy;
-    const int ix = split_disp(dx, cols, fx);
-    const int iy = split_disp(dy, rows, fy);
-    // |ix| <= cols, |iy| <= rows: the sums cannot overflow
-    const int xa = clampi(x + ix, cols), xb = clampi(x + ix + 1, cols);
-    const int ya = clampi(y + iy, rows), yb = clampi(y + iy + 1, rows);
-    const T *top = img + (size_t)ya * cols;
-    const T *bot = img + (size_t)yb * cols;
-    const F ta = (F)top[xa], tb = (F)top[xb], ba = (F)bot[xa], bb = (F)bot[xb];
-    // exact at fx = fy = 0: zero flow returns the pixel itself
-    const F t = ta + (F)fx * (tb - ta);
-    const F w = ba + (F)fx * (bb - ba);
-    const F r = t + (F)fy * (w - t);
-    const float tx = (float)x + dx, ty = (float)y + dy;
-    in = tx >= -0.5f && tx <= (float)cols - 0.5f && ty >= -0.5f && ty <= (float)rows - 0.5f;
-    nearest = (fy >= 0.5f ? yb : ya) * cols + (fx >= 0.5f ? xb : xa);  // < rows * cols <= 2^29
-    return (float)r;
+    const Taps t = sample_taps(rows, cols, x, y, u, v, in, nearest);
+    const T *top = img + (size_t)t.ya * cols;
+    const T *bot = img + (size_t)t.yb * cols;
+    const F ta = (F)top[t.xa], tb = (F)top[t.xb], ba = (F)bot[t.xa], bb = (F)bot[t.xb];
+    return (float)lerp_taps<F>(ta, tb, ba, bb, t.fx, t.fy);
 }
 
 // ---- KR: block 64 x 4, one pixel per thread (KW's map);
@@ -121,32 +101,6 @@ void launch_warp_t(const void *I, const float *u, const float *v, int rows, int 
 
 // ---- KI
 constexpr int kThreads = 256, kPix = 2, kTile = kThreads * kPix;
-
-// value of lane `Q` of the caller's quad (DPP quad_perm broadcast)
-template <int Q>
-__device__ __forceinline__ uint32_t quad_lane(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, Q * 0x55, 0xf, 0xf, true);
-}
-
-// One byte per lane into a u8 plane at dst + pk (pk: the lane's pixel, q0 its
-// quad's first): an aligned dword per quad where the quad lies in the plane
-// and its address allows, else a byte per valid lane.  Every lane of the wave
-// calls (the exchange needs them all).
-__device__ __forceinline__ void store_quad_u8(uint8_t *dst, int pk, int q0, int plane,
-                                              bool valid, uint32_t byte, int lane) {
-    const uint32_t quad = byte | quad_lane<1>(byte) << 8 | quad_lane<2>(byte) << 16 |
-                          quad_lane<3>(byte) << 24;
-    if (q0 + 3 < plane && (((uintptr_t)dst + (size_t)q0) & 3) == 0) {  // q0 >= 0 always
-        if ((lane & 3) == 0) *reinterpret_cast<uint32_t *>(dst + q0) = quad;
-    } else if (valid) {
-        dst[pk] = (uint8_t)byte;
-    }
-}
-
-// the times of one launch, by value in the kernel arguments
-struct InterpTimes {
-    float t[kInterpMaxTimes];
-};
 
 // grid (blocks per pair, batch)
 template <typename T>
@@ -201,19 +155,15 @@ __global__ __launch_bounds__(kThreads) void hs_frame_interp_kernel(
                 int n0, n1;
                 const float s0 = sample(p0, rows, cols, x[k], y[k], u0, v0, in0, n0);
                 const float s1 = sample(p1, rows, cols, x[k], y[k], u1, v1, in1, n1);
-                const float wt = in0 == in1 ? tt : (in0 ? 0.0f : 1.0f);
-                const float o =
-                    wt == 0.0f ? s0 : (wt == 1.0f ? s1 : (1.0f - wt) * s0 + wt * s1);
+                const float wt = blend_weight(in0, in1, tt);
+                const float o = blend(wt, s0, s1);
                 uint32_t fl = (in0 ? 0u : 1u) | (in1 ? 0u : 2u);
                 if (mf) fl |= mf[n0] != 0 ? 4u : 0u;  // uniform
                 if (mb) fl |= mb[n1] != 0 ? 8u : 0u;  // uniform
                 good += valid && fl == 0u;
                 const int q0 = pk[k] - (t & 3);  // the quad's first pixel
                 if (out_u8) {                    // uniform
-                    // floorf(o + 0.5f) clamped to 0..255; NaN -> 0 (fmaxf drops it)
-                    const float r = fminf(fmaxf(floorf(o + 0.5f), 0.0f), 255.0f);
-                    store_quad_u8((uint8_t *)out + obase, pk[k], q0, plane, valid, (uint32_t)r,
-                                  t);
+                    store_quad_u8((uint8_t *)out + obase, pk[k], q0, plane, valid, round_u8(o), t);
                 } else if (valid) {
                     ((float *)out)[obase + pk[k]] = o;
                 }
@@ -242,8 +192,8 @@ void launch_interp_t(const void *I0, const void *I1, const float *uf, const floa
                      hipStream_t s) {
     const size_t plane = (size_t)rows * cols;
     const int ntiles = (int)((plane + kTile - 1) / kTile);
-    // six blocks of four waves are resident per CU (72 VGPRs, 78 for f64
-    // frames: 7 and 6 waves per SIMD); more blocks would wait for a slot and
+    // six blocks of four waves are resident per CU (64 to 68 VGPRs: 7 waves
+    // per SIMD; the cap predates that count); more blocks would wait for a slot and
     // only add atomics on the counts, which share a cache line
     const int cap = std::max(1, (6 * device_cus() + batch - 1) / batch);
     dim3 blk(kThreads, 1, 1), grd(std::min(ntiles, cap), batch, 1);

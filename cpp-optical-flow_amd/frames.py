@@ -21,7 +21,9 @@ PyAV), so the seekable sources here are the containers that need none:
 `read(i)` returns BGR uint8 (H x W x 3) or gray (H x W) like imread would;
 `capture_pair(src, prev, next)` is main.cpp:53-59; `solve_stream` feeds
 consecutive pairs to frame_parallel.run_stream with the BGR->gray
-conversion on the GPU (hsflow_bgr_to_gray_device) and libhsflow as solver.
+conversion on the GPU (hsflow_bgr_to_gray_device) and libhsflow as solver;
+`interpolate_sequence` yields a BGR source at a multiple of its frame rate
+(hsflow_flow_interp_bgr: the motion-compensated colour frames in between).
 """
 from __future__ import annotations
 
@@ -320,3 +322,48 @@ def solve_stream(src, pairs: Sequence[Tuple[int, int]], window: int, iters: int,
     if rank != 0 or not gather:
         return None
     return None if on_flow is not None else out
+
+
+# ------------------------------------------------------- frame interpolation
+def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int, iters: int,
+                         alpha: float, median: int = 0, context=None):
+    """A colour source at `factor` times its frame rate: a generator of
+    (len(src) - 1) * factor + 1 BGR uint8 frames.  Every factor-th one is a
+    source frame itself, untouched; between two consecutive source frames come
+    the factor - 1 frames at t = j / factor, from one Context.interpolate_bgr
+    call per pair (the bidirectional warped solve on the grey frames, then the
+    motion-compensated blend of each channel).  `src.read(i)` must return BGR
+    (H x W x 3); a grey source raises FrameError (use Context.interpolate).
+    `context`: an hsflow.Context to run on (default: hsflow.default_context())."""
+    factor = int(factor)
+    if factor < 1:
+        raise ValueError("factor must be at least 1")
+    n = len(src)
+    if n == 0:
+        return
+    prev = _bgr_frame(src, 0)
+    yield prev
+    times = [j / factor for j in range(1, factor)]
+    ctx = context
+    for i in range(1, n):
+        nxt = _bgr_frame(src, i)
+        if nxt.shape != prev.shape:
+            raise FrameError("Image sizes are different")  # main.cpp:70-73
+        if times:
+            if ctx is None:
+                import hsflow
+                ctx = hsflow.default_context()
+            mid = ctx.interpolate_bgr(prev, nxt, times, levels, warps, window, iters, alpha,
+                                      median=median, out_dtype=np.uint8)
+            for k in range(len(times)):
+                yield mid[k]
+        yield nxt
+        prev = nxt
+
+
+def _bgr_frame(src, i: int) -> np.ndarray:
+    a = np.asarray(src.read(i))
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+        raise FrameError(f"frame {i} is not 8-bit BGR (H x W x 3): interpolate_sequence needs a "
+                         "colour source; for grey frames use Context.interpolate")
+    return a

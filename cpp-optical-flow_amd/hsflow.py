@@ -82,6 +82,9 @@ EXPORTS = (
     "hsflow_flow_interp_workspace_bytes", "hsflow_flow_interp_device", "hsflow_flow_interp",
     "hsflow_set_first_pass_fusion", "hsflow_first_pass_fusion",
     "hsflow_first_pass_launches",
+    "hsflow_warp_image_bgr_device", "hsflow_frame_interp_bgr_device",
+    "hsflow_flow_interp_bgr_workspace_bytes", "hsflow_flow_interp_bgr_device",
+    "hsflow_flow_interp_bgr", "hsflow_set_interp_bgr_loads",
 )
 
 
@@ -204,6 +207,17 @@ def lib():
     L.hsflow_flow_interp.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
                                      ctypes.c_double, f, f, fp, i, ctypes.POINTER(_vp), i, _sz,
                                      ctypes.POINTER(_vp), _sz, _vp]
+    L.hsflow_warp_image_bgr_device.argtypes = [_vp, i, i, i, _vp, _vp, _vp, i, _vp, _vp]
+    L.hsflow_frame_interp_bgr_device.argtypes = [_vp, _vp, i, i, i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 fp, i, _vp, i, _vp, _vp, _vp]
+    L.hsflow_flow_interp_bgr_workspace_bytes.argtypes = [i, i, i, i]
+    L.hsflow_flow_interp_bgr_workspace_bytes.restype = _sz
+    L.hsflow_flow_interp_bgr_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f, fp, i,
+                                                _vp, i, _vp, _vp, _vp, _sz, _vp]
+    L.hsflow_flow_interp_bgr.argtypes = [_vp, _vp, _vp, i, i, _sz, _sz, i, i, i, i, i,
+                                         ctypes.c_double, f, f, fp, i, ctypes.POINTER(_vp), i,
+                                         _sz, ctypes.POINTER(_vp), _sz, _vp]
+    L.hsflow_set_interp_bgr_loads.argtypes = [i]
     L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               _vp, _sz, _vp]
@@ -447,6 +461,47 @@ class Context:
             b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
             float(alpha), float(rel), float(abs), tm, nt, planes, _dtype_code(out),
             out.strides[1], fplanes, cols, trusted.ctypes.data if with_flags else None)
+        _check(rc, self._p)
+        return (out, flags, trusted) if with_flags else out
+
+    def interpolate_bgr(self, bgr0, bgr1, times, levels: int, warps: int, window: int,
+                        iters: int, alpha: float, median: int = 0,
+                        rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
+                        out_dtype=np.uint8, with_flags: bool = False):
+        """The colour frames at `times` between two decoded 8-bit BGR frames
+        (H x W x 3, strided rows accepted): uploaded as BGR, converted to grey
+        and solved both ways on the GPU, then the motion-compensated blend of
+        each channel (hsflow_flow_interp_bgr in include/hsflow.h).  Returns an
+        array [len(times), rows, cols, 3] of out_dtype (uint8 or float32), or
+        with_flags: (frames, flags, trusted) -- flags uint8 [len(times), rows,
+        cols] and trusted uint32 [len(times)] as in interpolate."""
+        a = np.asarray(bgr0)
+        b = np.asarray(bgr1)
+        for x in (a, b):
+            if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
+                raise HsflowError(HSFLOW_ERR_ARG, "need H x W x 3 BGR uint8 (grey frames: "
+                                  "Context.interpolate)")
+        if a.shape != b.shape:
+            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
+        if a.strides[1:] != (3, 1) or a.strides[0] < 3 * a.shape[1]:
+            a = np.ascontiguousarray(a)
+        if b.strides[1:] != (3, 1) or b.strides[0] < 3 * b.shape[1]:
+            b = np.ascontiguousarray(b)
+        rows, cols = a.shape[:2]
+        tm = _times_array(times)
+        nt = len(tm)
+        out = np.empty((nt, rows, cols, 3), out_dtype)
+        if out.dtype not in (np.uint8, np.float32):
+            raise HsflowError(HSFLOW_ERR_ARG, "out_dtype: need uint8 or float32")
+        flags = np.empty((nt, rows, cols), np.uint8) if with_flags else None
+        trusted = np.zeros(nt, np.uint32) if with_flags else None
+        planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
+        fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
+        rc = lib().hsflow_flow_interp_bgr(
+            self._p, a.ctypes.data, b.ctypes.data, rows, cols, a.strides[0], b.strides[0],
+            int(levels), int(warps), int(median), int(window), int(iters), float(alpha),
+            float(rel), float(abs), tm, nt, planes, _dtype_code(out), out.strides[1] if nt else 0,
+            fplanes, cols, trusted.ctypes.data if with_flags else None)
         _check(rc, self._p)
         return (out, flags, trusted) if with_flags else out
 
@@ -1033,6 +1088,133 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
             _stream_ptr(stream, I0.device))
     _check(rc)
     return out, flags, trusted
+
+
+def _check_bgr(t, name):
+    """A batch of dense interleaved BGR frames: uint8, contiguous, CUDA,
+    [B, H, W, 3] or [H, W, 3].  Returns (rows, cols, batch)."""
+    if torch is None or not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or \
+            t.dim() not in (3, 4) or t.shape[-1] != 3 or not t.is_cuda or not t.is_contiguous():
+        raise HsflowError(HSFLOW_ERR_ARG, f"{name}: need a contiguous uint8 CUDA tensor "
+                          "[B, H, W, 3] or [H, W, 3]")
+    return t.shape[-3], t.shape[-2], (t.shape[0] if t.dim() == 4 else 1)
+
+
+def _bgr_interp_outputs(bgr0, nt, out, out_dtype, flags, trusted):
+    """out / flags / trusted of a BGR interpolation of `nt` times:
+    [B, nt, H, W, 3] ([nt, H, W, 3]), [B, nt, H, W] and [B, nt]."""
+    rows, cols, batch = _check_bgr(bgr0, "bgr0")
+    lead = tuple(bgr0.shape[:-3])
+    if out is None:
+        out = torch.empty(lead + (nt, rows, cols, 3), dtype=out_dtype, device=bgr0.device)
+    if out.dtype not in (torch.float32, torch.uint8):
+        raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
+    out = _check_output(out, lead + (nt, rows, cols, 3), out.dtype, bgr0.device, "out")
+    flags = _check_output(flags, lead + (nt, rows, cols), torch.uint8, bgr0.device, "flags")
+    trusted = _check_output(trusted, (batch, nt), torch.int32, bgr0.device, "trusted")
+    return out, flags, trusted
+
+
+def warp_image_bgr_device(bgr, u, v, out=None, out_dtype=None, oof=None, stream=None):
+    """warp_image_device for colour frames: bgr a uint8 CUDA tensor [B, H, W, 3]
+    or [H, W, 3], (u, v) float32 [B, H, W] in solver units; out(y, x, c) =
+    bgr(.., c) at (y + 8 v, x + 8 u), each channel the bits warp_image_device
+    gives its plane (hsflow_warp_image_bgr_device in include/hsflow.h).  out:
+    float32 (default) or uint8, like bgr; oof: True / a uint8 tensor [B, H, W].
+    Returns out, or (out, oof) when oof was asked for.  Stream-ordered."""
+    rows, cols, batch = _check_bgr(bgr, "bgr")
+    _check_plane(u, (rows, cols), batch, "u")
+    _check_plane(v, (rows, cols), batch, "v")
+    if out is None:
+        out = torch.empty(bgr.shape, dtype=out_dtype or torch.float32, device=bgr.device)
+    if out.dtype not in (torch.float32, torch.uint8):
+        raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
+    out = _check_output(out, bgr.shape, out.dtype, bgr.device, "out")
+    oof = _check_output(oof, bgr.shape[:-1], torch.uint8, bgr.device, "oof")
+    with _on(bgr.device):
+        rc = lib().hsflow_warp_image_bgr_device(
+            bgr.data_ptr(), rows, cols, batch, u.data_ptr(), v.data_ptr(), out.data_ptr(),
+            U8 if out.dtype == torch.uint8 else F32, oof.data_ptr() if oof is not None else None,
+            _stream_ptr(stream, bgr.device))
+    _check(rc)
+    return out if oof is None else (out, oof)
+
+
+def frame_interp_bgr_device(bgr0, bgr1, uf, vf, ub, vb, times, mask_f=None, mask_b=None,
+                            out=None, out_dtype=None, flags=None, trusted=None, stream=None):
+    """frame_interp_device for colour frames: bgr0, bgr1 uint8 CUDA tensors
+    [B, H, W, 3] or [H, W, 3]; flows, masks and times as there (the flow is a
+    grey-level quantity).  out: float32 (default) or uint8, [B, len(times), H,
+    W, 3], channel c the bits frame_interp_device gives the plane bgr[..., c];
+    flags [B, len(times), H, W] and trusted [B, len(times)] are per pixel
+    (hsflow_frame_interp_bgr_device in include/hsflow.h).  Returns (out, flags,
+    trusted), None for those not asked for.  Stream-ordered."""
+    if out_dtype is None:
+        out_dtype = torch.float32
+    rows, cols, batch = _check_bgr(bgr0, "bgr0")
+    _check_bgr(bgr1, "bgr1")
+    if bgr1.shape != bgr0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "bgr0/bgr1 differ in shape")
+    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
+        _check_plane(t, (rows, cols), batch, name)
+    for t, name in ((mask_f, "mask_f"), (mask_b, "mask_b")):
+        if t is not None:
+            _check_output(t, bgr0.shape[:-1], torch.uint8, bgr0.device, name)
+    tm = _times_array(times)
+    out, flags, trusted = _bgr_interp_outputs(bgr0, len(tm), out, out_dtype, flags, trusted)
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    with _on(bgr0.device):
+        rc = lib().hsflow_frame_interp_bgr_device(
+            bgr0.data_ptr(), bgr1.data_ptr(), rows, cols, batch, uf.data_ptr(), vf.data_ptr(),
+            ub.data_ptr(), vb.data_ptr(), ptr(mask_f), ptr(mask_b), tm, len(tm), out.data_ptr(),
+            U8 if out.dtype == torch.uint8 else F32, ptr(flags), ptr(trusted),
+            _stream_ptr(stream, bgr0.device))
+    _check(rc)
+    return out, flags, trusted
+
+
+def flow_interp_bgr_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -> int:
+    return int(lib().hsflow_flow_interp_bgr_workspace_bytes(rows, cols, batch, levels))
+
+
+def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: int, iters: int,
+                           alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
+                           abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
+                           trusted=None, workspace=None, stream=None):
+    """bgr_to_gray_device of both frames, flow_bidir_device(median=...) on the
+    grey planes, then frame_interp_bgr_device with both masks: one call, the
+    same bits (hsflow_flow_interp_bgr_device in include/hsflow.h).
+    `workspace`: flow_interp_bgr_workspace_bytes(rows, cols, batch, levels)
+    bytes.  Returns (out, flags, trusted) as frame_interp_bgr_device.
+    Stream-ordered."""
+    if out_dtype is None:
+        out_dtype = torch.float32
+    rows, cols, batch = _check_bgr(bgr0, "bgr0")
+    _check_bgr(bgr1, "bgr1")
+    if bgr1.shape != bgr0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "bgr0/bgr1 differ in shape")
+    tm = _times_array(times)
+    out, flags, trusted = _bgr_interp_outputs(bgr0, len(tm), out, out_dtype, flags, trusted)
+    if workspace is None:
+        n = flow_interp_bgr_workspace_bytes(rows, cols, batch, levels)
+        workspace = torch.empty(n, dtype=torch.uint8, device=bgr0.device)
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    with _on(bgr0.device):
+        rc = lib().hsflow_flow_interp_bgr_device(
+            bgr0.data_ptr(), bgr1.data_ptr(), rows, cols, batch, int(levels), int(warps),
+            int(median), int(window), int(iters), float(alpha), float(rel), float(abs), tm,
+            len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32, ptr(flags),
+            ptr(trusted), workspace.data_ptr(), workspace.numel(),
+            _stream_ptr(stream, bgr0.device))
+    _check(rc)
+    return out, flags, trusted
+
+
+def set_interp_bgr_loads(wide: bool) -> bool:
+    """hsflow_set_interp_bgr_loads: the BGR kernels fetch a row's two adjacent
+    taps as six bytes (False, default) or as one unaligned dword and halfword;
+    same bits.  Returns the previous setting."""
+    return bool(lib().hsflow_set_interp_bgr_loads(1 if wide else 0))
 
 
 def warp_gradients_device(I0, I1, u0, v0, workspace, gx=None, gy=None, gt=None, stream=None):

@@ -536,6 +536,75 @@ int hsflow_flow_interp(hsflow_ctx *ctx, const void *I0, const void *I1, int dtyp
                        size_t out_step, uint8_t *const *flags, size_t flags_step,
                        uint32_t *trusted);
 
+/* ---- frame warp and frame interpolation of colour frames -----------------
+ * The pipeline's input is colour (main.cpp decodes 8-bit BGR), the flow a
+ * grey-level quantity: only the sampling has to know about channels.  Frames
+ * are dense 8-bit interleaved BGR, [batch][rows][cols][3], what
+ * hsflow_bgr_to_gray_device reads.  Per output pixel the flows, the two
+ * targets, their taps and fractions, in0, in1, n0, n1, wt and flags are those
+ * of hsflow_frame_interp_device, computed once; its three lerps and its blend
+ * then run on each channel, so channel c of the result equals, bit for bit,
+ * hsflow_frame_interp_device on the u8 plane bgr[..][c] with the same flows,
+ * masks and times.  flags and trusted are per pixel, not per channel.  No
+ * index leaves a pair's plane, whatever the flows hold. */
+#define HSFLOW_HAS_INTERP_BGR 1
+
+/* hsflow_warp_image_device for BGR frames: out(y, x, c) = bgr(.., c) at
+ * (y + 8 v, x + 8 u).  out: [batch][rows][cols][3] of dtype_out, HSFLOW_F32 or
+ * HSFLOW_U8 (floorf(out + 0.5f) clamped to 0..255); oof (u8, may be NULL):
+ * [batch][rows][cols].  The outputs must not overlap the inputs or each other.
+ * Stream-ordered, no workspace, never allocates or synchronises, capturable. */
+int hsflow_warp_image_bgr_device(const uint8_t *bgr, int rows, int cols, int batch, const float *u,
+                                 const float *v, void *out, int dtype_out, uint8_t *oof,
+                                 void *stream);
+
+/* hsflow_frame_interp_device for BGR frames, same conventions (NULL masks,
+ * flags and trusted allowed; trusted zeroed stream-ordered by the call; the
+ * outputs disjoint from the inputs and from each other; all arguments checked
+ * before any device work).  out: [batch][nt][rows][cols][3] of dtype_out,
+ * HSFLOW_F32 or HSFLOW_U8; flags: u8 [batch][nt][rows][cols]; trusted:
+ * uint32[batch][nt].  Stream-ordered, no workspace, never allocates or
+ * synchronises, capturable. */
+int hsflow_frame_interp_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                   int batch, const float *uf, const float *vf, const float *ub,
+                                   const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
+                                   const float *times, int nt, void *out, int dtype_out,
+                                   uint8_t *flags, uint32_t *trusted, void *stream);
+
+/* Convert, solve and interpolate in one call: hsflow_bgr_to_gray_device of
+ * both frames into the workspace, hsflow_flow_bidir_median_device on the grey
+ * u8 planes (both masks only when flags or trusted is asked for), then
+ * hsflow_frame_interp_bgr_device on the BGR frames -- bit for bit what the
+ * three calls give one after the other.  `workspace`: at least
+ * hsflow_flow_interp_bgr_workspace_bytes(rows, cols, batch, levels) bytes
+ * (hsflow_flow_interp_workspace_bytes plus two grey u8 planes), 256-byte
+ * aligned; it must not overlap the frames. */
+size_t hsflow_flow_interp_bgr_workspace_bytes(int rows, int cols, int batch, int levels);
+int hsflow_flow_interp_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                  int batch, int levels, int warps, int median, int window,
+                                  int iters, float alpha, float rel, float abs_thr,
+                                  const float *times, int nt, void *out, int dtype_out,
+                                  uint8_t *flags, uint32_t *trusted, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+/* Host-buffer, blocking form: two decoded 8-bit BGR frames (row steps
+ * bgr_step0, bgr_step1 bytes) go up as 3 B/px, as hsflow_flow_bgr sends them.
+ * out: `nt` host planes of rows x cols BGR pixels of dtype_out (HSFLOW_U8 or
+ * HSFLOW_F32), row step out_step >= 3 * cols * element size bytes; flags and
+ * trusted as in hsflow_flow_interp. */
+int hsflow_flow_interp_bgr(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                           int cols, size_t bgr_step0, size_t bgr_step1, int levels, int warps,
+                           int median, int window, int iters, double alpha, float rel,
+                           float abs_thr, const float *times, int nt, void *const *out,
+                           int dtype_out, size_t out_step, uint8_t *const *flags,
+                           size_t flags_step, uint32_t *trusted);
+
+/* How the BGR kernels fetch the two horizontally adjacent taps of a row (six
+ * consecutive bytes unless the pair is clamped at a frame edge): wide = 0
+ * (default, the faster one measured) as six single bytes, wide != 0 as one
+ * unaligned dword and one halfword.  Both give identical bits (DESIGN.md has
+ * the timings).  Process-wide; returns the previous setting. */
+int hsflow_set_interp_bgr_loads(int wide);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

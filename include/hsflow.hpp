@@ -54,6 +54,14 @@ inline ImageView view(const double *p, int rows, int cols, size_t step = 0) {
     return {p, rows, cols, step ? step : (size_t)cols * 8, HSFLOW_F64};
 }
 
+// One decoded 8-bit colour frame, interleaved BGR (CV_8UC3, what cv::imread
+// returns); `step` = bytes between rows, 0 = dense (3 * cols).
+struct BgrView {
+    const uint8_t *data = nullptr;
+    int rows = 0, cols = 0;
+    size_t step = 0;
+};
+
 // RAII device context (device, stream, cached buffers).
 class Context {
   public:
@@ -193,6 +201,38 @@ class HornSchunck {
                         std::vector<std::vector<float>> &planes,
                         std::vector<std::vector<uint8_t>> &flags) {
         getFrameInterp(imagePrev, imageNext, times, levels, warps, median, planes, &flags);
+    }
+
+    // getFrameInterp for colour frames (hsflow.h, hsflow_flow_interp_bgr): the
+    // frames go up as BGR, the solve runs on their grey conversion, and each
+    // channel gets the motion-compensated blend.  frames[k]: the frame at
+    // times[k] as rows*cols*3 uint8, interleaved BGR; flags[k]: rows*cols
+    // HSFLOW_INTERP_* bytes, one per pixel.
+    void getFrameInterpBgr(const BgrView &prev, const BgrView &next,
+                           const std::vector<float> &times, int levels, int warps, int median,
+                           std::vector<std::vector<uint8_t>> &frames,
+                           std::vector<std::vector<uint8_t>> *flags = nullptr) {
+        if (!prev.data || !next.data) throw Error(HSFLOW_ERR_ARG, "empty image");
+        if (prev.rows != next.rows || prev.cols != next.cols)
+            throw Error(HSFLOW_ERR_SIZE, "Image sizes are different");
+        const size_t n = (size_t)prev.rows * prev.cols;
+        frames.resize(times.size());
+        if (flags) flags->resize(times.size());
+        std::vector<void *> out(times.size());
+        std::vector<uint8_t *> fl(times.size());
+        for (size_t k = 0; k < times.size(); ++k) {
+            frames[k].resize(n * 3);
+            out[k] = frames[k].data();
+            if (flags) (*flags)[k].resize(n), fl[k] = (*flags)[k].data();
+        }
+        const size_t dense = (size_t)prev.cols * 3;
+        Context &c = ctx();
+        c.check(hsflow_flow_interp_bgr(
+            c.get(), prev.data, next.data, prev.rows, prev.cols, prev.step ? prev.step : dense,
+            next.step ? next.step : dense, levels, warps, median, windowSize, maxIterations,
+            alpha, HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS, times.data(),
+            (int)times.size(), out.data(), HSFLOW_U8, dense, flags ? fl.data() : nullptr,
+            (size_t)prev.cols, nullptr));
     }
 
     // Raw form for callers that own output rows (cv::Mat adapter): dtype_out
