@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +41,9 @@ struct hsflow_ctx {
     size_t h_stage_bytes = 0;
     // one event per downloaded row chunk (created on first use)
     std::vector<hipEvent_t> dl_ev;
+    // hsflow_ctx_set_prefilter: what the warped, bidirectional and interpolating
+    // host-buffer calls run on the frames first (mode 0: nothing)
+    hsflow_prefilter pf{0, 0.0f, 0.0f, 0.0f};
 };
 
 namespace {
@@ -940,6 +944,167 @@ int bidir_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
     return rc;
 }
 
+// ---- brightness-robust prefilter --------------------------------------------
+// A checked hsflow_prefilter: the radius and the Gaussian's weights w[0..radius],
+// normalised to sum 1 (w[0] + 2 sum w[i]) in double and rounded to f32 once.
+struct PfPlan {
+    int mode, radius;
+    float w[HSFLOW_PREFILTER_MAX_RADIUS + 1];
+    float eps, scale;
+};
+
+bool pf_on(const hsflow_prefilter *pf) { return pf && pf->mode != 0; }
+
+int plan_prefilter(hsflow_ctx *ctx, const hsflow_prefilter *pf, PfPlan *P) {
+    if (!pf) return fail(ctx, HSFLOW_ERR_ARG, "null prefilter");
+    if (pf->mode != HSFLOW_PREFILTER_HIGHPASS && pf->mode != HSFLOW_PREFILTER_NORMALIZE)
+        return fail(ctx, HSFLOW_ERR_ARG, "prefilter mode %d is not 1 or 2", pf->mode);
+    // negated comparisons: NaN fails
+    if (!(pf->sigma >= 0.5f && pf->sigma <= 5.0f))
+        return fail(ctx, HSFLOW_ERR_ARG, "prefilter sigma %g outside [0.5, 5]", (double)pf->sigma);
+    if (!(pf->eps > 0.0f && pf->eps <= 3.0e38f))
+        return fail(ctx, HSFLOW_ERR_ARG, "prefilter eps %g must be finite and > 0",
+                    (double)pf->eps);
+    if (!(pf->scale > 0.0f && pf->scale <= 3.0e38f))
+        return fail(ctx, HSFLOW_ERR_ARG, "prefilter scale %g must be finite and > 0",
+                    (double)pf->scale);
+    const double sigma = (double)pf->sigma;
+    P->mode = pf->mode;
+    P->radius = std::min((int)std::ceil(3.0 * sigma), HSFLOW_PREFILTER_MAX_RADIUS);
+    P->eps = pf->eps;
+    P->scale = pf->scale;
+    double w[HSFLOW_PREFILTER_MAX_RADIUS + 1], sum = 0.0;
+    for (int i = 0; i <= P->radius; ++i) {
+        w[i] = std::exp(-(double)(i * i) / (2.0 * sigma * sigma));
+        sum += i ? 2.0 * w[i] : w[i];
+    }
+    for (int i = 0; i <= HSFLOW_PREFILTER_MAX_RADIUS; ++i)
+        P->w[i] = i <= P->radius ? (float)(w[i] / sum) : 0.0f;
+    return HSFLOW_OK;
+}
+
+// the two f32 planes the *_pf solves prefilter the frames into
+size_t pf_planes_bytes(int rows, int cols, int batch) {
+    return 2 * align_up((size_t)rows * cols * batch * 4);
+}
+
+int prefilter_run(hsflow_ctx *ctx, const void *I, int dtype_in, int rows, int cols, int batch,
+                  const PfPlan &P, float *out, hipStream_t s) {
+    hipError_t e = hsflow::launch_prefilter(I, dtype_in, rows, cols, batch, P.mode, P.radius, P.w,
+                                            P.eps, P.scale, out, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "prefilter launch");
+    return HSFLOW_OK;
+}
+
+int prefilter_impl(hsflow_ctx *ctx, const void *I, int dtype_in, int rows, int cols, int batch,
+                   const hsflow_prefilter *pf, float *out, hipStream_t s) {
+    PfPlan P;
+    int rc = plan_prefilter(ctx, pf, &P);
+    if (rc) return rc;
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!device_dtype_ok(dtype_in))
+        return fail(ctx, HSFLOW_ERR_ARG, "device input dtype must be U8, F16, F32 or F64");
+    if (!I || !out) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    const size_t n = (size_t)rows * cols * batch;
+    const uintptr_t pi = (uintptr_t)I, po = (uintptr_t)out;
+    if (pi < po + n * 4 && po < pi + n * elem_size(dtype_in))
+        return fail(ctx, HSFLOW_ERR_ARG, "prefilter output overlaps the input");
+    return prefilter_run(ctx, I, dtype_in, rows, cols, batch, P, out, s);
+}
+
+// What a *_pf solve does in front of the call it extends, whose own workspace
+// is the first `solve_bytes` (256-aligned) of `ws`: the checks, then KN on both
+// frames into the two planes behind it.  The caller has checked sizes, dtype
+// and the pointers.
+int prefilter_pair(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                   int cols, int batch, const PfPlan &P, void *ws, size_t solve_bytes,
+                   float **p0, float **p1, hipStream_t s) {
+    const size_t n = (size_t)rows * cols * batch;
+    *p0 = (float *)((char *)ws + solve_bytes);
+    *p1 = (float *)((char *)ws + solve_bytes + align_up(n * 4));
+    int rc = prefilter_run(ctx, I0, dtype_in, rows, cols, batch, P, *p0, s);
+    if (rc) return rc;
+    return prefilter_run(ctx, I1, dtype_in, rows, cols, batch, P, *p1, s);
+}
+
+// the frames of a *_pf solve must not share a byte with its workspace: the
+// planes are written while the frames are still to be read
+int check_pf_workspace(hsflow_ctx *ctx, const void *I0, const void *I1, size_t frame_bytes,
+                       const void *ws, size_t ws_bytes, size_t need) {
+    if (ws_bytes < need)
+        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, need);
+    const uintptr_t w = (uintptr_t)ws;
+    for (const void *I : {I0, I1}) {
+        const uintptr_t p = (uintptr_t)I;
+        if (p < w + need && w < p + frame_bytes)
+            return fail(ctx, HSFLOW_ERR_ARG, "the frames overlap the workspace");
+    }
+    return HSFLOW_OK;
+}
+
+// hsflow_flow_warped_pf_device: KN on both frames, then warped_impl on the planes
+// as f32 frames (not integer-valued, so the pyramid does not round them) -- the
+// public pieces one after the other, so the bits are theirs by construction.
+// No prefilter: warped_impl itself.
+int warped_pf_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                   int cols, int batch, int levels, int warps, int median, int window, int iters,
+                   float alpha, float *u, float *v, const hsflow_prefilter *pf, void *ws,
+                   size_t ws_bytes, hipStream_t s) {
+    if (!pf_on(pf))
+        return warped_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
+                           iters, alpha, u, v, ws, ws_bytes, s);
+    PfPlan P;
+    int rc = plan_prefilter(ctx, pf, &P);
+    if (rc) return rc;
+    if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
+    rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, u, v, ws, ws_bytes);
+    if (rc) return rc;
+    const size_t solve = align_up(pyr_layout(rows, cols, batch, levels).bytes);
+    rc = check_pf_workspace(ctx, I0, I1, (size_t)rows * cols * batch * elem_size(dtype_in), ws,
+                            ws_bytes, solve + pf_planes_bytes(rows, cols, batch));
+    if (rc) return rc;
+    float *p0, *p1;
+    rc = prefilter_pair(ctx, I0, I1, dtype_in, rows, cols, batch, P, ws, solve, &p0, &p1, s);
+    if (rc) return rc;
+    return warped_impl(ctx, p0, p1, HSFLOW_F32, rows, cols, batch, levels, warps, median, window,
+                       iters, alpha, u, v, ws, solve, s);
+}
+
+// hsflow_flow_bidir_pf_device: likewise in front of bidir_impl
+int bidir_pf_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
+                  int cols, int batch, int levels, int warps, int median, int window, int iters,
+                  float alpha, float rel, float abs_thr, float *uf, float *vf, float *ub,
+                  float *vb, float *err_f, uint8_t *mask_f, uint32_t *counts_f, float *err_b,
+                  uint8_t *mask_b, uint32_t *counts_b, const hsflow_prefilter *pf, void *ws,
+                  size_t ws_bytes, hipStream_t s) {
+    if (!pf_on(pf))
+        return bidir_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
+                          iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f,
+                          err_b, mask_b, counts_b, ws, ws_bytes, s);
+    PfPlan P;
+    int rc = plan_prefilter(ctx, pf, &P);
+    if (rc) return rc;
+    if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
+    if ((rc = check_median_arg(ctx, median))) return rc;
+    rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, uf, vf, ws,
+                            ws_bytes);
+    if (rc) return rc;
+    if (!ub || !vb) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
+    const size_t solve = align_up(pyr_layout(rows, cols, batch, levels).bytes);
+    rc = check_pf_workspace(ctx, I0, I1, (size_t)rows * cols * batch * elem_size(dtype_in), ws,
+                            ws_bytes, solve + pf_planes_bytes(rows, cols, batch));
+    if (rc) return rc;
+    float *p0, *p1;
+    rc = prefilter_pair(ctx, I0, I1, dtype_in, rows, cols, batch, P, ws, solve, &p0, &p1, s);
+    if (rc) return rc;
+    return bidir_impl(ctx, p0, p1, HSFLOW_F32, rows, cols, batch, levels, warps, median, window,
+                      iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f, err_b,
+                      mask_b, counts_b, ws, solve, s);
+}
+
 // The host-buffer form of both pyramid solves: warps = 0 is hsflow_flow_pyramid,
 // warps >= 1 hsflow_flow_warped[_median] (same upload, download, f64 widening
 // and huge-page advice).
@@ -959,16 +1124,20 @@ int pyramid_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
     const size_t in_es = (size_t)dev_elem_size(dtype_in);
     if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * in_es) * 2))) return rc;
     if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, align_up(n * 4) * 3))) return rc;
-    const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels);
+    // the warped solves honour the context's prefilter (its planes lie behind
+    // the solve's workspace); hsflow_flow_pyramid keeps the reference's semantics
+    const bool pf = warps && pf_on(&ctx->pf);
+    const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels) +
+                       (pf ? pf_planes_bytes(rows, cols, 1) : 0);
     if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
     char *in0 = (char *)ctx->d_in, *in1 = in0 + align_up(n * in_es);
     float *du = (float *)ctx->d_out, *dv = (float *)((char *)du + align_up(n * 4));
     if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
         return rc;
     const int dt0 = dtype_in;
-    rc = warps ? warped_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, warps, median, window,
-                             iters, (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes,
-                             ctx->stream)
+    rc = warps ? warped_pf_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, warps, median, window,
+                                iters, (float)alpha, du, dv, &ctx->pf, ctx->d_ws,
+                                ctx->d_ws_bytes, ctx->stream)
                : pyramid_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, window, iters,
                               (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
@@ -1008,7 +1177,8 @@ int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
     const size_t fb = align_up(n * 4), mb = align_up(n);
     if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * in_es) * 2))) return rc;
     if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, fb * 4 + mb * 2 + kAlign))) return rc;
-    const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels);
+    const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels) +
+                       (pf_on(&ctx->pf) ? pf_planes_bytes(rows, cols, 1) : 0);
     if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
     char *in0 = (char *)ctx->d_in, *in1 = in0 + align_up(n * in_es);
     char *out = (char *)ctx->d_out;
@@ -1018,11 +1188,11 @@ int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
     uint32_t *dc = (uint32_t *)(dmb + mb);
     if ((rc = upload_pair(ctx, I0, I1, (int)in_es, rows, cols, in_step0, in_step1, in0, in1)))
         return rc;
-    rc = bidir_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, median, window, iters,
-                    (float)alpha, rel, abs_thr, d[0], d[1], d[2], d[3], nullptr,
-                    mask_f ? dmf : nullptr, counts ? dc : nullptr, nullptr,
-                    mask_b ? dmb : nullptr, counts ? dc + 3 : nullptr, ctx->d_ws,
-                    ctx->d_ws_bytes, ctx->stream);
+    rc = bidir_pf_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, median, window,
+                       iters, (float)alpha, rel, abs_thr, d[0], d[1], d[2], d[3], nullptr,
+                       mask_f ? dmf : nullptr, counts ? dc : nullptr, nullptr,
+                       mask_b ? dmb : nullptr, counts ? dc + 3 : nullptr, &ctx->pf, ctx->d_ws,
+                       ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
     if (mask_f)
         HIP_TRY(ctx, hipMemcpy2DAsync(mask_f, mask_step, dmf, (size_t)cols, (size_t)cols, rows,
@@ -1155,14 +1325,18 @@ InterpLayout interp_layout(int rows, int cols, int batch, int levels) {
 
 // hsflow_flow_bidir_median_device into the workspace's planes (the masks only
 // when flags or trusted needs them), then KI: the two public calls one after
-// the other, so the bits are theirs by construction.
+// the other, so the bits are theirs by construction.  With a prefilter (the
+// _pf entry point, or the context's setting) the solve runs on the two
+// prefiltered f32 planes behind that layout; KI samples the frames themselves.
 int flow_interp_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
                      int cols, int batch, int levels, int warps, int median, int window,
                      int iters, float alpha, float rel, float abs_thr, const float *times, int nt,
-                     void *out, int dtype_out, uint8_t *flags, uint32_t *trusted, void *ws,
-                     size_t ws_bytes, hipStream_t s) {
-    int rc = check_warped_args(ctx, warps, window, iters);
+                     void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
+                     const hsflow_prefilter *pf, void *ws, size_t ws_bytes, hipStream_t s) {
+    PfPlan P;
+    int rc = pf_on(pf) ? plan_prefilter(ctx, pf, &P) : HSFLOW_OK;
     if (rc) return rc;
+    if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
     if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
         return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
@@ -1175,25 +1349,36 @@ int flow_interp_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
     if ((rc = check_interp_args(ctx, times, nt, dtype_out, false))) return rc;
     const InterpLayout L = interp_layout(rows, cols, batch, levels);
-    if (ws_bytes < L.bytes)
-        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, L.bytes);
+    const size_t need = L.bytes + (pf_on(pf) ? pf_planes_bytes(rows, cols, batch) : 0);
+    if (ws_bytes < need)
+        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, need);
     const size_t n = (size_t)rows * cols * batch, fb = n * elem_size(dtype_in);
-    const ByteRange in[3] = {{I0, fb}, {I1, fb}, {ws, L.bytes}};
+    const ByteRange in[3] = {{I0, fb}, {I1, fb}, {ws, need}};
     const ByteRange outs[3] = {{out, n * nt * elem_size(dtype_out)},
                                {flags, n * nt},
                                {trusted, (size_t)batch * nt * 4}};
     if (!outputs_disjoint(in, 3, outs, 3))
         return fail(ctx, HSFLOW_ERR_ARG,
                     "interpolation outputs overlap the frames, the workspace or each other");
+    if (pf_on(pf) && (rc = check_pf_workspace(ctx, I0, I1, fb, ws, ws_bytes, need))) return rc;
     char *base = (char *)ws;
     float *f[4];
     for (int k = 0; k < 4; ++k) f[k] = (float *)(base + L.flow[k]);
     const bool masks = flags || trusted;
     uint8_t *mf = masks ? (uint8_t *)(base + L.mask[0]) : nullptr;
     uint8_t *mb = masks ? (uint8_t *)(base + L.mask[1]) : nullptr;
-    rc = bidir_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window, iters,
-                    alpha, rel, abs_thr, f[0], f[1], f[2], f[3], nullptr, mf, nullptr, nullptr, mb,
-                    nullptr, ws, L.solve_bytes, s);
+    // the frames the solve sees: the prefiltered planes, or the frames themselves
+    const void *S0 = I0, *S1 = I1;
+    int dtype_solve = dtype_in;
+    if (pf_on(pf)) {
+        float *p0, *p1;
+        rc = prefilter_pair(ctx, I0, I1, dtype_in, rows, cols, batch, P, ws, L.bytes, &p0, &p1, s);
+        if (rc) return rc;
+        S0 = p0, S1 = p1, dtype_solve = HSFLOW_F32;
+    }
+    rc = bidir_impl(ctx, S0, S1, dtype_solve, rows, cols, batch, levels, warps, median, window,
+                    iters, alpha, rel, abs_thr, f[0], f[1], f[2], f[3], nullptr, mf, nullptr,
+                    nullptr, mb, nullptr, ws, L.solve_bytes, s);
     if (rc) return rc;
     return frame_interp_run(ctx, I0, I1, dtype_in, rows, cols, batch, f[0], f[1], f[2], f[3], mf,
                             mb, times, nt, out, dtype_out, flags, trusted, s);
@@ -1237,7 +1422,8 @@ int flow_interp_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
     const size_t ob = align_up(n * nt * elem_size(dev_out)), flb = align_up(n * nt);
     if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * in_es) * 2))) return rc;
     if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, ob + flb + kAlign))) return rc;
-    const size_t wsb = hsflow_flow_interp_workspace_bytes(rows, cols, 1, levels);
+    const size_t wsb = hsflow_flow_interp_workspace_bytes(rows, cols, 1, levels) +
+                       (pf_on(&ctx->pf) ? pf_planes_bytes(rows, cols, 1) : 0);
     if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
     char *in0 = (char *)ctx->d_in, *in1 = in0 + align_up(n * in_es);
     char *dout = (char *)ctx->d_out;
@@ -1247,7 +1433,7 @@ int flow_interp_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
         return rc;
     rc = flow_interp_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, median, window,
                           iters, (float)alpha, rel, abs_thr, times, nt, dout, dev_out,
-                          flags ? dfl : nullptr, trusted ? dtr : nullptr, ctx->d_ws,
+                          flags ? dfl : nullptr, trusted ? dtr : nullptr, &ctx->pf, ctx->d_ws,
                           ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
     if (flags)
@@ -1355,14 +1541,18 @@ InterpBgrLayout interp_bgr_layout(int rows, int cols, int batch, int levels) {
 // hsflow_bgr_to_gray_device of both frames into the workspace,
 // hsflow_flow_bidir_median_device on the grey planes (the masks only when
 // flags or trusted needs them), then KIC on the BGR frames: three public
-// calls one after the other, so the bits are theirs by construction.
+// calls one after the other, so the bits are theirs by construction.  With a
+// prefilter the grey planes are prefiltered into two f32 planes behind that
+// layout and the solve runs on those.
 int flow_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
                          int cols, int batch, int levels, int warps, int median, int window,
                          int iters, float alpha, float rel, float abs_thr, const float *times,
                          int nt, void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
-                         void *ws, size_t ws_bytes, hipStream_t s) {
-    int rc = check_warped_args(ctx, warps, window, iters);
+                         const hsflow_prefilter *pf, void *ws, size_t ws_bytes, hipStream_t s) {
+    PfPlan P;
+    int rc = pf_on(pf) ? plan_prefilter(ctx, pf, &P) : HSFLOW_OK;
     if (rc) return rc;
+    if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
     if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
         return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
@@ -1373,10 +1563,11 @@ int flow_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
     if ((rc = check_interp_args(ctx, times, nt, dtype_out, false))) return rc;
     const InterpBgrLayout L = interp_bgr_layout(rows, cols, batch, levels);
-    if (ws_bytes < L.bytes)
-        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, L.bytes);
+    const size_t need = L.bytes + (pf_on(pf) ? pf_planes_bytes(rows, cols, batch) : 0);
+    if (ws_bytes < need)
+        return fail(ctx, HSFLOW_ERR_ARG, "workspace %zu < %zu bytes", ws_bytes, need);
     const size_t n = (size_t)rows * cols * batch;
-    const ByteRange in[3] = {{bgr0, n * 3}, {bgr1, n * 3}, {ws, L.bytes}};
+    const ByteRange in[3] = {{bgr0, n * 3}, {bgr1, n * 3}, {ws, need}};
     const ByteRange outs[3] = {{out, n * nt * 3 * elem_size(dtype_out)},
                                {flags, n * nt},
                                {trusted, (size_t)batch * nt * 4}};
@@ -1385,7 +1576,7 @@ int flow_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
                     "interpolation outputs overlap the frames, the workspace or each other");
     // the frames must not overlap the workspace either: the grey planes are
     // written while the BGR frames are still to be read
-    if (bytes_overlap(bgr0, n * 3, ws, L.bytes) || bytes_overlap(bgr1, n * 3, ws, L.bytes))
+    if (bytes_overlap(bgr0, n * 3, ws, need) || bytes_overlap(bgr1, n * 3, ws, need))
         return fail(ctx, HSFLOW_ERR_ARG, "the frames overlap the workspace");
     char *base = (char *)ws;
     uint8_t *g0 = (uint8_t *)(base + L.gray[0]), *g1 = (uint8_t *)(base + L.gray[1]);
@@ -1397,7 +1588,16 @@ int flow_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
     hipError_t e = hsflow::launch_bgr2gray(bgr0, rows, cols, batch, g0, s);
     if (e == hipSuccess) e = hsflow::launch_bgr2gray(bgr1, rows, cols, batch, g1, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "bgr2gray launch");
-    rc = bidir_impl(ctx, g0, g1, HSFLOW_U8, rows, cols, batch, levels, warps, median, window,
+    const void *S0 = g0, *S1 = g1;
+    int dtype_solve = HSFLOW_U8;
+    if (pf_on(pf)) {
+        float *p0, *p1;
+        rc = prefilter_pair(ctx, g0, g1, HSFLOW_U8, rows, cols, batch, P, ws, L.bytes, &p0, &p1,
+                            s);
+        if (rc) return rc;
+        S0 = p0, S1 = p1, dtype_solve = HSFLOW_F32;
+    }
+    rc = bidir_impl(ctx, S0, S1, dtype_solve, rows, cols, batch, levels, warps, median, window,
                     iters, alpha, rel, abs_thr, f[0], f[1], f[2], f[3], nullptr, mf, nullptr,
                     nullptr, mb, nullptr, ws, L.grey.solve_bytes, s);
     if (rc) return rc;
@@ -1445,7 +1645,8 @@ int flow_interp_bgr_host(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
     const size_t ob = align_up(n * nt * 3 * es), flb = align_up(n * nt);
     if ((rc = grow(ctx, &ctx->d_in, &ctx->d_in_bytes, align_up(n * 3) * 2))) return rc;
     if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_bytes, ob + flb + kAlign))) return rc;
-    const size_t wsb = interp_bgr_layout(rows, cols, 1, levels).bytes;
+    const size_t wsb = interp_bgr_layout(rows, cols, 1, levels).bytes +
+                       (pf_on(&ctx->pf) ? pf_planes_bytes(rows, cols, 1) : 0);
     if ((rc = grow(ctx, &ctx->d_ws, &ctx->d_ws_bytes, wsb))) return rc;
     uint8_t *in0 = (uint8_t *)ctx->d_in, *in1 = in0 + align_up(n * 3);
     char *dout = (char *)ctx->d_out;
@@ -1455,7 +1656,7 @@ int flow_interp_bgr_host(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
         return rc;
     rc = flow_interp_bgr_impl(ctx, in0, in1, rows, cols, 1, levels, warps, median, window, iters,
                               (float)alpha, rel, abs_thr, times, nt, dout, dtype_out,
-                              flags ? dfl : nullptr, trusted ? dtr : nullptr, ctx->d_ws,
+                              flags ? dfl : nullptr, trusted ? dtr : nullptr, &ctx->pf, ctx->d_ws,
                               ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
     if (flags)
@@ -1883,6 +2084,17 @@ int hsflow_flow_warped_median_device(const void *I0, const void *I1, int dtype_i
                        (hipStream_t)stream);
 }
 
+int hsflow_flow_warped_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float *u, float *v,
+                                 const hsflow_prefilter *pf, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return warped_pf_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                          window, iters, alpha, u, v, pf, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
 int hsflow_flow_warped_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                               int batch, int levels, int warps, int window, int iters,
                               float alpha, float *u, float *v, void *workspace,
@@ -1945,6 +2157,20 @@ int hsflow_flow_bidir_median_device(const void *I0, const void *I1, int dtype_in
     return bidir_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
                       iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f, err_b,
                       mask_b, counts_b, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_bidir_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                int batch, int levels, int warps, int median, int window,
+                                int iters, float alpha, float rel, float abs_thr, float *uf,
+                                float *vf, float *ub, float *vb, float *err_f, uint8_t *mask_f,
+                                uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                uint32_t *counts_b, const hsflow_prefilter *pf, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return bidir_pf_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                         window, iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f,
+                         counts_f, err_b, mask_b, counts_b, pf, workspace, workspace_bytes,
+                         (hipStream_t)stream);
 }
 
 int hsflow_flow_bidir_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
@@ -2011,10 +2237,22 @@ int hsflow_flow_interp_device(const void *I0, const void *I1, int dtype_in, int 
                               const float *times, int nt, void *out, int dtype_out,
                               uint8_t *flags, uint32_t *trusted, void *workspace,
                               size_t workspace_bytes, void *stream) {
+    return hsflow_flow_interp_pf_device(I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                                        window, iters, alpha, rel, abs_thr, times, nt, out,
+                                        dtype_out, flags, trusted, nullptr, workspace,
+                                        workspace_bytes, stream);
+}
+
+int hsflow_flow_interp_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, void *out, int dtype_out,
+                                 uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     return flow_interp_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
                             window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out, flags,
-                            trusted, workspace, workspace_bytes, (hipStream_t)stream);
+                            trusted, pf, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int hsflow_flow_interp(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
@@ -2058,10 +2296,23 @@ int hsflow_flow_interp_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int 
                                   const float *times, int nt, void *out, int dtype_out,
                                   uint8_t *flags, uint32_t *trusted, void *workspace,
                                   size_t workspace_bytes, void *stream) {
+    return hsflow_flow_interp_bgr_pf_device(bgr0, bgr1, rows, cols, batch, levels, warps, median,
+                                            window, iters, alpha, rel, abs_thr, times, nt, out,
+                                            dtype_out, flags, trusted, nullptr, workspace,
+                                            workspace_bytes, stream);
+}
+
+int hsflow_flow_interp_bgr_pf_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int warps, int median, int window,
+                                     int iters, float alpha, float rel, float abs_thr,
+                                     const float *times, int nt, void *out, int dtype_out,
+                                     uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                     void *workspace, size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     return flow_interp_bgr_impl(nullptr, bgr0, bgr1, rows, cols, batch, levels, warps, median,
                                 window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out,
-                                flags, trusted, workspace, workspace_bytes, (hipStream_t)stream);
+                                flags, trusted, pf, workspace, workspace_bytes,
+                                (hipStream_t)stream);
 }
 
 int hsflow_flow_interp_bgr(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bgr1, int rows,
@@ -2076,6 +2327,36 @@ int hsflow_flow_interp_bgr(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *
 }
 
 int hsflow_set_interp_bgr_loads(int wide) { return hsflow::set_interp_bgr_wide_loads(wide); }
+
+int hsflow_prefilter_device(const void *I, int dtype_in, int rows, int cols, int batch,
+                            const hsflow_prefilter *pf, float *out, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return prefilter_impl(nullptr, I, dtype_in, rows, cols, batch, pf, out, (hipStream_t)stream);
+}
+
+size_t hsflow_prefilter_planes_bytes(int rows, int cols, int batch) {
+    if (!sizes_ok(rows, cols, batch)) return 0;
+    return pf_planes_bytes(rows, cols, batch);
+}
+
+int hsflow_ctx_set_prefilter(hsflow_ctx *ctx, const hsflow_prefilter *pf) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    if (pf_on(pf)) {
+        PfPlan P;
+        int rc = plan_prefilter(ctx, pf, &P);
+        if (rc) return rc;
+        ctx->pf = *pf;
+    } else {
+        ctx->pf = hsflow_prefilter{0, 0.0f, 0.0f, 0.0f};
+    }
+    return HSFLOW_OK;
+}
+
+int hsflow_ctx_prefilter(const hsflow_ctx *ctx, hsflow_prefilter *pf) {
+    if (!ctx || !pf) return fail(nullptr, HSFLOW_ERR_ARG, "null %s", ctx ? "prefilter" : "context");
+    *pf = ctx->pf;
+    return HSFLOW_OK;
+}
 
 int hsflow_bgr_to_gray_device(const uint8_t *bgr, int rows, int cols, int batch,
                               uint8_t *gray, void *stream) {

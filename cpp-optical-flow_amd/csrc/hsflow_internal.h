@@ -108,6 +108,14 @@ hipError_t launch_frame_interp_bgr(const uint8_t *I0, const uint8_t *I1, int row
 // default) or as one unaligned dword and halfword; same bits.  Returns the
 // previous setting.
 int set_interp_bgr_wide_loads(int on);
+// KN (hsflow_prefilter.hip): v = I - G*I (mode 1) or scale v / (sqrt(G*(v v)) +
+// eps) (mode 2), G the separable Gaussian of `radius` (1..kPrefilterMaxRadius)
+// with weights[0..radius] (read on the host at launch), reflect-101 folded;
+// dense batch planes of dtype_in -> f32
+constexpr int kPrefilterMaxRadius = 15;
+hipError_t launch_prefilter(const void *I, int dtype_in, int rows, int cols, int batch, int mode,
+                            int radius, const float *weights, float eps, float scale, float *out,
+                            hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

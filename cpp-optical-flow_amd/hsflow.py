@@ -17,6 +17,7 @@ If the library is missing or no gfx950 device is present, calls raise.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -85,7 +86,45 @@ EXPORTS = (
     "hsflow_warp_image_bgr_device", "hsflow_frame_interp_bgr_device",
     "hsflow_flow_interp_bgr_workspace_bytes", "hsflow_flow_interp_bgr_device",
     "hsflow_flow_interp_bgr", "hsflow_set_interp_bgr_loads",
+    "hsflow_prefilter_device", "hsflow_prefilter_planes_bytes",
+    "hsflow_flow_warped_pf_device", "hsflow_flow_bidir_pf_device",
+    "hsflow_flow_interp_pf_device", "hsflow_flow_interp_bgr_pf_device",
+    "hsflow_ctx_set_prefilter", "hsflow_ctx_prefilter",
 )
+
+# modes of the brightness-robust prefilter (HSFLOW_PREFILTER_*)
+PREFILTER_NONE, PREFILTER_HIGHPASS, PREFILTER_NORMALIZE = 0, 1, 2
+PREFILTER_MAX_RADIUS = 15
+
+
+class _CPrefilter(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("sigma", ctypes.c_float), ("eps", ctypes.c_float),
+                ("scale", ctypes.c_float)]
+
+
+class Prefilter(collections.namedtuple("Prefilter", "mode sigma eps scale")):
+    """hsflow_prefilter: what the warped, bidirectional and interpolating
+    solves run on the frames first.  v = I - G*I with G a Gaussian of `sigma`;
+    mode PREFILTER_HIGHPASS gives v, PREFILTER_NORMALIZE gives
+    scale * v / (sqrt(G*(v v)) + eps) (include/hsflow.h).  It lowers the
+    contrast the solver sees: use alpha ~ 100 with median=5."""
+    __slots__ = ()
+
+    def __new__(cls, mode, sigma=4.0, eps=4.0, scale=32.0):
+        return super().__new__(cls, int(mode), float(sigma), float(eps), float(scale))
+
+    def _c(self):
+        return _CPrefilter(self.mode, self.sigma, self.eps, self.scale)
+
+
+def _pf_arg(prefilter):
+    """(keep-alive struct, pointer or None) of a Prefilter / None."""
+    if prefilter is None:
+        return None, None
+    if not isinstance(prefilter, Prefilter):
+        prefilter = Prefilter(*prefilter)
+    c = prefilter._c()
+    return c, ctypes.byref(c)
 
 
 BidirHost = collections.namedtuple("BidirHost", "u v ub vb mask_f mask_b counts")
@@ -218,6 +257,21 @@ def lib():
                                          ctypes.c_double, f, f, fp, i, ctypes.POINTER(_vp), i,
                                          _sz, ctypes.POINTER(_vp), _sz, _vp]
     L.hsflow_set_interp_bgr_loads.argtypes = [i]
+    pfp = ctypes.POINTER(_CPrefilter)
+    L.hsflow_prefilter_device.argtypes = [_vp, i, i, i, i, pfp, _vp, _vp]
+    L.hsflow_prefilter_planes_bytes.argtypes = [i, i, i]
+    L.hsflow_prefilter_planes_bytes.restype = _sz
+    L.hsflow_flow_warped_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f,
+                                               _vp, _vp, pfp, _vp, _sz, _vp]
+    L.hsflow_flow_bidir_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, pfp, _vp, _sz, _vp]
+    L.hsflow_flow_interp_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f, fp,
+                                               i, _vp, i, _vp, _vp, pfp, _vp, _sz, _vp]
+    L.hsflow_flow_interp_bgr_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f, fp,
+                                                   i, _vp, i, _vp, _vp, pfp, _vp, _sz, _vp]
+    L.hsflow_ctx_set_prefilter.argtypes = [_vp, pfp]
+    L.hsflow_ctx_prefilter.argtypes = [_vp, pfp]
     L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               _vp, _sz, _vp]
@@ -317,6 +371,34 @@ class Context:
         self.close()
         return False
 
+    def set_prefilter(self, prefilter=None):
+        """The context's prefilter (hsflow_ctx_set_prefilter): flow_warped,
+        flow_bidir, interpolate and interpolate_bgr run it on the frames first.
+        None or mode 0 = off (default).  flow, flow_bgr, flow_pyramid and
+        gradients are the reference's semantics and ignore it."""
+        _, p = _pf_arg(prefilter)
+        _check(lib().hsflow_ctx_set_prefilter(self._p, p), self._p)
+
+    def prefilter(self):
+        """The context's current Prefilter, None when off."""
+        c = _CPrefilter()
+        _check(lib().hsflow_ctx_prefilter(self._p, ctypes.byref(c)))
+        return Prefilter(c.mode, c.sigma, c.eps, c.scale) if c.mode else None
+
+    @contextlib.contextmanager
+    def _prefilter_as(self, prefilter):
+        """`prefilter` (a Prefilter) on the context for one call, the setting
+        before it restored afterwards; None leaves the context's own."""
+        if prefilter is None:
+            yield
+            return
+        was = self.prefilter()
+        self.set_prefilter(prefilter)
+        try:
+            yield
+        finally:
+            self.set_prefilter(was)
+
     def flow(self, I0, I1, window: int, iters: int, alpha: float, out_dtype=np.float64,
              out=None):
         """getFlow on host arrays.  `out` = (u, v): C-contiguous rows x cols
@@ -362,13 +444,14 @@ class Context:
         return u, v
 
     def flow_warped(self, I0, I1, levels: int, warps: int, window: int, iters: int,
-                    alpha: float, out_dtype=np.float64, median: int = 0):
+                    alpha: float, out_dtype=np.float64, median: int = 0, prefilter=None):
         """Warped coarse-to-fine solve for large displacements (`warps`
         re-linearisations per level, `iters` iterations each), see
         hsflow_flow_warped in include/hsflow.h.  (u, v) * SOBEL_GAIN is the
         motion in pixels.  median = 3 or 5 filters (u, v) with a median of
         that size after every warp's iterations (hsflow_flow_warped_median);
-        0 = none."""
+        0 = none.  prefilter: a Prefilter set on the context for this call
+        (None: the context's own setting, off by default)."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -377,17 +460,19 @@ class Context:
         u = np.empty((rows, cols), out_dtype)
         v = np.empty((rows, cols), out_dtype)
         code = F64 if u.dtype == np.float64 else F32
-        rc = lib().hsflow_flow_warped_median(
-            self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
-            b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
-            float(alpha), u.ctypes.data, v.ctypes.data, code, u.strides[0])
+        with self._prefilter_as(prefilter):
+            rc = lib().hsflow_flow_warped_median(
+                self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
+                b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
+                float(alpha), u.ctypes.data, v.ctypes.data, code, u.strides[0])
         _check(rc, self._p)
         return u, v
 
     def flow_bidir(self, I0, I1, levels: int, warps: int, window: int, iters: int,
                    alpha: float, rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                    out_dtype=np.float64, backward: bool = True, masks: bool = True,
-                   counts: bool = True, out=None, mask_out=None, median: int = 0):
+                   counts: bool = True, out=None, mask_out=None, median: int = 0,
+                   prefilter=None):
         """Warped solve in both directions with the forward-backward check
         (hsflow_flow_bidir in include/hsflow.h).  Returns a BidirHost: u, v
         (I0 -> I1), ub, vb (I1 -> I0, None unless `backward`), mask_f, mask_b
@@ -396,7 +481,7 @@ class Context:
         `counts`).  `out`: an array [4, rows, >= cols] of out_dtype whose
         planes' first `cols` columns receive u, v, ub, vb (a padded row step);
         `mask_out`: likewise uint8 [2, rows, >= cols] for the masks.  median
-        as in flow_warped, for both directions."""
+        and prefilter as in flow_warped, for both directions."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -418,15 +503,16 @@ class Context:
         mf, mb = mask_out[0, :, :cols], mask_out[1, :, :cols]
         cnt = np.zeros((2, 3), np.uint32) if counts else None
         code = F64 if out.dtype == np.float64 else F32
-        rc = lib().hsflow_flow_bidir_median(
-            self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
-            b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
-            float(alpha),
-            float(rel), float(abs), u.ctypes.data, v.ctypes.data,
-            ub.ctypes.data if backward else None, vb.ctypes.data if backward else None, code,
-            out.strides[1], mf.ctypes.data if masks else None,
-            mb.ctypes.data if masks else None, mask_out.strides[1],
-            cnt.ctypes.data if counts else None)
+        with self._prefilter_as(prefilter):
+            rc = lib().hsflow_flow_bidir_median(
+                self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
+                b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
+                float(alpha),
+                float(rel), float(abs), u.ctypes.data, v.ctypes.data,
+                ub.ctypes.data if backward else None, vb.ctypes.data if backward else None, code,
+                out.strides[1], mf.ctypes.data if masks else None,
+                mb.ctypes.data if masks else None, mask_out.strides[1],
+                cnt.ctypes.data if counts else None)
         _check(rc, self._p)
         return BidirHost(u, v, ub if backward else None, vb if backward else None,
                          mf if masks else None, mb if masks else None, cnt)
@@ -434,14 +520,16 @@ class Context:
     def interpolate(self, I0, I1, times, levels: int, warps: int, window: int, iters: int,
                     alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                     abs: float = CONSISTENCY_ABS, out_dtype=np.float32,
-                    with_flags: bool = False):
+                    with_flags: bool = False, prefilter=None):
         """The frames at `times` (each in [0, 1]; at most MAX_TIMES) between I0
         and I1: the bidirectional warped solve, then the motion-compensated
         blend (hsflow_flow_interp in include/hsflow.h).  Returns an array
         [len(times), rows, cols] of out_dtype (uint8, float32 or float64), or
         with_flags: (frames, flags, trusted) -- flags uint8 like frames (FLAG_*
         bits; 0 = both sources pass the forward-backward check), trusted uint32
-        [len(times)], the pixels per frame with flags == 0."""
+        [len(times)], the pixels per frame with flags == 0.  prefilter as in
+        flow_warped: the flows come from the prefiltered frames, the frames
+        themselves are sampled."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -456,25 +544,27 @@ class Context:
         trusted = np.zeros(nt, np.uint32) if with_flags else None
         planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
         fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
-        rc = lib().hsflow_flow_interp(
-            self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
-            b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
-            float(alpha), float(rel), float(abs), tm, nt, planes, _dtype_code(out),
-            out.strides[1], fplanes, cols, trusted.ctypes.data if with_flags else None)
+        with self._prefilter_as(prefilter):
+            rc = lib().hsflow_flow_interp(
+                self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
+                b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
+                float(alpha), float(rel), float(abs), tm, nt, planes, _dtype_code(out),
+                out.strides[1], fplanes, cols, trusted.ctypes.data if with_flags else None)
         _check(rc, self._p)
         return (out, flags, trusted) if with_flags else out
 
     def interpolate_bgr(self, bgr0, bgr1, times, levels: int, warps: int, window: int,
                         iters: int, alpha: float, median: int = 0,
                         rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
-                        out_dtype=np.uint8, with_flags: bool = False):
+                        out_dtype=np.uint8, with_flags: bool = False, prefilter=None):
         """The colour frames at `times` between two decoded 8-bit BGR frames
         (H x W x 3, strided rows accepted): uploaded as BGR, converted to grey
         and solved both ways on the GPU, then the motion-compensated blend of
         each channel (hsflow_flow_interp_bgr in include/hsflow.h).  Returns an
         array [len(times), rows, cols, 3] of out_dtype (uint8 or float32), or
         with_flags: (frames, flags, trusted) -- flags uint8 [len(times), rows,
-        cols] and trusted uint32 [len(times)] as in interpolate."""
+        cols] and trusted uint32 [len(times)] as in interpolate.  prefilter as
+        in flow_warped, run on the grey planes."""
         a = np.asarray(bgr0)
         b = np.asarray(bgr1)
         for x in (a, b):
@@ -497,11 +587,13 @@ class Context:
         trusted = np.zeros(nt, np.uint32) if with_flags else None
         planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
         fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
-        rc = lib().hsflow_flow_interp_bgr(
-            self._p, a.ctypes.data, b.ctypes.data, rows, cols, a.strides[0], b.strides[0],
-            int(levels), int(warps), int(median), int(window), int(iters), float(alpha),
-            float(rel), float(abs), tm, nt, planes, _dtype_code(out), out.strides[1] if nt else 0,
-            fplanes, cols, trusted.ctypes.data if with_flags else None)
+        with self._prefilter_as(prefilter):
+            rc = lib().hsflow_flow_interp_bgr(
+                self._p, a.ctypes.data, b.ctypes.data, rows, cols, a.strides[0], b.strides[0],
+                int(levels), int(warps), int(median), int(window), int(iters), float(alpha),
+                float(rel), float(abs), tm, nt, planes, _dtype_code(out),
+                out.strides[1] if nt else 0, fplanes, cols,
+                trusted.ctypes.data if with_flags else None)
         _check(rc, self._p)
         return (out, flags, trusted) if with_flags else out
 
@@ -649,21 +741,24 @@ class hornSchunck:  # noqa: N801  (reference class name, hornSchunck.cpp:8)
 
 
 def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int = 1,
-            warps: int = 0, median: int = 0):
+            warps: int = 0, median: int = 0, prefilter=None):
     """compute(I0, I1, alpha, nIter) -> (u, v): the north-star convenience
     wrapper over hornSchunck(windowSize, nIter, alpha).getFlow; levels > 1
     runs the config-5 coarse-to-fine warm start (nIter per level).  warps >= 1
     runs the warped coarse-to-fine solve instead (large displacements:
     `warps` re-linearisations per level, nIter iterations each); warps = 0
     keeps the behaviour above.  median = 3 or 5 (MEDIAN_SIZES) filters the
-    flow after every warp's iterations and needs warps >= 1."""
+    flow after every warp's iterations and needs warps >= 1; so does
+    prefilter (a Prefilter: the frames are locally normalised first)."""
     if median and not warps:
         raise HsflowError(HSFLOW_ERR_ARG, f"median {median} needs the warped solve (warps >= 1)")
+    if prefilter is not None and not warps:
+        raise HsflowError(HSFLOW_ERR_ARG, "prefilter needs the warped solve (warps >= 1)")
     if warps:
         if not 1 <= int(warps) <= MAX_WARPS:
             raise HsflowError(HSFLOW_ERR_ARG, f"warps {warps} outside [1, {MAX_WARPS}]")
         return default_context().flow_warped(I0, I1, levels, warps, windowSize, nIter, alpha,
-                                             median=median)
+                                             median=median, prefilter=prefilter)
     if levels > 1:
         return default_context().flow_pyramid(I0, I1, levels, windowSize, nIter, alpha)
     return hornSchunck(windowSize, nIter, alpha).getFlow(I0, I1)
@@ -816,14 +911,16 @@ def flow_pyramid_device(I0, I1, levels: int, window: int, iters: int, alpha: flo
 
 def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
                        alpha: float, u=None, v=None, workspace=None, stream=None,
-                       median: int = 0):
+                       median: int = 0, prefilter=None):
     """Warped coarse-to-fine solve on torch CUDA tensors [B, H, W] (uint8 /
     float16 / float32 / float64): per level `warps` times the gradients
     linearised around the current flow and `iters` Jacobi iterations.
     `workspace`: pyramid_workspace_bytes(rows, cols, batch, levels) bytes.
     (u, v) * SOBEL_GAIN is the motion in pixels.  median = 3 or 5: a median
     of that size over (u, v) after every warp's iterations
-    (hsflow_flow_warped_median_device); 0 = none.  Stream-ordered."""
+    (hsflow_flow_warped_median_device); 0 = none.  prefilter: a Prefilter run
+    on both frames first (hsflow_flow_warped_pf_device); the workspace then
+    needs prefilter_planes_bytes(rows, cols, batch) more.  Stream-ordered."""
     rows, cols = I0.shape[-2:]
     batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
     _check_dense(I0, (rows, cols), "I0")
@@ -836,14 +933,16 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
         v = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
     _check_plane(u, (rows, cols), batch, "u")
     _check_plane(v, (rows, cols), batch, "v")
+    keep, pf = _pf_arg(prefilter)
     if workspace is None:
-        n = pyramid_workspace_bytes(rows, cols, batch, levels)
+        n = pyramid_workspace_bytes(rows, cols, batch, levels) + \
+            _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     with _on(I0.device):
-        rc = lib().hsflow_flow_warped_median_device(
+        rc = lib().hsflow_flow_warped_pf_device(
             I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
             int(warps), int(median), int(window), int(iters), float(alpha), u.data_ptr(),
-            v.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            v.data_ptr(), pf, workspace.data_ptr(), workspace.numel(),
             _stream_ptr(stream, I0.device))
     _check(rc)
     return u, v
@@ -921,7 +1020,7 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
                       rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                       uf=None, vf=None, ub=None, vb=None, err_f=None, mask_f=True,
                       counts_f=None, err_b=None, mask_b=None, counts_b=None, workspace=None,
-                      stream=None, median: int = 0):
+                      stream=None, median: int = 0, prefilter=None):
     """Warped solve of I0 -> I1 (uf, vf) and I1 -> I0 (ub, vb) on torch CUDA
     tensors [B, H, W], then the forward-backward check each way
     (hsflow_flow_bidir_device in include/hsflow.h).  The flows equal
@@ -929,7 +1028,9 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
     consistency_device (True / tensor / None); a direction with none runs no
     check.  Returns a BidirDevice, None for outputs not asked for.
     `workspace`: bidir_workspace_bytes(rows, cols, batch, levels) bytes.
-    median as in flow_warped_device, for both directions.  Stream-ordered."""
+    median and prefilter (hsflow_flow_bidir_pf_device; prefilter_planes_bytes
+    more workspace) as in flow_warped_device, for both directions.
+    Stream-ordered."""
     rows, cols = I0.shape[-2:]
     batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
     _check_dense(I0, (rows, cols), "I0")
@@ -951,16 +1052,18 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
             outs.append(_check_output(
                 want, I0.shape, torch.float32 if name.startswith("err") else torch.uint8,
                 I0.device, name))
+    keep, pf = _pf_arg(prefilter)
     if workspace is None:
-        n = bidir_workspace_bytes(rows, cols, batch, levels)
+        n = bidir_workspace_bytes(rows, cols, batch, levels) + \
+            _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     ptr = (lambda t: t.data_ptr() if t is not None else None)
     with _on(I0.device):
-        rc = lib().hsflow_flow_bidir_median_device(
+        rc = lib().hsflow_flow_bidir_pf_device(
             I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
             int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
             float(abs),
-            *[t.data_ptr() for t in flows], *[ptr(t) for t in outs], workspace.data_ptr(),
+            *[t.data_ptr() for t in flows], *[ptr(t) for t in outs], pf, workspace.data_ptr(),
             workspace.numel(), _stream_ptr(stream, I0.device))
     _check(rc)
     return BidirDevice(*flows, *outs)
@@ -1059,12 +1162,15 @@ def flow_interp_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -
 def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iters: int,
                        alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                        abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
-                       trusted=None, workspace=None, stream=None):
+                       trusted=None, workspace=None, stream=None, prefilter=None):
     """flow_bidir_device(median=...) into planes of the workspace, then
     frame_interp_device with both masks: one call, the same bits
     (hsflow_flow_interp_device in include/hsflow.h).  `workspace`:
-    flow_interp_workspace_bytes(rows, cols, batch, levels) bytes.  Returns
-    (out, flags, trusted) as frame_interp_device.  Stream-ordered."""
+    flow_interp_workspace_bytes(rows, cols, batch, levels) bytes.  prefilter: a
+    Prefilter; the flows then come from the prefiltered frames while the
+    frames themselves are sampled (hsflow_flow_interp_pf_device;
+    prefilter_planes_bytes more workspace).  Returns (out, flags, trusted) as
+    frame_interp_device.  Stream-ordered."""
     if out_dtype is None:
         out_dtype = torch.float32
     rows, cols = I0.shape[-2:]
@@ -1075,16 +1181,18 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
         raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
     tm = _times_array(times)
     out, flags, trusted = _interp_outputs(I0, len(tm), out, out_dtype, flags, trusted)
+    keep, pf = _pf_arg(prefilter)
     if workspace is None:
-        n = flow_interp_workspace_bytes(rows, cols, batch, levels)
+        n = flow_interp_workspace_bytes(rows, cols, batch, levels) + \
+            _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     ptr = (lambda t: t.data_ptr() if t is not None else None)
     with _on(I0.device):
-        rc = lib().hsflow_flow_interp_device(
+        rc = lib().hsflow_flow_interp_pf_device(
             I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
             int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
             float(abs), tm, len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32,
-            ptr(flags), ptr(trusted), workspace.data_ptr(), workspace.numel(),
+            ptr(flags), ptr(trusted), pf, workspace.data_ptr(), workspace.numel(),
             _stream_ptr(stream, I0.device))
     _check(rc)
     return out, flags, trusted
@@ -1180,12 +1288,14 @@ def flow_interp_bgr_workspace_bytes(rows: int, cols: int, batch: int, levels: in
 def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: int, iters: int,
                            alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                            abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
-                           trusted=None, workspace=None, stream=None):
+                           trusted=None, workspace=None, stream=None, prefilter=None):
     """bgr_to_gray_device of both frames, flow_bidir_device(median=...) on the
     grey planes, then frame_interp_bgr_device with both masks: one call, the
     same bits (hsflow_flow_interp_bgr_device in include/hsflow.h).
     `workspace`: flow_interp_bgr_workspace_bytes(rows, cols, batch, levels)
-    bytes.  Returns (out, flags, trusted) as frame_interp_bgr_device.
+    bytes.  prefilter: a Prefilter run on the grey planes in front of the
+    solve (hsflow_flow_interp_bgr_pf_device; prefilter_planes_bytes more
+    workspace).  Returns (out, flags, trusted) as frame_interp_bgr_device.
     Stream-ordered."""
     if out_dtype is None:
         out_dtype = torch.float32
@@ -1195,19 +1305,53 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
         raise HsflowError(HSFLOW_ERR_SIZE, "bgr0/bgr1 differ in shape")
     tm = _times_array(times)
     out, flags, trusted = _bgr_interp_outputs(bgr0, len(tm), out, out_dtype, flags, trusted)
+    keep, pf = _pf_arg(prefilter)
     if workspace is None:
-        n = flow_interp_bgr_workspace_bytes(rows, cols, batch, levels)
+        n = flow_interp_bgr_workspace_bytes(rows, cols, batch, levels) + \
+            _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=bgr0.device)
     ptr = (lambda t: t.data_ptr() if t is not None else None)
     with _on(bgr0.device):
-        rc = lib().hsflow_flow_interp_bgr_device(
+        rc = lib().hsflow_flow_interp_bgr_pf_device(
             bgr0.data_ptr(), bgr1.data_ptr(), rows, cols, batch, int(levels), int(warps),
             int(median), int(window), int(iters), float(alpha), float(rel), float(abs), tm,
             len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32, ptr(flags),
-            ptr(trusted), workspace.data_ptr(), workspace.numel(),
+            ptr(trusted), pf, workspace.data_ptr(), workspace.numel(),
             _stream_ptr(stream, bgr0.device))
     _check(rc)
     return out, flags, trusted
+
+
+def prefilter_planes_bytes(rows: int, cols: int, batch: int = 1) -> int:
+    """Workspace a solve with prefilter= needs on top of its own size function."""
+    return int(lib().hsflow_prefilter_planes_bytes(rows, cols, batch))
+
+
+def _pf_extra(prefilter, rows, cols, batch) -> int:
+    on = prefilter is not None and int(prefilter[0]) != PREFILTER_NONE
+    return prefilter_planes_bytes(rows, cols, batch) if on else 0
+
+
+def prefilter_device(I, prefilter, out=None, stream=None):
+    """The prefilter alone (hsflow_prefilter_device in include/hsflow.h): I a
+    torch CUDA tensor [B, H, W] or [H, W] (uint8 / float16 / float32 /
+    float64) -> float32 of the same shape: v = I - G*I (PREFILTER_HIGHPASS) or
+    scale * v / (sqrt(G*(v v)) + eps) (PREFILTER_NORMALIZE).  `out` must not
+    overlap I.  One launch, no workspace.  Stream-ordered."""
+    rows, cols = I.shape[-2:]
+    batch = int(np.prod(I.shape[:-2])) if I.dim() > 2 else 1
+    _check_dense(I, (rows, cols), "I")
+    if prefilter is None:
+        raise HsflowError(HSFLOW_ERR_ARG, "prefilter_device needs a Prefilter")
+    if out is None:
+        out = torch.empty(I.shape, dtype=torch.float32, device=I.device)
+    _check_plane(out, (rows, cols), batch, "out")
+    keep, pf = _pf_arg(prefilter)
+    with _on(I.device):
+        rc = lib().hsflow_prefilter_device(I.data_ptr(), _tensor_dtype(I), rows, cols, batch, pf,
+                                           out.data_ptr(), _stream_ptr(stream, I.device))
+    _check(rc)
+    return out
 
 
 def set_interp_bgr_loads(wide: bool) -> bool:

@@ -605,6 +605,103 @@ int hsflow_flow_interp_bgr(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *
  * the timings).  Process-wide; returns the previous setting. */
 int hsflow_set_interp_bgr_loads(int wide);
 
+/* ---- brightness-robust prefilter (local contrast normalisation) -----------
+ * Every solve rests on brightness constancy, I1(x + d) = I0(x); an exposure or
+ * gain step, a fade or flicker breaks it, and the solver turns the change
+ * into motion (a ten-grey-level offset costs two orders of magnitude of
+ * accuracy).  The remedy is to solve on the locally normalised
+ * texture of the frames.  Per plane, in exact arithmetic:
+ *   G   = separable Gaussian of radius r = ceil(3 sigma), weights
+ *         w[i] = exp(-i^2 / (2 sigma^2)), |i| <= r, normalised to sum 1 in
+ *         double on the host and rounded to f32 once; border reflect-101
+ *         folded with period 2 (n - 1) (n = 1: index 0), so any r works on
+ *         any size
+ *   v   = I - G*I
+ *   mode HSFLOW_PREFILTER_HIGHPASS:   out = v           (removes an offset)
+ *   mode HSFLOW_PREFILTER_NORMALIZE:  out = scale v / (sqrt(G*(v v)) + eps)
+ *                                     (removes an offset and, up to the eps
+ *                                     term, a gain)
+ * G*(v v), not G*(I I) - (G*I)^2: it has no cancellation in f32.  sigma lies in
+ * [0.5, 5] (r <= HSFLOW_PREFILTER_MAX_RADIUS); eps and scale are finite and
+ * > 0; anything else is HSFLOW_ERR_ARG before any device work.  U8, F16 and F32
+ * frames are computed in f32, F64 frames accumulated in f64 and rounded once.
+ * The filter lowers the contrast of what the solver sees, so alpha has to go
+ * down with it: recommended is alpha ~ 100 with the 5x5 median, sigma 4,
+ * eps 1..4, scale 32; at alpha 400 without the median it does not help, and
+ * at sigma 2 it hurts.
+ * hsflow_flow, hsflow_flow_bgr, hsflow_flow_pyramid, hsflow_flow_multi and
+ * hsflow_gradients are the reference's semantics and never prefilter,
+ * whatever the context's setting. */
+#define HSFLOW_HAS_PREFILTER 1
+#define HSFLOW_PREFILTER_NONE 0
+#define HSFLOW_PREFILTER_HIGHPASS 1
+#define HSFLOW_PREFILTER_NORMALIZE 2
+#define HSFLOW_PREFILTER_MAX_RADIUS 15
+
+typedef struct hsflow_prefilter {
+    int mode; /* 0 = none */
+    float sigma, eps, scale;
+} hsflow_prefilter;
+
+/* The filter alone: I dense [batch][rows][cols] of dtype_in (U8, F16, F32,
+ * F64) -> out, f32 of the same shape; one launch, no workspace.  out must not
+ * overlap I (HSFLOW_ERR_ARG); pf->mode == 0 is an error for this call.
+ * Stream-ordered, never allocates or synchronises, capturable (the weights
+ * travel in the kernel arguments); all arguments are checked before any
+ * device work. */
+int hsflow_prefilter_device(const void *I, int dtype_in, int rows, int cols, int batch,
+                            const hsflow_prefilter *pf, float *out, void *stream);
+/* Bytes of the two f32 planes per pair a *_pf solve prefilters the frames
+ * into (each 256-byte aligned); 0 for a bad size. */
+size_t hsflow_prefilter_planes_bytes(int rows, int cols, int batch);
+
+/* The *_median device solves and the two fused interpolations with `const
+ * hsflow_prefilter *pf` in front of `workspace`.  They prefilter I0 and I1 into
+ * two f32 planes that lie behind the workspace of the call they extend, so
+ * `workspace` must hold that call's own size function
+ * (hsflow_pyramid_workspace_bytes, hsflow_flow_bidir_workspace_bytes,
+ * hsflow_flow_interp_workspace_bytes, hsflow_flow_interp_bgr_workspace_bytes)
+ * plus hsflow_prefilter_planes_bytes, and must not overlap the frames; then
+ * they run that call on the planes as HSFLOW_F32 frames (not integer-valued,
+ * so the pyramid does not round them).  The two interpolations solve on the
+ * prefiltered planes and sample the original frames; the BGR one prefilters
+ * the grey u8 planes it makes anyway.  The result is bit for bit what the
+ * public pieces give one after the other.  pf == NULL or pf->mode == 0 runs
+ * the launches of the call without it and returns its bits. */
+int hsflow_flow_warped_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float *u, float *v,
+                                 const hsflow_prefilter *pf, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int hsflow_flow_bidir_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                int batch, int levels, int warps, int median, int window,
+                                int iters, float alpha, float rel, float abs_thr, float *uf,
+                                float *vf, float *ub, float *vb, float *err_f, uint8_t *mask_f,
+                                uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                uint32_t *counts_b, const hsflow_prefilter *pf, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, void *out, int dtype_out,
+                                 uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_bgr_pf_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int warps, int median, int window,
+                                     int iters, float alpha, float rel, float abs_thr,
+                                     const float *times, int nt, void *out, int dtype_out,
+                                     uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* The context's prefilter: the host-buffer, blocking calls hsflow_flow_warped*,
+ * hsflow_flow_bidir*, hsflow_flow_interp and hsflow_flow_interp_bgr honour it
+ * and then equal their *_pf_device form bit for bit (there are no host _pf
+ * variants).  NULL or mode 0: off, the default, which leaves every call as it
+ * was.  A bad setting is HSFLOW_ERR_ARG and leaves the old one in place.
+ * hsflow_ctx_prefilter reads the setting back. */
+int hsflow_ctx_set_prefilter(hsflow_ctx *ctx, const hsflow_prefilter *pf);
+int hsflow_ctx_prefilter(const hsflow_ctx *ctx, hsflow_prefilter *pf);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

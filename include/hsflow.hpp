@@ -76,9 +76,38 @@ class Context {
     void check(int rc) const {
         if (rc != HSFLOW_OK) throw Error(rc, hsflow_last_error(ctx_));
     }
+    // The brightness-robust prefilter (hsflow.h, hsflow_ctx_set_prefilter) the
+    // warped, bidirectional and interpolating solves run on the frames first;
+    // nullptr or mode 0 = off (default).  getFlow and getGradients ignore it.
+    void setPrefilter(const hsflow_prefilter *pf) { check(hsflow_ctx_set_prefilter(ctx_, pf)); }
+    hsflow_prefilter prefilter() const {
+        hsflow_prefilter pf{};
+        check(hsflow_ctx_prefilter(ctx_, &pf));
+        return pf;
+    }
 
   private:
     hsflow_ctx *ctx_ = nullptr;
+};
+
+// `pf` on a context for one call (nullptr: the context's own setting stays)
+class PrefilterScope {
+  public:
+    PrefilterScope(Context &c, const hsflow_prefilter *pf) : c_(c), on_(pf != nullptr) {
+        if (!on_) return;
+        was_ = c_.prefilter();
+        c_.setPrefilter(pf);
+    }
+    ~PrefilterScope() {
+        if (on_) hsflow_ctx_set_prefilter(c_.get(), &was_);
+    }
+    PrefilterScope(const PrefilterScope &) = delete;
+    PrefilterScope &operator=(const PrefilterScope &) = delete;
+
+  private:
+    Context &c_;
+    bool on_;
+    hsflow_prefilter was_{};
 };
 
 class HornSchunck {
@@ -123,10 +152,14 @@ class HornSchunck {
     // iterations each.  u, v as getFlow; 8 (u, v) is the motion in pixels.
     // median = 3 or 5: a median x median filter of (u, v) after every warp's
     // iterations (hsflow_flow_warped_median), which makes alpha ~ 100 usable
-    // and keeps a moving object's edges; 0 = none.
+    // and keeps a moving object's edges; 0 = none.  prefilter: the solve runs
+    // on the locally normalised frames (hsflow.h, hsflow_prefilter; exposure
+    // steps, fades, flicker), set on the context for this call; nullptr
+    // leaves the context's own setting (setPrefilter; off by default).
+    void setPrefilter(const hsflow_prefilter *pf) { ctx().setPrefilter(pf); }
     void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                        int warps, std::vector<double> &u, std::vector<double> &v,
-                       int median = 0) {
+                       int median = 0, const hsflow_prefilter *prefilter = nullptr) {
         check_pair(imagePrev, imageNext);
         const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
         u.resize(n);
@@ -135,6 +168,7 @@ class HornSchunck {
         const ImageView a = common_type(imagePrev, imageNext, ha);
         const ImageView b = common_type(imageNext, imagePrev, hb);
         Context &c = ctx();
+        PrefilterScope scope(c, prefilter);
         c.check(hsflow_flow_warped_median(c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step,
                                           b.step, levels, warps, median, windowSize,
                                           maxIterations, alpha, u.data(), v.data(), HSFLOW_F64,
@@ -145,10 +179,11 @@ class HornSchunck {
     // hsflow_flow_bidir): the solve also runs next -> prev, and `mask` gets
     // the forward check per pixel -- HSFLOW_CONSISTENT, HSFLOW_INCONSISTENT or
     // HSFLOW_OUT_OF_FRAME -- at the default thresholds.  median as in
-    // getFlowWarped, for both directions.
+    // and prefilter as in getFlowWarped, for both directions.
     void getFlowBidir(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                       int warps, std::vector<double> &u, std::vector<double> &v,
-                      std::vector<uint8_t> &mask, int median = 0) {
+                      std::vector<uint8_t> &mask, int median = 0,
+                      const hsflow_prefilter *prefilter = nullptr) {
         check_pair(imagePrev, imageNext);
         const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
         u.resize(n);
@@ -158,6 +193,7 @@ class HornSchunck {
         const ImageView a = common_type(imagePrev, imageNext, ha);
         const ImageView b = common_type(imageNext, imagePrev, hb);
         Context &c = ctx();
+        PrefilterScope scope(c, prefilter);
         c.check(hsflow_flow_bidir_median(
             c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step, b.step, levels, warps, median,
             windowSize, maxIterations, alpha, HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS,
@@ -170,11 +206,14 @@ class HornSchunck {
     // motion-compensated blend (hsflow.h, hsflow_flow_interp).  planes[k]: the
     // frame at times[k] as rows*cols float32 grey levels; flags[k]: per pixel
     // the HSFLOW_INTERP_* bits, 0 where both source pixels pass the
-    // forward-backward check at the default thresholds.
+    // forward-backward check at the default thresholds.  prefilter as in
+    // getFlowWarped: the flows come from the prefiltered frames, the frames
+    // themselves are sampled.
     void getFrameInterp(const ImageView &imagePrev, const ImageView &imageNext,
                         const std::vector<float> &times, int levels, int warps, int median,
                         std::vector<std::vector<float>> &planes,
-                        std::vector<std::vector<uint8_t>> *flags = nullptr) {
+                        std::vector<std::vector<uint8_t>> *flags = nullptr,
+                        const hsflow_prefilter *prefilter = nullptr) {
         check_pair(imagePrev, imageNext);
         const size_t n = (size_t)imagePrev.rows * imagePrev.cols;
         planes.resize(times.size());
@@ -190,6 +229,7 @@ class HornSchunck {
         const ImageView a = common_type(imagePrev, imageNext, ha);
         const ImageView b = common_type(imageNext, imagePrev, hb);
         Context &c = ctx();
+        PrefilterScope scope(c, prefilter);
         c.check(hsflow_flow_interp(
             c.get(), a.data, b.data, a.type, a.rows, a.cols, a.step, b.step, levels, warps, median,
             windowSize, maxIterations, alpha, HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS,
@@ -199,19 +239,23 @@ class HornSchunck {
     void getFrameInterp(const ImageView &imagePrev, const ImageView &imageNext,
                         const std::vector<float> &times, int levels, int warps, int median,
                         std::vector<std::vector<float>> &planes,
-                        std::vector<std::vector<uint8_t>> &flags) {
-        getFrameInterp(imagePrev, imageNext, times, levels, warps, median, planes, &flags);
+                        std::vector<std::vector<uint8_t>> &flags,
+                        const hsflow_prefilter *prefilter = nullptr) {
+        getFrameInterp(imagePrev, imageNext, times, levels, warps, median, planes, &flags,
+                       prefilter);
     }
 
     // getFrameInterp for colour frames (hsflow.h, hsflow_flow_interp_bgr): the
     // frames go up as BGR, the solve runs on their grey conversion, and each
     // channel gets the motion-compensated blend.  frames[k]: the frame at
     // times[k] as rows*cols*3 uint8, interleaved BGR; flags[k]: rows*cols
-    // HSFLOW_INTERP_* bytes, one per pixel.
+    // HSFLOW_INTERP_* bytes, one per pixel.  prefilter as in getFlowWarped, run
+    // on the grey planes.
     void getFrameInterpBgr(const BgrView &prev, const BgrView &next,
                            const std::vector<float> &times, int levels, int warps, int median,
                            std::vector<std::vector<uint8_t>> &frames,
-                           std::vector<std::vector<uint8_t>> *flags = nullptr) {
+                           std::vector<std::vector<uint8_t>> *flags = nullptr,
+                           const hsflow_prefilter *prefilter = nullptr) {
         if (!prev.data || !next.data) throw Error(HSFLOW_ERR_ARG, "empty image");
         if (prev.rows != next.rows || prev.cols != next.cols)
             throw Error(HSFLOW_ERR_SIZE, "Image sizes are different");
@@ -227,6 +271,7 @@ class HornSchunck {
         }
         const size_t dense = (size_t)prev.cols * 3;
         Context &c = ctx();
+        PrefilterScope scope(c, prefilter);
         c.check(hsflow_flow_interp_bgr(
             c.get(), prev.data, next.data, prev.rows, prev.cols, prev.step ? prev.step : dense,
             next.step ? next.step : dense, levels, warps, median, windowSize, maxIterations,
