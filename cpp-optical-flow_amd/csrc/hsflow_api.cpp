@@ -44,6 +44,9 @@ struct hsflow_ctx {
     // hsflow_ctx_set_prefilter: what the warped, bidirectional and interpolating
     // host-buffer calls run on the frames first (mode 0: nothing)
     hsflow_prefilter pf{0, 0.0f, 0.0f, 0.0f};
+    // hsflow_ctx_set_smoothness: the smoothness term of the same calls' solves
+    // (mode 0: the quadratic one)
+    hsflow_smoothness sm{0, 0.0f};
 };
 
 namespace {
@@ -272,29 +275,35 @@ struct Frames {
 
 int jacobi_one(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                float alpha, bool warm, bool maybe_f32, float *u, float *v,
-               void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr = nullptr);
+               void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr = nullptr,
+               const float *g = nullptr);
 int check_jacobi_args(hsflow_ctx *ctx, int rows, int cols, int batch, int window,
                       int iters, const float *u, const float *v, void *workspace,
                       size_t ws_bytes);
 int jacobi_sub(hsflow_ctx *ctx, int rows, int cols, int nb, int first, int batch,
                int window, int iters, float alpha, bool warm, bool maybe_f32, float *u,
-               float *v, const Workspace &w, hipStream_t s, const Frames *fr = nullptr);
+               float *v, const Workspace &w, hipStream_t s, const Frames *fr = nullptr,
+               const float *g = nullptr);
 
+// `g`: the weights of the flow-driven smoothness term (batch planes, as u and
+// v); then the passes are KJ's weighted ones (always warm, f32 planes), else
+// the plain Jacobi passes.
 int jacobi_impl(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                 float alpha, bool warm, bool maybe_f32, float *u, float *v,
-                void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr = nullptr) {
+                void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr = nullptr,
+                const float *g = nullptr) {
     int rc0 = check_jacobi_args(ctx, rows, cols, batch, window, iters, u, v, workspace,
                                 ws_bytes);
     if (rc0) return rc0;
     const int split = split_for(batch, s);
     if (split <= 1 || iters == 0)
         return jacobi_one(ctx, rows, cols, batch, window, iters, alpha, warm, maybe_f32, u,
-                          v, workspace, ws_bytes, s, fr);
+                          v, workspace, ws_bytes, s, fr, g);
     Workspace w = carve(workspace, rows, cols, batch);
     SidePool *pool = side_pool(split);
     if (!pool)
         return jacobi_one(ctx, rows, cols, batch, window, iters, alpha, warm, maybe_f32, u,
-                          v, workspace, ws_bytes, s, fr);
+                          v, workspace, ws_bytes, s, fr, g);
     const size_t plane = (size_t)rows * cols;
     HIP_TRY(ctx, hipEventRecord(pool->events[0], s));
     int first = 0, forked = 0, rc = HSFLOW_OK;
@@ -309,7 +318,8 @@ int jacobi_impl(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int 
         ++forked;
         // the sub-batch's slice of every workspace plane, as its own workspace
         rc = jacobi_sub(ctx, rows, cols, nb, first, batch, window, iters, alpha, warm,
-                        maybe_f32, u + first * plane, v + first * plane, w, sk, fr);
+                        maybe_f32, u + first * plane, v + first * plane, w, sk, fr,
+                        g ? g + first * plane : nullptr);
         first += nb;
     }
     // join every forked stream back, the error path included (a capture
@@ -322,11 +332,62 @@ int jacobi_impl(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int 
     return rc;
 }
 
+// KJ's depth: the caller's (hsflow_set_iters_per_launch) where KJ is built for
+// it, else the window's default
+int weighted_kb(int window) {
+    return hsflow::weighted_kb_supported(window, g_kb_override) ? g_kb_override
+                                                                : hsflow::weighted_default_kb(window);
+}
+
+// `iters` weighted iterations (KJ) of `batch` pairs from (u, v), the f32
+// gradient planes of `w` and the weights g; ping-pong with w.u2 / w.v2 as
+// run_passes does, the last pass landing in (u, v).
+int run_weighted_passes(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
+                        float alpha, const float *g, float *u, float *v, const Workspace &w,
+                        hipStream_t s) {
+    if (iters == 0) return HSFLOW_OK;
+    const size_t n = (size_t)rows * cols * batch;
+    const int kb = weighted_kb(window);
+    const int passes = (iters + kb - 1) / kb;
+    JacobiArgs a{};
+    a.rows = rows;
+    a.cols = cols;
+    a.batch = batch;
+    a.alpha2 = (float)((double)alpha * (double)alpha);
+    a.gx = w.gx;
+    a.gy = w.gy;
+    a.gt = w.gt;
+    auto dst_is_user = [&](int pass) { return ((passes - 1 - pass) & 1) == 0; };
+    const float *src_u = u, *src_v = v;
+    if (dst_is_user(0)) {  // would read and write (u, v) in one pass
+        HIP_TRY(ctx, hipMemcpyAsync(w.u2, u, n * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(w.v2, v, n * 4, hipMemcpyDeviceToDevice, s));
+        src_u = w.u2;
+        src_v = w.v2;
+    }
+    int done = 0;
+    for (int pass = 0; pass < passes; ++pass) {
+        a.iters = std::min(kb, iters - done);
+        a.u_in = src_u;
+        a.v_in = src_v;
+        a.u_out = dst_is_user(pass) ? u : w.u2;
+        a.v_out = dst_is_user(pass) ? v : w.v2;
+        hipError_t e = hsflow::launch_jacobi_weighted(a, g, window, kb, s);
+        if (e != hipSuccess) return hip_fail(ctx, e, "weighted jacobi launch");
+        src_u = a.u_out;
+        src_v = a.v_out;
+        done += a.iters;
+    }
+    return HSFLOW_OK;
+}
+
 // The Jacobi passes of `batch` pairs whose workspace planes are `w` (a view
 // that may start at any pair of a larger workspace).
 int run_passes(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                float alpha, bool warm, bool maybe_f32, float *u, float *v,
-               const Workspace &w, hipStream_t s, int fill_batch, const Frames *fr = nullptr) {
+               const Workspace &w, hipStream_t s, int fill_batch, const Frames *fr = nullptr,
+               const float *g = nullptr) {
+    if (g) return run_weighted_passes(ctx, rows, cols, batch, window, iters, alpha, g, u, v, w, s);
     const size_t n = (size_t)rows * cols * batch;
     if (iters == 0) {
         // hornSchunck.cpp:49-50: the loop does not run, u = v = 0
@@ -460,18 +521,19 @@ int check_jacobi_args(hsflow_ctx *ctx, int rows, int cols, int batch, int window
 
 int jacobi_one(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
                float alpha, bool warm, bool maybe_f32, float *u, float *v,
-               void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr) {
+               void *workspace, size_t ws_bytes, hipStream_t s, const Frames *fr,
+               const float *g) {
     int rc = check_jacobi_args(ctx, rows, cols, batch, window, iters, u, v, workspace,
                                ws_bytes);
     if (rc) return rc;
     return run_passes(ctx, rows, cols, batch, window, iters, alpha, warm, maybe_f32, u, v,
-                      carve(workspace, rows, cols, batch), s, batch, fr);
+                      carve(workspace, rows, cols, batch), s, batch, fr, g);
 }
 
 // pairs [first, first + nb) of a `batch`-pair workspace w
 int jacobi_sub(hsflow_ctx *ctx, int rows, int cols, int nb, int first, int batch,
                int window, int iters, float alpha, bool warm, bool maybe_f32, float *u,
-               float *v, const Workspace &w, hipStream_t s, const Frames *fr) {
+               float *v, const Workspace &w, hipStream_t s, const Frames *fr, const float *g) {
     const size_t off = (size_t)first * rows * cols;
     Workspace sub = w;
     sub.gpack = w.gpack + off;
@@ -489,7 +551,7 @@ int jacobi_sub(hsflow_ctx *ctx, int rows, int cols, int nb, int first, int batch
         sf = Frames{(const char *)fr->I0 + fo, (const char *)fr->I1 + fo, fr->dtype};
     }
     return run_passes(ctx, rows, cols, nb, window, iters, alpha, warm, maybe_f32, u, v, sub,
-                      s, batch, fr ? &sf : nullptr);
+                      s, batch, fr ? &sf : nullptr, g);
 }
 
 int gradients_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
@@ -821,17 +883,89 @@ int median_in_place(hsflow_ctx *ctx, float *u, float *v, int rows, int cols, int
     return HSFLOW_OK;
 }
 
+// ---- flow-driven smoothness ---------------------------------------------------
+bool sm_on(const hsflow_smoothness *sm) { return sm && sm->mode != HSFLOW_SMOOTH_QUADRATIC; }
+
+// a setting that is on: the mode and lambda (negated comparisons: NaN fails)
+int check_smoothness(hsflow_ctx *ctx, const hsflow_smoothness *sm) {
+    if (sm->mode != HSFLOW_SMOOTH_FLOW_DRIVEN)
+        return fail(ctx, HSFLOW_ERR_ARG, "smoothness mode %d is not 0 or 1", sm->mode);
+    if (!(sm->lambda > 0.0f && sm->lambda <= 3.0e38f))
+        return fail(ctx, HSFLOW_ERR_ARG, "smoothness lambda %g must be finite and > 0",
+                    (double)sm->lambda);
+    return HSFLOW_OK;
+}
+
+// ... and the window of a solve that runs with it: the sizes KJ is built for
+int check_smoothness_for(hsflow_ctx *ctx, const hsflow_smoothness *sm, int window) {
+    if (!sm_on(sm)) return HSFLOW_OK;
+    int rc = check_smoothness(ctx, sm);
+    if (rc) return rc;
+    if (window != 3 && window != 5)
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "flow-driven smoothness needs windowSize 3 or 5, not %d", window);
+    return HSFLOW_OK;
+}
+
+bool floats_overlap(const float *a, size_t na, const void *b, size_t nb_bytes) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb_bytes && pb < pa + na * 4;
+}
+
+// KG alone
+int diffusivity_impl(hsflow_ctx *ctx, const float *u, const float *v, int rows, int cols,
+                     int batch, float lambda, float *g, hipStream_t s) {
+    const hsflow_smoothness sm{HSFLOW_SMOOTH_FLOW_DRIVEN, lambda};
+    int rc = check_smoothness(ctx, &sm);
+    if (rc) return rc;
+    if (!sizes_ok(rows, cols, batch))
+        return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d batch %d", rows, cols, batch);
+    if (!u || !v || !g) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    const size_t n = (size_t)rows * cols * batch;
+    if (ranges_overlap(g, u, n) || ranges_overlap(g, v, n))
+        return fail(ctx, HSFLOW_ERR_ARG, "the weights overlap the flow");
+    hipError_t e = hsflow::launch_diffusivity(u, v, rows, cols, batch, lambda, g, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "diffusivity launch");
+    return HSFLOW_OK;
+}
+
+// KJ alone: `iters` weighted iterations from the workspace's f32 planes
+int jacobi_weighted_impl(hsflow_ctx *ctx, int rows, int cols, int batch, int window, int iters,
+                         float alpha, const float *g, float *u, float *v, void *workspace,
+                         size_t ws_bytes, hipStream_t s) {
+    if (window != 3 && window != 5)
+        return fail(ctx, HSFLOW_ERR_ARG, "weighted iterations need windowSize 3 or 5, not %d",
+                    window);
+    int rc = check_jacobi_args(ctx, rows, cols, batch, window, iters, u, v, workspace, ws_bytes);
+    if (rc) return rc;
+    if (!g) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
+    const size_t n = (size_t)rows * cols * batch;
+    const size_t wsb = carve(workspace, rows, cols, batch).bytes;
+    if (ranges_overlap(g, u, n) || ranges_overlap(g, v, n) || ranges_overlap(u, v, n) ||
+        floats_overlap(g, n, workspace, wsb) || floats_overlap(u, n, workspace, wsb) ||
+        floats_overlap(v, n, workspace, wsb))
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "the weights, the flow and the workspace overlap each other");
+    return jacobi_impl(ctx, rows, cols, batch, window, iters, alpha, true, true, u, v, workspace,
+                       ws_bytes, s, nullptr, g);
+}
+
 // The pyramid of pyramid_impl; per level, coarsest first: (u, v) = 0 or the
 // coarser result projected up, then `warps` times KW around the current
 // (u, v), `iters` Jacobi iterations warm-started from it and, for median != 0,
 // KM (median x median) on the level's (u, v).  median = 0 launches exactly
-// what the solve without the filter always has.
+// what the solve without the filter always has.  With a smoothness mode on,
+// KG turns each warp's (u, v) into weights -- in the Jacobi workspace's packed
+// gradient plane, which a warped solve never reads (KW sets flags[pair] = 1) --
+// and the iterations are KJ's weighted ones; off, the launches are unchanged.
 int warped_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
                 int cols, int batch, int levels, int warps, int median, int window, int iters,
-                float alpha, float *u, float *v, void *ws, size_t ws_bytes, hipStream_t s) {
+                float alpha, float *u, float *v, void *ws, size_t ws_bytes, hipStream_t s,
+                const hsflow_smoothness *sm = nullptr) {
     int rc = check_warped_args(ctx, warps, window, iters);
     if (rc) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_smoothness_for(ctx, sm, window))) return rc;
     rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, u, v, ws,
                             ws_bytes);
     if (rc) return rc;
@@ -857,9 +991,16 @@ int warped_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, i
                                      l ? HSFLOW_F32 : dtype_in, L.R[l], L.C[l], batch, ul, vl,
                                      nullptr, nullptr, nullptr, ws, L.jac_bytes, s);
             if (rc) return rc;
+            float *g = nullptr;
+            if (sm_on(sm)) {
+                g = (float *)carve(ws, L.R[l], L.C[l], batch).gpack;
+                hipError_t e = hsflow::launch_diffusivity(ul, vl, L.R[l], L.C[l], batch,
+                                                          sm->lambda, g, s);
+                if (e != hipSuccess) return hip_fail(ctx, e, "diffusivity launch");
+            }
             // need_f32: the planes are f32 for every pair
             rc = jacobi_impl(ctx, L.R[l], L.C[l], batch, window, iters, alpha, true, true, ul,
-                             vl, ws, L.jac_bytes, s);
+                             vl, ws, L.jac_bytes, s, nullptr, g);
             if (rc) return rc;
             if (median) {
                 rc = median_in_place(ctx, ul, vl, L.R[l], L.C[l], batch, median, ws, s);
@@ -918,20 +1059,22 @@ int bidir_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
                float alpha,
                float rel, float abs_thr, float *uf, float *vf, float *ub, float *vb,
                float *err_f, uint8_t *mask_f, uint32_t *counts_f, float *err_b,
-               uint8_t *mask_b, uint32_t *counts_b, void *ws, size_t ws_bytes, hipStream_t s) {
+               uint8_t *mask_b, uint32_t *counts_b, void *ws, size_t ws_bytes, hipStream_t s,
+               const hsflow_smoothness *sm = nullptr) {
     int rc = check_warped_args(ctx, warps, window, iters);
     if (rc) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_smoothness_for(ctx, sm, window))) return rc;
     rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, uf, vf, ws,
                             ws_bytes);
     if (rc) return rc;
     if (!ub || !vb) return fail(ctx, HSFLOW_ERR_ARG, "null device pointer");
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
     rc = warped_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
-                     iters, alpha, uf, vf, ws, ws_bytes, s);
+                     iters, alpha, uf, vf, ws, ws_bytes, s, sm);
     if (rc) return rc;
     rc = warped_impl(ctx, I1, I0, dtype_in, rows, cols, batch, levels, warps, median, window,
-                     iters, alpha, ub, vb, ws, ws_bytes, s);
+                     iters, alpha, ub, vb, ws, ws_bytes, s, sm);
     if (rc) return rc;
     if (err_f || mask_f || counts_f) {
         rc = consistency_run(ctx, uf, vf, ub, vb, rows, cols, batch, rel, abs_thr, err_f,
@@ -1050,15 +1193,16 @@ int check_pf_workspace(hsflow_ctx *ctx, const void *I0, const void *I1, size_t f
 int warped_pf_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
                    int cols, int batch, int levels, int warps, int median, int window, int iters,
                    float alpha, float *u, float *v, const hsflow_prefilter *pf, void *ws,
-                   size_t ws_bytes, hipStream_t s) {
+                   size_t ws_bytes, hipStream_t s, const hsflow_smoothness *sm = nullptr) {
     if (!pf_on(pf))
         return warped_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
-                           iters, alpha, u, v, ws, ws_bytes, s);
+                           iters, alpha, u, v, ws, ws_bytes, s, sm);
     PfPlan P;
     int rc = plan_prefilter(ctx, pf, &P);
     if (rc) return rc;
     if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_smoothness_for(ctx, sm, window))) return rc;
     rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, u, v, ws, ws_bytes);
     if (rc) return rc;
     const size_t solve = align_up(pyr_layout(rows, cols, batch, levels).bytes);
@@ -1069,7 +1213,7 @@ int warped_pf_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in
     rc = prefilter_pair(ctx, I0, I1, dtype_in, rows, cols, batch, P, ws, solve, &p0, &p1, s);
     if (rc) return rc;
     return warped_impl(ctx, p0, p1, HSFLOW_F32, rows, cols, batch, levels, warps, median, window,
-                       iters, alpha, u, v, ws, solve, s);
+                       iters, alpha, u, v, ws, solve, s, sm);
 }
 
 // hsflow_flow_bidir_pf_device: likewise in front of bidir_impl
@@ -1078,16 +1222,17 @@ int bidir_pf_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
                   float alpha, float rel, float abs_thr, float *uf, float *vf, float *ub,
                   float *vb, float *err_f, uint8_t *mask_f, uint32_t *counts_f, float *err_b,
                   uint8_t *mask_b, uint32_t *counts_b, const hsflow_prefilter *pf, void *ws,
-                  size_t ws_bytes, hipStream_t s) {
+                  size_t ws_bytes, hipStream_t s, const hsflow_smoothness *sm = nullptr) {
     if (!pf_on(pf))
         return bidir_impl(ctx, I0, I1, dtype_in, rows, cols, batch, levels, warps, median, window,
                           iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f,
-                          err_b, mask_b, counts_b, ws, ws_bytes, s);
+                          err_b, mask_b, counts_b, ws, ws_bytes, s, sm);
     PfPlan P;
     int rc = plan_prefilter(ctx, pf, &P);
     if (rc) return rc;
     if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_smoothness_for(ctx, sm, window))) return rc;
     rc = check_pyramid_args(ctx, I0, I1, dtype_in, rows, cols, batch, levels, uf, vf, ws,
                             ws_bytes);
     if (rc) return rc;
@@ -1102,7 +1247,7 @@ int bidir_pf_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
     if (rc) return rc;
     return bidir_impl(ctx, p0, p1, HSFLOW_F32, rows, cols, batch, levels, warps, median, window,
                       iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f, counts_f, err_b,
-                      mask_b, counts_b, ws, solve, s);
+                      mask_b, counts_b, ws, solve, s, sm);
 }
 
 // The host-buffer form of both pyramid solves: warps = 0 is hsflow_flow_pyramid,
@@ -1137,7 +1282,7 @@ int pyramid_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, 
     const int dt0 = dtype_in;
     rc = warps ? warped_pf_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, warps, median, window,
                                 iters, (float)alpha, du, dv, &ctx->pf, ctx->d_ws,
-                                ctx->d_ws_bytes, ctx->stream)
+                                ctx->d_ws_bytes, ctx->stream, &ctx->sm)
                : pyramid_impl(ctx, in0, in1, dt0, rows, cols, 1, levels, window, iters,
                               (float)alpha, du, dv, ctx->d_ws, ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
@@ -1192,7 +1337,7 @@ int bidir_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, in
                        iters, (float)alpha, rel, abs_thr, d[0], d[1], d[2], d[3], nullptr,
                        mask_f ? dmf : nullptr, counts ? dc : nullptr, nullptr,
                        mask_b ? dmb : nullptr, counts ? dc + 3 : nullptr, &ctx->pf, ctx->d_ws,
-                       ctx->d_ws_bytes, ctx->stream);
+                       ctx->d_ws_bytes, ctx->stream, &ctx->sm);
     if (rc) return rc;
     if (mask_f)
         HIP_TRY(ctx, hipMemcpy2DAsync(mask_f, mask_step, dmf, (size_t)cols, (size_t)cols, rows,
@@ -1332,12 +1477,14 @@ int flow_interp_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
                      int cols, int batch, int levels, int warps, int median, int window,
                      int iters, float alpha, float rel, float abs_thr, const float *times, int nt,
                      void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
-                     const hsflow_prefilter *pf, void *ws, size_t ws_bytes, hipStream_t s) {
+                     const hsflow_prefilter *pf, void *ws, size_t ws_bytes, hipStream_t s,
+                     const hsflow_smoothness *sm = nullptr) {
     PfPlan P;
     int rc = pf_on(pf) ? plan_prefilter(ctx, pf, &P) : HSFLOW_OK;
     if (rc) return rc;
     if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_smoothness_for(ctx, sm, window))) return rc;
     if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
         return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
                     HSFLOW_MAX_LEVELS);
@@ -1378,7 +1525,7 @@ int flow_interp_impl(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
     }
     rc = bidir_impl(ctx, S0, S1, dtype_solve, rows, cols, batch, levels, warps, median, window,
                     iters, alpha, rel, abs_thr, f[0], f[1], f[2], f[3], nullptr, mf, nullptr,
-                    nullptr, mb, nullptr, ws, L.solve_bytes, s);
+                    nullptr, mb, nullptr, ws, L.solve_bytes, s, sm);
     if (rc) return rc;
     return frame_interp_run(ctx, I0, I1, dtype_in, rows, cols, batch, f[0], f[1], f[2], f[3], mf,
                             mb, times, nt, out, dtype_out, flags, trusted, s);
@@ -1434,7 +1581,7 @@ int flow_interp_host(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
     rc = flow_interp_impl(ctx, in0, in1, dtype_in, rows, cols, 1, levels, warps, median, window,
                           iters, (float)alpha, rel, abs_thr, times, nt, dout, dev_out,
                           flags ? dfl : nullptr, trusted ? dtr : nullptr, &ctx->pf, ctx->d_ws,
-                          ctx->d_ws_bytes, ctx->stream);
+                          ctx->d_ws_bytes, ctx->stream, &ctx->sm);
     if (rc) return rc;
     if (flags)
         for (int k = 0; k < nt; ++k)
@@ -1548,12 +1695,14 @@ int flow_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
                          int cols, int batch, int levels, int warps, int median, int window,
                          int iters, float alpha, float rel, float abs_thr, const float *times,
                          int nt, void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
-                         const hsflow_prefilter *pf, void *ws, size_t ws_bytes, hipStream_t s) {
+                         const hsflow_prefilter *pf, void *ws, size_t ws_bytes, hipStream_t s,
+                         const hsflow_smoothness *sm = nullptr) {
     PfPlan P;
     int rc = pf_on(pf) ? plan_prefilter(ctx, pf, &P) : HSFLOW_OK;
     if (rc) return rc;
     if ((rc = check_warped_args(ctx, warps, window, iters))) return rc;
     if ((rc = check_median_arg(ctx, median))) return rc;
+    if ((rc = check_smoothness_for(ctx, sm, window))) return rc;
     if (levels < 1 || levels > HSFLOW_MAX_LEVELS)
         return fail(ctx, HSFLOW_ERR_ARG, "levels %d outside [1, %d]", levels,
                     HSFLOW_MAX_LEVELS);
@@ -1599,7 +1748,7 @@ int flow_interp_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
     }
     rc = bidir_impl(ctx, S0, S1, dtype_solve, rows, cols, batch, levels, warps, median, window,
                     iters, alpha, rel, abs_thr, f[0], f[1], f[2], f[3], nullptr, mf, nullptr,
-                    nullptr, mb, nullptr, ws, L.grey.solve_bytes, s);
+                    nullptr, mb, nullptr, ws, L.grey.solve_bytes, s, sm);
     if (rc) return rc;
     return frame_interp_bgr_run(ctx, bgr0, bgr1, rows, cols, batch, f[0], f[1], f[2], f[3], mf, mb,
                                 times, nt, out, dtype_out, flags, trusted, s);
@@ -1657,7 +1806,7 @@ int flow_interp_bgr_host(hsflow_ctx *ctx, const uint8_t *bgr0, const uint8_t *bg
     rc = flow_interp_bgr_impl(ctx, in0, in1, rows, cols, 1, levels, warps, median, window, iters,
                               (float)alpha, rel, abs_thr, times, nt, dout, dtype_out,
                               flags ? dfl : nullptr, trusted ? dtr : nullptr, &ctx->pf, ctx->d_ws,
-                              ctx->d_ws_bytes, ctx->stream);
+                              ctx->d_ws_bytes, ctx->stream, &ctx->sm);
     if (rc) return rc;
     if (flags)
         for (int k = 0; k < nt; ++k)
@@ -2355,6 +2504,91 @@ int hsflow_ctx_set_prefilter(hsflow_ctx *ctx, const hsflow_prefilter *pf) {
 int hsflow_ctx_prefilter(const hsflow_ctx *ctx, hsflow_prefilter *pf) {
     if (!ctx || !pf) return fail(nullptr, HSFLOW_ERR_ARG, "null %s", ctx ? "prefilter" : "context");
     *pf = ctx->pf;
+    return HSFLOW_OK;
+}
+
+int hsflow_flow_diffusivity_device(const float *u, const float *v, int rows, int cols, int batch,
+                                   float lambda, float *g, void *stream) {
+    DeviceGuard guard((hipStream_t)stream);
+    return diffusivity_impl(nullptr, u, v, rows, cols, batch, lambda, g, (hipStream_t)stream);
+}
+
+int hsflow_jacobi_weighted_device(int rows, int cols, int batch, int window, int iters,
+                                  float alpha, const float *g, float *u, float *v,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard guard((hipStream_t)stream);
+    return jacobi_weighted_impl(nullptr, rows, cols, batch, window, iters, alpha, g, u, v,
+                                workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_warped_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float *u, float *v,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return warped_pf_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                          window, iters, alpha, u, v, pf, workspace, workspace_bytes,
+                          (hipStream_t)stream, sm);
+}
+
+int hsflow_flow_bidir_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                int batch, int levels, int warps, int median, int window,
+                                int iters, float alpha, float rel, float abs_thr, float *uf,
+                                float *vf, float *ub, float *vb, float *err_f, uint8_t *mask_f,
+                                uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                uint32_t *counts_b, const hsflow_prefilter *pf,
+                                const hsflow_smoothness *sm, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return bidir_pf_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                         window, iters, alpha, rel, abs_thr, uf, vf, ub, vb, err_f, mask_f,
+                         counts_f, err_b, mask_b, counts_b, pf, workspace, workspace_bytes,
+                         (hipStream_t)stream, sm);
+}
+
+int hsflow_flow_interp_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, void *out, int dtype_out,
+                                 uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                 const hsflow_smoothness *sm, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return flow_interp_impl(nullptr, I0, I1, dtype_in, rows, cols, batch, levels, warps, median,
+                            window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out, flags,
+                            trusted, pf, workspace, workspace_bytes, (hipStream_t)stream, sm);
+}
+
+int hsflow_flow_interp_bgr_sm_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int warps, int median, int window,
+                                     int iters, float alpha, float rel, float abs_thr,
+                                     const float *times, int nt, void *out, int dtype_out,
+                                     uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                     const hsflow_smoothness *sm, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return flow_interp_bgr_impl(nullptr, bgr0, bgr1, rows, cols, batch, levels, warps, median,
+                                window, iters, alpha, rel, abs_thr, times, nt, out, dtype_out,
+                                flags, trusted, pf, workspace, workspace_bytes,
+                                (hipStream_t)stream, sm);
+}
+
+int hsflow_ctx_set_smoothness(hsflow_ctx *ctx, const hsflow_smoothness *sm) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    if (sm_on(sm)) {
+        int rc = check_smoothness(ctx, sm);
+        if (rc) return rc;
+        ctx->sm = *sm;
+    } else {
+        ctx->sm = hsflow_smoothness{HSFLOW_SMOOTH_QUADRATIC, 0.0f};
+    }
+    return HSFLOW_OK;
+}
+
+int hsflow_ctx_smoothness(const hsflow_ctx *ctx, hsflow_smoothness *sm) {
+    if (!ctx || !sm) return fail(nullptr, HSFLOW_ERR_ARG, "null %s", ctx ? "smoothness" : "context");
+    *sm = ctx->sm;
     return HSFLOW_OK;
 }
 

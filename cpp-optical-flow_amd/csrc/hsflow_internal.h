@@ -116,6 +116,18 @@ constexpr int kPrefilterMaxRadius = 15;
 hipError_t launch_prefilter(const void *I, int dtype_in, int rows, int cols, int batch, int mode,
                             int radius, const float *weights, float eps, float scale, float *out,
                             hipStream_t s);
+// KG (hsflow_smooth.hip): the flow-driven smoothness weights of (u, v), dense
+// f32 batch planes -> g = 1 / sqrt(1 + |grad (8u, 8v)|^2 / lambda^2), central
+// differences with the border replicated
+hipError_t launch_diffusivity(const float *u, const float *v, int rows, int cols, int batch,
+                              float lambda, float *g, hipStream_t s);
+// KJ (hsflow_smooth.hip): one pass of a.iters (<= KB) g-weighted Jacobi
+// iterations from the f32 gradient planes (a.gx, a.gy, a.gt) and the weights
+// g; a.u_in / a.v_in are required (always a warm start), a.gpack and a.flags
+// are not read.  W = 3 or 5; same bits for every supported KB.
+bool weighted_kb_supported(int W, int KB);
+int weighted_default_kb(int W);
+hipError_t launch_jacobi_weighted(JacobiArgs a, const float *g, int W, int KB, hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

@@ -326,7 +326,8 @@ def solve_stream(src, pairs: Sequence[Tuple[int, int]], window: int, iters: int,
 
 # ------------------------------------------------------- frame interpolation
 def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int, iters: int,
-                         alpha: float, median: int = 0, context=None, prefilter=None):
+                         alpha: float, median: int = 0, context=None, prefilter=None,
+                         smoothness=None):
     """A colour source at `factor` times its frame rate: a generator of
     (len(src) - 1) * factor + 1 BGR uint8 frames.  Every factor-th one is a
     source frame itself, untouched; between two consecutive source frames come
@@ -336,7 +337,8 @@ def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int,
     (H x W x 3); a grey source raises FrameError (use Context.interpolate).
     `context`: an hsflow.Context to run on (default: hsflow.default_context()).
     `prefilter`: an hsflow.Prefilter for every pair's solve (exposure steps,
-    fades, flicker), as in Context.interpolate_bgr."""
+    fades, flicker), as in Context.interpolate_bgr.  `smoothness`: an
+    hsflow.Smoothness for every pair's solve (sharp motion boundaries)."""
     factor = int(factor)
     if factor < 1:
         raise ValueError("factor must be at least 1")
@@ -356,7 +358,8 @@ def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int,
                 import hsflow
                 ctx = hsflow.default_context()
             mid = ctx.interpolate_bgr(prev, nxt, times, levels, warps, window, iters, alpha,
-                                      median=median, out_dtype=np.uint8, prefilter=prefilter)
+                                      median=median, out_dtype=np.uint8, prefilter=prefilter,
+                                      smoothness=smoothness)
             for k in range(len(times)):
                 yield mid[k]
         yield nxt

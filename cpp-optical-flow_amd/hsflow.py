@@ -90,6 +90,10 @@ EXPORTS = (
     "hsflow_flow_warped_pf_device", "hsflow_flow_bidir_pf_device",
     "hsflow_flow_interp_pf_device", "hsflow_flow_interp_bgr_pf_device",
     "hsflow_ctx_set_prefilter", "hsflow_ctx_prefilter",
+    "hsflow_flow_diffusivity_device", "hsflow_jacobi_weighted_device",
+    "hsflow_flow_warped_sm_device", "hsflow_flow_bidir_sm_device",
+    "hsflow_flow_interp_sm_device", "hsflow_flow_interp_bgr_sm_device",
+    "hsflow_ctx_set_smoothness", "hsflow_ctx_smoothness",
 )
 
 # modes of the brightness-robust prefilter (HSFLOW_PREFILTER_*)
@@ -124,6 +128,40 @@ def _pf_arg(prefilter):
     if not isinstance(prefilter, Prefilter):
         prefilter = Prefilter(*prefilter)
     c = prefilter._c()
+    return c, ctypes.byref(c)
+
+
+# smoothness terms of the warped solves (HSFLOW_SMOOTH_*)
+SMOOTH_QUADRATIC, SMOOTH_FLOW_DRIVEN = 0, 1
+
+
+class _CSmoothness(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("lam", ctypes.c_float)]
+
+
+class Smoothness(collections.namedtuple("Smoothness", "mode lam")):
+    """hsflow_smoothness: the smoothness term of the warped, bidirectional and
+    interpolating solves.  SMOOTH_FLOW_DRIVEN weights each tap of the window
+    mean by g = 1 / sqrt(1 + |grad flow|^2 / lam^2), recomputed at every warp
+    (include/hsflow.h): motion boundaries stay sharp.  lam: the flow gradient,
+    px per px, at which the weight is 1/sqrt(2); 0.1 .. 0.3.  The window must
+    be 3 or 5.  Use alpha ~ 100 with median=5 and 4 warps."""
+    __slots__ = ()
+
+    def __new__(cls, mode=SMOOTH_FLOW_DRIVEN, lam=0.3):
+        return super().__new__(cls, int(mode), float(lam))
+
+    def _c(self):
+        return _CSmoothness(self.mode, self.lam)
+
+
+def _sm_arg(smoothness):
+    """(keep-alive struct, pointer or None) of a Smoothness / None."""
+    if smoothness is None:
+        return None, None
+    if not isinstance(smoothness, Smoothness):
+        smoothness = Smoothness(*smoothness)
+    c = smoothness._c()
     return c, ctypes.byref(c)
 
 
@@ -272,6 +310,20 @@ def lib():
                                                    i, _vp, i, _vp, _vp, pfp, _vp, _sz, _vp]
     L.hsflow_ctx_set_prefilter.argtypes = [_vp, pfp]
     L.hsflow_ctx_prefilter.argtypes = [_vp, pfp]
+    smp = ctypes.POINTER(_CSmoothness)
+    L.hsflow_flow_diffusivity_device.argtypes = [_vp, _vp, i, i, i, f, _vp, _vp]
+    L.hsflow_jacobi_weighted_device.argtypes = [i, i, i, i, i, f, _vp, _vp, _vp, _vp, _sz, _vp]
+    L.hsflow_flow_warped_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f,
+                                               _vp, _vp, pfp, smp, _vp, _sz, _vp]
+    L.hsflow_flow_bidir_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, pfp, smp, _vp, _sz, _vp]
+    L.hsflow_flow_interp_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f, fp,
+                                               i, _vp, i, _vp, _vp, pfp, smp, _vp, _sz, _vp]
+    L.hsflow_flow_interp_bgr_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f, fp,
+                                                   i, _vp, i, _vp, _vp, pfp, smp, _vp, _sz, _vp]
+    L.hsflow_ctx_set_smoothness.argtypes = [_vp, smp]
+    L.hsflow_ctx_smoothness.argtypes = [_vp, smp]
     L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               _vp, _sz, _vp]
@@ -399,6 +451,34 @@ class Context:
         finally:
             self.set_prefilter(was)
 
+    def set_smoothness(self, smoothness=None):
+        """The context's smoothness term (hsflow_ctx_set_smoothness) for
+        flow_warped, flow_bidir, interpolate and interpolate_bgr.  None or mode
+        0 = quadratic (default).  flow, flow_bgr, flow_pyramid and gradients are
+        the reference's semantics and ignore it."""
+        _, p = _sm_arg(smoothness)
+        _check(lib().hsflow_ctx_set_smoothness(self._p, p), self._p)
+
+    def smoothness(self):
+        """The context's current Smoothness, None when quadratic."""
+        c = _CSmoothness()
+        _check(lib().hsflow_ctx_smoothness(self._p, ctypes.byref(c)))
+        return Smoothness(c.mode, c.lam) if c.mode else None
+
+    @contextlib.contextmanager
+    def _smoothness_as(self, smoothness):
+        """`smoothness` (a Smoothness) on the context for one call, the setting
+        before it restored afterwards; None leaves the context's own."""
+        if smoothness is None:
+            yield
+            return
+        was = self.smoothness()
+        self.set_smoothness(smoothness)
+        try:
+            yield
+        finally:
+            self.set_smoothness(was)
+
     def flow(self, I0, I1, window: int, iters: int, alpha: float, out_dtype=np.float64,
              out=None):
         """getFlow on host arrays.  `out` = (u, v): C-contiguous rows x cols
@@ -444,14 +524,16 @@ class Context:
         return u, v
 
     def flow_warped(self, I0, I1, levels: int, warps: int, window: int, iters: int,
-                    alpha: float, out_dtype=np.float64, median: int = 0, prefilter=None):
+                    alpha: float, out_dtype=np.float64, median: int = 0, prefilter=None,
+                    smoothness=None):
         """Warped coarse-to-fine solve for large displacements (`warps`
         re-linearisations per level, `iters` iterations each), see
         hsflow_flow_warped in include/hsflow.h.  (u, v) * SOBEL_GAIN is the
         motion in pixels.  median = 3 or 5 filters (u, v) with a median of
         that size after every warp's iterations (hsflow_flow_warped_median);
         0 = none.  prefilter: a Prefilter set on the context for this call
-        (None: the context's own setting, off by default)."""
+        (None: the context's own setting, off by default).  smoothness: a
+        Smoothness, likewise (window 3 or 5 then)."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -460,7 +542,7 @@ class Context:
         u = np.empty((rows, cols), out_dtype)
         v = np.empty((rows, cols), out_dtype)
         code = F64 if u.dtype == np.float64 else F32
-        with self._prefilter_as(prefilter):
+        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
             rc = lib().hsflow_flow_warped_median(
                 self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
                 b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
@@ -472,7 +554,7 @@ class Context:
                    alpha: float, rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                    out_dtype=np.float64, backward: bool = True, masks: bool = True,
                    counts: bool = True, out=None, mask_out=None, median: int = 0,
-                   prefilter=None):
+                   prefilter=None, smoothness=None):
         """Warped solve in both directions with the forward-backward check
         (hsflow_flow_bidir in include/hsflow.h).  Returns a BidirHost: u, v
         (I0 -> I1), ub, vb (I1 -> I0, None unless `backward`), mask_f, mask_b
@@ -480,8 +562,8 @@ class Context:
         and counts (uint32 [2, 3], forward then backward, None unless
         `counts`).  `out`: an array [4, rows, >= cols] of out_dtype whose
         planes' first `cols` columns receive u, v, ub, vb (a padded row step);
-        `mask_out`: likewise uint8 [2, rows, >= cols] for the masks.  median
-        and prefilter as in flow_warped, for both directions."""
+        `mask_out`: likewise uint8 [2, rows, >= cols] for the masks.  median,
+        prefilter and smoothness as in flow_warped, for both directions."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -503,7 +585,7 @@ class Context:
         mf, mb = mask_out[0, :, :cols], mask_out[1, :, :cols]
         cnt = np.zeros((2, 3), np.uint32) if counts else None
         code = F64 if out.dtype == np.float64 else F32
-        with self._prefilter_as(prefilter):
+        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
             rc = lib().hsflow_flow_bidir_median(
                 self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
                 b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
@@ -520,7 +602,7 @@ class Context:
     def interpolate(self, I0, I1, times, levels: int, warps: int, window: int, iters: int,
                     alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                     abs: float = CONSISTENCY_ABS, out_dtype=np.float32,
-                    with_flags: bool = False, prefilter=None):
+                    with_flags: bool = False, prefilter=None, smoothness=None):
         """The frames at `times` (each in [0, 1]; at most MAX_TIMES) between I0
         and I1: the bidirectional warped solve, then the motion-compensated
         blend (hsflow_flow_interp in include/hsflow.h).  Returns an array
@@ -529,7 +611,7 @@ class Context:
         bits; 0 = both sources pass the forward-backward check), trusted uint32
         [len(times)], the pixels per frame with flags == 0.  prefilter as in
         flow_warped: the flows come from the prefiltered frames, the frames
-        themselves are sampled."""
+        themselves are sampled.  smoothness as in flow_warped."""
         a, b = _as_image(I0), _as_image(I1)
         if a.shape != b.shape:
             raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
@@ -544,7 +626,7 @@ class Context:
         trusted = np.zeros(nt, np.uint32) if with_flags else None
         planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
         fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
-        with self._prefilter_as(prefilter):
+        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
             rc = lib().hsflow_flow_interp(
                 self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
                 b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
@@ -556,7 +638,8 @@ class Context:
     def interpolate_bgr(self, bgr0, bgr1, times, levels: int, warps: int, window: int,
                         iters: int, alpha: float, median: int = 0,
                         rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
-                        out_dtype=np.uint8, with_flags: bool = False, prefilter=None):
+                        out_dtype=np.uint8, with_flags: bool = False, prefilter=None,
+                        smoothness=None):
         """The colour frames at `times` between two decoded 8-bit BGR frames
         (H x W x 3, strided rows accepted): uploaded as BGR, converted to grey
         and solved both ways on the GPU, then the motion-compensated blend of
@@ -564,7 +647,7 @@ class Context:
         array [len(times), rows, cols, 3] of out_dtype (uint8 or float32), or
         with_flags: (frames, flags, trusted) -- flags uint8 [len(times), rows,
         cols] and trusted uint32 [len(times)] as in interpolate.  prefilter as
-        in flow_warped, run on the grey planes."""
+        in flow_warped, run on the grey planes; smoothness as in flow_warped."""
         a = np.asarray(bgr0)
         b = np.asarray(bgr1)
         for x in (a, b):
@@ -587,7 +670,7 @@ class Context:
         trusted = np.zeros(nt, np.uint32) if with_flags else None
         planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
         fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
-        with self._prefilter_as(prefilter):
+        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
             rc = lib().hsflow_flow_interp_bgr(
                 self._p, a.ctypes.data, b.ctypes.data, rows, cols, a.strides[0], b.strides[0],
                 int(levels), int(warps), int(median), int(window), int(iters), float(alpha),
@@ -741,7 +824,7 @@ class hornSchunck:  # noqa: N801  (reference class name, hornSchunck.cpp:8)
 
 
 def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int = 1,
-            warps: int = 0, median: int = 0, prefilter=None):
+            warps: int = 0, median: int = 0, prefilter=None, smoothness=None):
     """compute(I0, I1, alpha, nIter) -> (u, v): the north-star convenience
     wrapper over hornSchunck(windowSize, nIter, alpha).getFlow; levels > 1
     runs the config-5 coarse-to-fine warm start (nIter per level).  warps >= 1
@@ -749,16 +832,20 @@ def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int =
     `warps` re-linearisations per level, nIter iterations each); warps = 0
     keeps the behaviour above.  median = 3 or 5 (MEDIAN_SIZES) filters the
     flow after every warp's iterations and needs warps >= 1; so does
-    prefilter (a Prefilter: the frames are locally normalised first)."""
+    prefilter (a Prefilter: the frames are locally normalised first) and so
+    does smoothness (a Smoothness: the flow-driven, edge-preserving term)."""
     if median and not warps:
         raise HsflowError(HSFLOW_ERR_ARG, f"median {median} needs the warped solve (warps >= 1)")
     if prefilter is not None and not warps:
         raise HsflowError(HSFLOW_ERR_ARG, "prefilter needs the warped solve (warps >= 1)")
+    if smoothness is not None and not warps:
+        raise HsflowError(HSFLOW_ERR_ARG, "smoothness needs the warped solve (warps >= 1)")
     if warps:
         if not 1 <= int(warps) <= MAX_WARPS:
             raise HsflowError(HSFLOW_ERR_ARG, f"warps {warps} outside [1, {MAX_WARPS}]")
         return default_context().flow_warped(I0, I1, levels, warps, windowSize, nIter, alpha,
-                                             median=median, prefilter=prefilter)
+                                             median=median, prefilter=prefilter,
+                                             smoothness=smoothness)
     if levels > 1:
         return default_context().flow_pyramid(I0, I1, levels, windowSize, nIter, alpha)
     return hornSchunck(windowSize, nIter, alpha).getFlow(I0, I1)
@@ -911,7 +998,7 @@ def flow_pyramid_device(I0, I1, levels: int, window: int, iters: int, alpha: flo
 
 def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
                        alpha: float, u=None, v=None, workspace=None, stream=None,
-                       median: int = 0, prefilter=None):
+                       median: int = 0, prefilter=None, smoothness=None):
     """Warped coarse-to-fine solve on torch CUDA tensors [B, H, W] (uint8 /
     float16 / float32 / float64): per level `warps` times the gradients
     linearised around the current flow and `iters` Jacobi iterations.
@@ -920,7 +1007,10 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
     of that size over (u, v) after every warp's iterations
     (hsflow_flow_warped_median_device); 0 = none.  prefilter: a Prefilter run
     on both frames first (hsflow_flow_warped_pf_device); the workspace then
-    needs prefilter_planes_bytes(rows, cols, batch) more.  Stream-ordered."""
+    needs prefilter_planes_bytes(rows, cols, batch) more.  smoothness: a
+    Smoothness; SMOOTH_FLOW_DRIVEN runs the g-weighted iterations
+    (hsflow_flow_warped_sm_device; window 3 or 5, no more workspace).
+    Stream-ordered."""
     rows, cols = I0.shape[-2:]
     batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
     _check_dense(I0, (rows, cols), "I0")
@@ -934,15 +1024,16 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
     _check_plane(u, (rows, cols), batch, "u")
     _check_plane(v, (rows, cols), batch, "v")
     keep, pf = _pf_arg(prefilter)
+    keep_sm, sm = _sm_arg(smoothness)
     if workspace is None:
         n = pyramid_workspace_bytes(rows, cols, batch, levels) + \
             _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     with _on(I0.device):
-        rc = lib().hsflow_flow_warped_pf_device(
+        rc = lib().hsflow_flow_warped_sm_device(
             I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
             int(warps), int(median), int(window), int(iters), float(alpha), u.data_ptr(),
-            v.data_ptr(), pf, workspace.data_ptr(), workspace.numel(),
+            v.data_ptr(), pf, sm, workspace.data_ptr(), workspace.numel(),
             _stream_ptr(stream, I0.device))
     _check(rc)
     return u, v
@@ -1020,7 +1111,7 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
                       rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                       uf=None, vf=None, ub=None, vb=None, err_f=None, mask_f=True,
                       counts_f=None, err_b=None, mask_b=None, counts_b=None, workspace=None,
-                      stream=None, median: int = 0, prefilter=None):
+                      stream=None, median: int = 0, prefilter=None, smoothness=None):
     """Warped solve of I0 -> I1 (uf, vf) and I1 -> I0 (ub, vb) on torch CUDA
     tensors [B, H, W], then the forward-backward check each way
     (hsflow_flow_bidir_device in include/hsflow.h).  The flows equal
@@ -1053,17 +1144,19 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
                 want, I0.shape, torch.float32 if name.startswith("err") else torch.uint8,
                 I0.device, name))
     keep, pf = _pf_arg(prefilter)
+    keep_sm, sm = _sm_arg(smoothness)
     if workspace is None:
         n = bidir_workspace_bytes(rows, cols, batch, levels) + \
             _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     ptr = (lambda t: t.data_ptr() if t is not None else None)
     with _on(I0.device):
-        rc = lib().hsflow_flow_bidir_pf_device(
+        rc = lib().hsflow_flow_bidir_sm_device(
             I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
             int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
             float(abs),
-            *[t.data_ptr() for t in flows], *[ptr(t) for t in outs], pf, workspace.data_ptr(),
+            *[t.data_ptr() for t in flows], *[ptr(t) for t in outs], pf, sm,
+            workspace.data_ptr(),
             workspace.numel(), _stream_ptr(stream, I0.device))
     _check(rc)
     return BidirDevice(*flows, *outs)
@@ -1162,7 +1255,8 @@ def flow_interp_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -
 def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iters: int,
                        alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                        abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
-                       trusted=None, workspace=None, stream=None, prefilter=None):
+                       trusted=None, workspace=None, stream=None, prefilter=None,
+                       smoothness=None):
     """flow_bidir_device(median=...) into planes of the workspace, then
     frame_interp_device with both masks: one call, the same bits
     (hsflow_flow_interp_device in include/hsflow.h).  `workspace`:
@@ -1182,17 +1276,18 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
     tm = _times_array(times)
     out, flags, trusted = _interp_outputs(I0, len(tm), out, out_dtype, flags, trusted)
     keep, pf = _pf_arg(prefilter)
+    keep_sm, sm = _sm_arg(smoothness)
     if workspace is None:
         n = flow_interp_workspace_bytes(rows, cols, batch, levels) + \
             _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
     ptr = (lambda t: t.data_ptr() if t is not None else None)
     with _on(I0.device):
-        rc = lib().hsflow_flow_interp_pf_device(
+        rc = lib().hsflow_flow_interp_sm_device(
             I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
             int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
             float(abs), tm, len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32,
-            ptr(flags), ptr(trusted), pf, workspace.data_ptr(), workspace.numel(),
+            ptr(flags), ptr(trusted), pf, sm, workspace.data_ptr(), workspace.numel(),
             _stream_ptr(stream, I0.device))
     _check(rc)
     return out, flags, trusted
@@ -1288,7 +1383,8 @@ def flow_interp_bgr_workspace_bytes(rows: int, cols: int, batch: int, levels: in
 def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: int, iters: int,
                            alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                            abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
-                           trusted=None, workspace=None, stream=None, prefilter=None):
+                           trusted=None, workspace=None, stream=None, prefilter=None,
+                           smoothness=None):
     """bgr_to_gray_device of both frames, flow_bidir_device(median=...) on the
     grey planes, then frame_interp_bgr_device with both masks: one call, the
     same bits (hsflow_flow_interp_bgr_device in include/hsflow.h).
@@ -1306,17 +1402,18 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
     tm = _times_array(times)
     out, flags, trusted = _bgr_interp_outputs(bgr0, len(tm), out, out_dtype, flags, trusted)
     keep, pf = _pf_arg(prefilter)
+    keep_sm, sm = _sm_arg(smoothness)
     if workspace is None:
         n = flow_interp_bgr_workspace_bytes(rows, cols, batch, levels) + \
             _pf_extra(prefilter, rows, cols, batch)
         workspace = torch.empty(n, dtype=torch.uint8, device=bgr0.device)
     ptr = (lambda t: t.data_ptr() if t is not None else None)
     with _on(bgr0.device):
-        rc = lib().hsflow_flow_interp_bgr_pf_device(
+        rc = lib().hsflow_flow_interp_bgr_sm_device(
             bgr0.data_ptr(), bgr1.data_ptr(), rows, cols, batch, int(levels), int(warps),
             int(median), int(window), int(iters), float(alpha), float(rel), float(abs), tm,
             len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32, ptr(flags),
-            ptr(trusted), pf, workspace.data_ptr(), workspace.numel(),
+            ptr(trusted), pf, sm, workspace.data_ptr(), workspace.numel(),
             _stream_ptr(stream, bgr0.device))
     _check(rc)
     return out, flags, trusted
@@ -1450,6 +1547,41 @@ def jacobi_device(rows, cols, batch, window, iters, alpha, u, v, workspace,
                                         int(iters), float(alpha), int(bool(warm_start)),
                                         u.data_ptr(), v.data_ptr(), workspace.data_ptr(),
                                         workspace.numel(), _stream_ptr(stream, u.device))
+    _check(rc)
+
+
+def diffusivity_device(u, v, lam: float, g=None, stream=None):
+    """The flow-driven smoothness weights alone (hsflow_flow_diffusivity_device
+    in include/hsflow.h): g = 1 / sqrt(1 + |grad (8u, 8v)|^2 / lam^2) of float32
+    CUDA tensors [B, H, W] (or [H, W]) in solver units, central differences,
+    border replicated.  g is allocated unless given and must not overlap u or
+    v.  Returns g.  Stream-ordered."""
+    rows, cols = u.shape[-2:]
+    batch = int(np.prod(u.shape[:-2])) if u.dim() > 2 else 1
+    if g is None:
+        g = torch.empty(u.shape, dtype=torch.float32, device=u.device)
+    for t, name in ((u, "u"), (v, "v"), (g, "g")):
+        _check_plane(t, (rows, cols), batch, name)
+    with _on(u.device):
+        rc = lib().hsflow_flow_diffusivity_device(u.data_ptr(), v.data_ptr(), rows, cols, batch,
+                                                  float(lam), g.data_ptr(),
+                                                  _stream_ptr(stream, u.device))
+    _check(rc)
+    return g
+
+
+def jacobi_weighted_device(rows, cols, batch, window, iters, alpha, g, u, v, workspace,
+                           stream=None):
+    """`iters` g-weighted iterations warm-started from (u, v), in place, from
+    the f32 gradient planes warp_gradients_device left in `workspace`
+    (hsflow_jacobi_weighted_device in include/hsflow.h); window 3 or 5."""
+    for t, name in ((g, "g"), (u, "u"), (v, "v")):
+        _check_plane(t, (rows, cols), batch, name)
+    with _on(u.device):
+        rc = lib().hsflow_jacobi_weighted_device(int(rows), int(cols), int(batch), int(window),
+                                                 int(iters), float(alpha), g.data_ptr(),
+                                                 u.data_ptr(), v.data_ptr(), workspace.data_ptr(),
+                                                 workspace.numel(), _stream_ptr(stream, u.device))
     _check(rc)
 
 

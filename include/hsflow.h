@@ -152,7 +152,10 @@ int hsflow_jacobi_device(int rows, int cols, int batch, int window, int iters,
 
 /* Iterations fused per Jacobi launch (temporal blocking depth) the library
  * picks for this shape; 0 = automatic (default).  Results are bit-identical
- * for every depth.  Process-wide; not thread-safe against running solves. */
+ * for every depth.  Process-wide; not thread-safe against running solves.
+ * The weighted passes of the flow-driven smoothness term (below) take k
+ * where they are built for it (window 5: 2..4, window 3: 3, 4, 6), else their
+ * own default (3 and 6). */
 int hsflow_set_iters_per_launch(int k);
 int hsflow_iters_per_launch(int rows, int cols, int batch, int window);
 
@@ -701,6 +704,108 @@ int hsflow_flow_interp_bgr_pf_device(const uint8_t *bgr0, const uint8_t *bgr1, i
  * hsflow_ctx_prefilter reads the setting back. */
 int hsflow_ctx_set_prefilter(hsflow_ctx *ctx, const hsflow_prefilter *pf);
 int hsflow_ctx_prefilter(const hsflow_ctx *ctx, hsflow_prefilter *pf);
+
+/* ---- flow-driven (edge-preserving) smoothness of the warped solves ---------
+ * The smoothness term of every solve above is quadratic: each iteration
+ * replaces (u, v) by its plain window mean, which averages across a motion
+ * boundary, so the flow crosses an object's edge as a ramp about ten pixels
+ * wide -- at pixels that are visible in both frames and that neither the median
+ * nor the forward-backward check repairs.  The flow-driven term
+ * weights each tap by a diffusivity g that is small where the flow around which
+ * the warp linearises already has a large gradient (lagged diffusivity).  Per
+ * level and per warp, from that warp's (u0, v0), U = 8 u0, V = 8 v0 in px:
+ *   Ux = 0.5 (U[y][min(x+1, cols-1)] - U[y][max(x-1, 0)]),  Uy, Vx, Vy likewise
+ *        (border replicated)
+ *   s  = Ux^2 + Uy^2 + Vx^2 + Vy^2
+ *   g  = 1 / sqrt(1 + s / lambda^2)                              in (0, 1]
+ * `lambda` is the flow gradient, px per px, at which the weight drops to
+ * 1/sqrt(2): finite and > 0, recommended 0.1 .. 0.3.  The iteration is the
+ * getFlow loop with the two means replaced.  S = the window sum over the taps
+ * inside the plane, m = the number of the window's taps outside it; those
+ * count as u = 0 with weight 1, the reference's zero border:
+ *   ubar = S(g u) / (S(g) + m);  vbar = S(g v) / (S(g) + m)
+ *   c = (Ix ubar + Iy vbar + It') / (alpha^2 + Ix^2 + Iy^2)
+ *   u = ubar - Ix c;  v = vbar - Iy c
+ * g = 1 everywhere gives the plain iteration's values (within rounding, not
+ * the same bits).  With the mode on `window` must be 3 or 5 (odd windows,
+ * centred anchor); any other is HSFLOW_ERR_ARG before any device work.
+ * Schedule per level, `warps` times: gradients around (u, v); g from (u, v);
+ * `iters` weighted iterations warm-started from (u, v), g fixed; the median
+ * if asked for.  At the first warp of the coarsest level the flow is zero and
+ * g = 1: with levels = 1, warps = 1 the mode changes nothing but rounding.
+ * Recommended: lambda 0.3 with alpha ~ 100, the 5x5 median and 4 warps.  A
+ * true occlusion (ground one frame does not show) is not repaired by it.
+ * hsflow_flow, hsflow_flow_bgr, hsflow_flow_pyramid, hsflow_flow_multi keep
+ * the reference's semantics whatever the context's setting. */
+#define HSFLOW_HAS_SMOOTHNESS 1
+#define HSFLOW_SMOOTH_QUADRATIC 0   /* default: the solves above              */
+#define HSFLOW_SMOOTH_FLOW_DRIVEN 1
+
+typedef struct hsflow_smoothness {
+    int mode; /* 0 = quadratic */
+    float lambda;
+} hsflow_smoothness;
+
+/* The weights alone: (u, v) dense f32 [batch][rows][cols] in solver units ->
+ * g, f32 of the same shape; one launch, no workspace.  g must not overlap u
+ * or v.  Stream-ordered, never allocates or synchronises, capturable; all
+ * arguments are checked before any device work. */
+int hsflow_flow_diffusivity_device(const float *u, const float *v, int rows, int cols, int batch,
+                                   float lambda, float *g, void *stream);
+/* `iters` weighted iterations warm-started from (u, v), window 3 or 5.  The
+ * gradients are the f32 planes of `workspace` (hsflow_workspace_bytes), the
+ * state hsflow_warp_gradients_device leaves.  g, u and v must not overlap the
+ * workspace or each other.  The result has the same bits however `iters` is
+ * split into calls and whatever hsflow_set_iters_per_launch says.  A batch is
+ * split over side streams as hsflow_jacobi_device's is (same bits). */
+int hsflow_jacobi_weighted_device(int rows, int cols, int batch, int window, int iters,
+                                  float alpha, const float *g, float *u, float *v,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* The four *_pf_device solves with `const hsflow_smoothness *sm` after `pf`.
+ * sm == NULL or sm->mode == 0 launches exactly what the *_pf_device call
+ * launches and returns its bits (those calls are the sm = NULL case of
+ * these).  The weights live in a plane of the solve's workspace that a warped
+ * solve does not otherwise use, so the workspace sizes are the *_pf_device
+ * calls'.  The result is bit for bit what the public pieces give one after
+ * the other (pyramid, upflow, warp gradients, diffusivity, weighted
+ * iterations, median). */
+int hsflow_flow_warped_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float *u, float *v,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_bidir_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                int batch, int levels, int warps, int median, int window,
+                                int iters, float alpha, float rel, float abs_thr, float *uf,
+                                float *vf, float *ub, float *vb, float *err_f, uint8_t *mask_f,
+                                uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                uint32_t *counts_b, const hsflow_prefilter *pf,
+                                const hsflow_smoothness *sm, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, void *out, int dtype_out,
+                                 uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                 const hsflow_smoothness *sm, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_bgr_sm_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int warps, int median, int window,
+                                     int iters, float alpha, float rel, float abs_thr,
+                                     const float *times, int nt, void *out, int dtype_out,
+                                     uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                     const hsflow_smoothness *sm, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
+/* The context's smoothness term: the host-buffer, blocking calls
+ * hsflow_flow_warped*, hsflow_flow_bidir*, hsflow_flow_interp and
+ * hsflow_flow_interp_bgr honour it and then equal their *_sm_device form bit
+ * for bit.  NULL or mode 0: quadratic, the default.  A bad setting is
+ * HSFLOW_ERR_ARG and leaves the old one in place (the window is checked by the
+ * call that solves).  hsflow_ctx_smoothness reads the setting back. */
+int hsflow_ctx_set_smoothness(hsflow_ctx *ctx, const hsflow_smoothness *sm);
+int hsflow_ctx_smoothness(const hsflow_ctx *ctx, hsflow_smoothness *sm);
 
 /* ---- host utilities on the path to the hot loop ------------------------ */
 

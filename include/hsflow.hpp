@@ -85,6 +85,16 @@ class Context {
         check(hsflow_ctx_prefilter(ctx_, &pf));
         return pf;
     }
+    // The smoothness term of the same solves (hsflow.h, hsflow_ctx_set_smoothness):
+    // HSFLOW_SMOOTH_FLOW_DRIVEN weights each tap of the window mean by a
+    // diffusivity of the current flow, which keeps motion boundaries sharp;
+    // nullptr or mode 0 = quadratic (default).  windowSize must then be 3 or 5.
+    void setSmoothness(const hsflow_smoothness *sm) { check(hsflow_ctx_set_smoothness(ctx_, sm)); }
+    hsflow_smoothness smoothness() const {
+        hsflow_smoothness sm{};
+        check(hsflow_ctx_smoothness(ctx_, &sm));
+        return sm;
+    }
 
   private:
     hsflow_ctx *ctx_ = nullptr;
@@ -157,6 +167,8 @@ class HornSchunck {
     // steps, fades, flicker), set on the context for this call; nullptr
     // leaves the context's own setting (setPrefilter; off by default).
     void setPrefilter(const hsflow_prefilter *pf) { ctx().setPrefilter(pf); }
+    // the flow-driven smoothness term for the same methods (Context::setSmoothness)
+    void setSmoothness(const hsflow_smoothness *sm) { ctx().setSmoothness(sm); }
     void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                        int warps, std::vector<double> &u, std::vector<double> &v,
                        int median = 0, const hsflow_prefilter *prefilter = nullptr) {
