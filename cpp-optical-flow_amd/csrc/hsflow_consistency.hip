@@ -5,9 +5,9 @@
 //     pair, with (uf, vf) the flow under test and (ub, vb) the opposite one
 //     (solver units: 8 px per unit, as KW):
 //       dx, dy   = 8 uf, 8 vf clamped to [-cols, cols] / [-rows, rows]
-//                  (KW's split_disp: clamped as floats, NaN -> lower bound);
+//                  (clamped as floats, NaN -> lower bound);
 //       ubw, vbw = ub, vb sampled bilinearly at (y + dy, x + dx), taps
-//                  clamped to the plane, KW's lerp order;
+//                  clamped to the plane: the sampler KW uses (hsflow_sampler.h);
 //       su, sv   = uf + ubw, vf + vbw
 //       d2       = 64 (su^2 + sv^2)                        px^2
 //       mag      = 64 ((uf^2 + vf^2) + (ubw^2 + vbw^2))
@@ -37,39 +37,14 @@
 #include <algorithm>
 
 #include "hsflow_internal.h"
+#include "hsflow_sampler.h"
 
 namespace hsflow {
 namespace {
 
-// KW's displacement split (hsflow_warp.hip), which also returns the clamped
-// float for the frame test: d (pixels) along an axis of length n is clamped
-// to [-n, n] while still a float, so NaN (-> -n), +-inf and huge flows never
-// reach the float -> int conversion and every tap index stays in the plane.
-__device__ __forceinline__ int split_disp(float &d, int n, float &frac) {
-    d = fminf(fmaxf(d, -(float)n), (float)n);
-    const float fl = floorf(d);
-    frac = d - fl;
-    return (int)fl;
-}
-
-__device__ __forceinline__ int clampi(int p, int len) { return min(max(p, 0), len - 1); }
-
-// KW's bilinear sample: top, bottom, then vertical; exact at fx = fy = 0
-__device__ __forceinline__ float bilerp(const float *top, const float *bot, int xa, int xb,
-                                        float fx, float fy) {
-    const float ta = top[xa], tb = top[xb], ba = bot[xa], bb = bot[xb];
-    const float t = ta + fx * (tb - ta);
-    const float w = ba + fx * (bb - ba);
-    return t + fy * (w - t);
-}
+using namespace sampler;
 
 constexpr int kThreads = 1024, kPix = 4, kTile = kThreads * kPix;
-
-// value of lane `Q` of the caller's quad (DPP quad_perm broadcast)
-template <int Q>
-__device__ __forceinline__ uint32_t quad_lane(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, Q * 0x55, 0xf, 0xf, true);
-}
 
 // grid (blocks per pair, batch); pack_mask: the mask's base is 4-byte aligned
 __global__ __launch_bounds__(kThreads) void hs_flow_consistency_kernel(
@@ -96,28 +71,16 @@ __global__ __launch_bounds__(kThreads) void hs_flow_consistency_kernel(
             // every lane computes (a pixel outside the plane on its nearest
             // one): the quad exchange below needs all lanes active
             const int p = clampi(pk, plane);
-            // y = p / cols from the f32 quotient, off by at most one: its
-            // relative error is 3 ulp and y < 2^18 rows (kMaxRows)
-            int y = (int)((float)p * inv_cols);
-            int x = p - y * cols;
-            if (x < 0) x += cols, --y;
-            else if (x >= cols) x -= cols, ++y;
+            const XY q = pixel_xy(p, cols, inv_cols);
+            const int x = q.x, y = q.y;
             const float u = puf[p], v = pvf[p];
-            float dx = 8.0f * u, dy = 8.0f * v, fx, fy;
-            const int ix = split_disp(dx, cols, fx);
-            const int iy = split_disp(dy, rows, fy);
-            // |ix| <= cols, |iy| <= rows: the sums cannot overflow
-            const int xa = clampi(x + ix, cols), xb = clampi(x + ix + 1, cols);
-            const size_t top = (size_t)clampi(y + iy, rows) * cols;
-            const size_t bot = (size_t)clampi(y + iy + 1, rows) * cols;
-            const float ubw = bilerp(pub + top, pub + bot, xa, xb, fx, fy);
-            const float vbw = bilerp(pvb + top, pvb + bot, xa, xb, fx, fy);
+            bool in;
+            int nearest;  // unused
+            const Taps tp = sample_taps(rows, cols, x, y, u, v, in, nearest);
+            const float ubw = sample_plane(pub, cols, tp), vbw = sample_plane(pvb, cols, tp);
             const float su = u + ubw, sv = v + vbw;
             const float d2 = 64.0f * (su * su + sv * sv);
             const float mag = 64.0f * ((u * u + v * v) + (ubw * ubw + vbw * vbw));
-            const float tx = (float)x + dx, ty = (float)y + dy;
-            const bool in = tx >= -0.5f && tx <= (float)cols - 0.5f && ty >= -0.5f &&
-                            ty <= (float)rows - 0.5f;
             // d2 <= FLT_MAX: a sum that overflows f32 fails the test, as it
             // does in exact arithmetic (inf <= inf would pass it)
             const bool ok = d2 <= rel * mag + abs_thr && d2 <= 3.402823466e38f;
@@ -127,6 +90,10 @@ __global__ __launch_bounds__(kThreads) void hs_flow_consistency_kernel(
             c2 += valid && cls == 2u;
             if (err && valid) err[base + p] = sqrtf(d2);
             if (mask) {  // uniform
+                // store_quad_u8 with the alignment decided on the host: base +
+                // q0 is a multiple of four here, so only the mask's base counts
+                // (the sampler's per-quad test costs KC 11 VGPRs and 2 % at
+                // batch 8)
                 const uint32_t quad = cls | quad_lane<1>(cls) << 8 | quad_lane<2>(cls) << 16 |
                                       quad_lane<3>(cls) << 24;
                 const int q0 = pk - (t & 3);  // the quad's first pixel

@@ -8,18 +8,18 @@
 //     (y + 8 v, x + 8 u): KR's positions and weights once per pixel, its three
 //     lerps per channel.  oof as KR's, one byte per pixel.
 //
-//  KIC hs_frame_interp_bgr_kernel  per output pixel exactly what KI does, once
-//     -- (u0, v0), (u1, v1) of each time, the clamped displacement split, the
-//     four tap positions and two fractions per source, in0, in1, n0, n1, wt,
-//     flags and the trusted count -- then KI's three lerps and KI's blend on
-//     each of the three channels.  The arithmetic is hsflow_sampler.h's, which
-//     KR and KI use too, so channel c of the result has the bits KI gives the
+//  KIC hs_frame_interp_kernel<BgrFrame>  KI's kernel (hsflow_sampler.h) with a
+//     pixel of three channels: per output pixel what KI does, once -- (u0, v0),
+//     (u1, v1) of each time, the clamped displacement split, the four tap
+//     positions and two fractions per source, in0, in1, n0, n1, wt, flags and
+//     the trusted count -- then KI's three lerps and KI's blend on each of the
+//     three channels, so channel c of the result has the bits KI gives the
 //     plane bgr[..., c].
 //
-// Thread map: KI's (256 threads, tiles of 512 consecutive pixels of a pair's
-// plane, thread t the pixels t and t + 256, flows loaded once and reused over
-// the times, the grid capped per CU and striding over the tiles, one global
-// atomic per block and time).
+// Thread map: KI's, the same text (256 threads, tiles of 512 consecutive pixels
+// of a pair's plane, thread t the pixels t and t + 256, flows loaded once and
+// reused over the times, the grid capped per CU and striding over the tiles,
+// one global atomic per block and time).
 // Loads: a tap is three bytes at a data-dependent address.  The two
 // horizontally adjacent taps of a row are six consecutive bytes unless the
 // pair is clamped at a frame edge (xb == xa); `Wide` reads them as one
@@ -36,7 +36,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
 #include <atomic>
 
 #include "hsflow_internal.h"
@@ -49,9 +48,7 @@ using namespace sampler;
 
 std::atomic<int> g_wide_loads{0};
 
-struct Bgr {
-    float c[3];
-};
+using Bgr = Pixel<3>;
 
 __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) {
     uint32_t v;
@@ -149,97 +146,28 @@ __global__ __launch_bounds__(256) void hs_warp_image_bgr_kernel(
     if (oof && valid) oof[o] = in ? 0 : 1;
 }
 
-// ---- KIC
-constexpr int kThreads = 256, kPix = 2, kTile = kThreads * kPix;
-// 83 VGPRs (84 with wide loads): five waves per SIMD, five blocks per CU
-constexpr int kBlocksPerCu = 5;
-
-// grid (blocks per pair, batch)
+// ---- KIC: hs_frame_interp_kernel on a BGR frame
 template <bool Wide>
-__global__ __launch_bounds__(kThreads) void hs_frame_interp_bgr_kernel(
-    const uint8_t *__restrict__ I0, const uint8_t *__restrict__ I1, const float *__restrict__ uf,
-    const float *__restrict__ vf, const float *__restrict__ ub, const float *__restrict__ vb,
-    const uint8_t *__restrict__ mask_f, const uint8_t *__restrict__ mask_b, int rows, int cols,
-    InterpTimes times, int nt, void *__restrict__ out, int out_u8, uint8_t *__restrict__ flags,
-    uint32_t *__restrict__ trusted) {
-    __shared__ uint32_t block_trusted[kInterpMaxTimes];
-    const int plane = rows * cols;  // <= 2^29 - 1
-    const size_t base = (size_t)blockIdx.y * plane;
-    const int ntiles = (plane + kTile - 1) / kTile;
-    const float inv_cols = 1.0f / (float)cols;
-    const uint8_t *p0 = I0 + base * 3, *p1 = I1 + base * 3;
-    const uint8_t *mf = mask_f ? mask_f + base : nullptr;
-    const uint8_t *mb = mask_b ? mask_b + base : nullptr;
-    const int t = threadIdx.x;
-    if (t < kInterpMaxTimes) block_trusted[t] = 0;
-    __syncthreads();
-
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        int pk[kPix], x[kPix], y[kPix];
-        float fu[kPix], fv[kPix], bu[kPix], bv[kPix];
-#pragma unroll
-        for (int k = 0; k < kPix; ++k) {
-            pk[k] = tile * kTile + k * kThreads + t;
-            // every lane computes (a pixel past the plane on its last one):
-            // the quad exchange needs all lanes active
-            const int p = min(pk[k], plane - 1);
-            // y = p / cols from the f32 quotient, off by at most one (as KI)
-            int yy = (int)((float)p * inv_cols);
-            int xx = p - yy * cols;
-            if (xx < 0) xx += cols, --yy;
-            else if (xx >= cols) xx -= cols, ++yy;
-            x[k] = xx, y[k] = yy;
-            fu[k] = uf[base + p], fv[k] = vf[base + p];
-            bu[k] = ub[base + p], bv[k] = vb[base + p];
-        }
-        for (int ti = 0; ti < nt; ++ti) {
-            const float tt = times.t[ti];
-            const float s = 1.0f - tt, a = s * tt, b = tt * tt, c = s * s;
-            const size_t obase = ((size_t)blockIdx.y * nt + ti) * plane;
-            uint32_t good = 0;
-#pragma unroll
-            for (int k = 0; k < kPix; ++k) {
-                const bool valid = pk[k] < plane;
-                const float u0 = b * bu[k] - a * fu[k], v0 = b * bv[k] - a * fv[k];
-                const float u1 = c * fu[k] - a * bu[k], v1 = c * fv[k] - a * bv[k];
-                bool in0, in1;
-                int n0, n1;
-                const Taps t0 = sample_taps(rows, cols, x[k], y[k], u0, v0, in0, n0);
-                const Taps t1 = sample_taps(rows, cols, x[k], y[k], u1, v1, in1, n1);
-                const Bgr s0 = sample_bgr<Wide>(p0, cols, t0);
-                const Bgr s1 = sample_bgr<Wide>(p1, cols, t1);
-                const float wt = blend_weight(in0, in1, tt);
-                Bgr o;
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) o.c[ch] = blend(wt, s0.c[ch], s1.c[ch]);
-                uint32_t fl = (in0 ? 0u : 1u) | (in1 ? 0u : 2u);
-                if (mf) fl |= mf[n0] != 0 ? 4u : 0u;  // uniform
-                if (mb) fl |= mb[n1] != 0 ? 8u : 0u;  // uniform
-                good += valid && fl == 0u;
-                const int q0 = pk[k] - (t & 3);  // the quad's first pixel, >= 0
-                if (out_u8) {                    // uniform
-                    store_quad_bgr_u8((uint8_t *)out + (obase + (size_t)q0) * 3, q0 + 3 < plane,
-                                      valid, pack_u8(o), t);
-                } else if (valid) {
-                    reinterpret_cast<Float3 *>(out)[obase + pk[k]] =
-                        Float3{{o.c[0], o.c[1], o.c[2]}};
-                }
-                if (flags)  // uniform
-                    store_quad_u8(flags + obase, pk[k], q0, plane, valid, fl, t);
-            }
-            if (trusted) {  // uniform: butterfly sum, one LDS atomic per wave
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) good += __shfl_xor(good, off, 64);
-                if ((t & 63) == 0 && good) atomicAdd(&block_trusted[ti], good);
-            }
-        }
+struct BgrFrame {
+    using Elem = uint8_t;
+    static constexpr int kChannels = 3;
+    using Px = Bgr;
+    // 84 VGPRs with wide loads: five waves per SIMD, five blocks per CU (80
+    // with byte loads, which would let a sixth in; one cap for both forms)
+    static constexpr int kBlocksPerCu = 5;
+    static __device__ __forceinline__ Bgr sample(const uint8_t *__restrict__ img, int cols,
+                                                 const Taps &t) {
+        return sample_bgr<Wide>(img, cols, t);
     }
-    if (!trusted) return;  // uniform over the grid
-    __syncthreads();
-    // per block: one ordinary global atomic per time with trusted pixels
-    if (t < nt && block_trusted[t])
-        atomicAdd(trusted + (size_t)blockIdx.y * nt + t, block_trusted[t]);
-}
+    static __device__ __forceinline__ void store_f32(void *out, size_t px, const Bgr &o) {
+        reinterpret_cast<Float3 *>(out)[px] = Float3{{o.c[0], o.c[1], o.c[2]}};
+    }
+    static __device__ __forceinline__ void store_u8(void *out, size_t obase, int, int q0,
+                                                    bool whole, bool valid, const Bgr &o, int lane) {
+        store_quad_bgr_u8((uint8_t *)out + (obase + (size_t)q0) * 3, whole, valid, pack_u8(o),
+                          lane);
+    }
+};
 
 }  // namespace
 
@@ -264,24 +192,10 @@ hipError_t launch_frame_interp_bgr(const uint8_t *I0, const uint8_t *I1, int row
                                    const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
                                    const float *times, int nt, void *out, bool out_u8,
                                    uint8_t *flags, uint32_t *trusted, hipStream_t s) {
-    if (nt < 1 || nt > kInterpMaxTimes) return hipErrorInvalidValue;
-    InterpTimes tm{};
-    for (int k = 0; k < nt; ++k) tm.t[k] = times[k];
-    const size_t plane = (size_t)rows * cols;
-    const int ntiles = (int)((plane + kTile - 1) / kTile);
-    // kBlocksPerCu blocks of four waves are resident per CU (the registers of
-    // either instantiation); more blocks would wait for a slot and only add
-    // atomics on the counts, which share a cache line
-    const int cap = std::max(1, (kBlocksPerCu * device_cus() + batch - 1) / batch);
-    dim3 blk(kThreads, 1, 1), grd(std::min(ntiles, cap), batch, 1);
-    const int u8 = out_u8 ? 1 : 0;
-    if (g_wide_loads.load())
-        hipLaunchKernelGGL(hs_frame_interp_bgr_kernel<true>, grd, blk, 0, s, I0, I1, uf, vf, ub,
-                           vb, mask_f, mask_b, rows, cols, tm, nt, out, u8, flags, trusted);
-    else
-        hipLaunchKernelGGL(hs_frame_interp_bgr_kernel<false>, grd, blk, 0, s, I0, I1, uf, vf, ub,
-                           vb, mask_f, mask_b, rows, cols, tm, nt, out, u8, flags, trusted);
-    return hipGetLastError();
+    const auto launch = g_wide_loads.load() ? launch_frame_interp_as<BgrFrame<true>>
+                                            : launch_frame_interp_as<BgrFrame<false>>;
+    return launch(I0, I1, rows, cols, batch, uf, vf, ub, vb, mask_f, mask_b, times, nt, out,
+                  out_u8, flags, trusted, s);
 }
 
 }  // namespace hsflow

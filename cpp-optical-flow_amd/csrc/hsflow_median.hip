@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hsflow_frame_types.h"
 #include "hsflow_internal.h"
 
 #define HSFLOW_NET_FN __device__ __forceinline__
@@ -45,8 +46,6 @@ __device__ __forceinline__ uint32_t to_key(uint32_t bits) {
 __device__ __forceinline__ uint32_t from_key(uint32_t key) {
     return key ^ (~(uint32_t)((int32_t)key >> 31) | 0x80000000u);
 }
-
-__device__ __forceinline__ int clampi(int p, int len) { return min(max(p, 0), len - 1); }
 
 constexpr int kCols = 64, kWaves = 4, kRun = 4;
 

@@ -44,6 +44,7 @@
 
 #include <algorithm>
 
+#include "hsflow_frame_types.h"
 #include "hsflow_internal.h"
 
 namespace hsflow {
@@ -52,10 +53,6 @@ namespace {
 struct Weights {
     float w[kPrefilterMaxRadius + 1];
 };
-
-// double for CV_64FC1 frames, else float (as K1 and KW)
-template <typename T> struct BlurMath { using type = float; };
-template <> struct BlurMath<double> { using type = double; };
 
 // reflect-101 of any index: period 2 (n - 1), n = 1 -> 0
 __device__ __forceinline__ int fold101(int p, int n) {
@@ -113,7 +110,7 @@ __global__ __launch_bounds__(TW + 64) void hs_prefilter_kernel(const T *__restri
                                                                int cols, Weights W, float eps,
                                                                float scale, int seg_rows,
                                                                float *__restrict__ out) {
-    using A = typename BlurMath<T>::type;
+    using A = typename FrameMath<T>::type;
     extern __shared__ __align__(8) unsigned char lds_raw[];
     A *lds = (A *)lds_raw;
     constexpr bool kNorm = MODE == 2;
@@ -214,7 +211,7 @@ __global__ __launch_bounds__(TW + 64) void hs_prefilter_kernel(const T *__restri
 template <typename T, int TW, int R>
 void launch_r(const void *I, int rows, int cols, int batch, int mode, int r, const Weights &W,
               float eps, float scale, float *out, hipStream_t s) {
-    using A = typename BlurMath<T>::type;
+    using A = typename FrameMath<T>::type;
     const int D = mode == 2 ? r : 0;
     const size_t lds = sizeof(A) * (size_t)lds_elems(TW, r, mode == 2);
     // segments: about four blocks per compute unit, none shorter than its own
@@ -269,13 +266,13 @@ hipError_t launch_prefilter(const void *I, int dtype_in, int rows, int cols, int
         return hipErrorInvalidValue;
     Weights W{};
     for (int i = 0; i <= radius; ++i) W.w[i] = weights[i];
-    switch (dtype_in) {
-    case 0: launch_t<uint8_t, 128>(I, rows, cols, batch, mode, radius, W, eps, scale, out, s); break;
-    case 1: launch_t<float, 128>(I, rows, cols, batch, mode, radius, W, eps, scale, out, s); break;
-    case 2: launch_t<double, 64>(I, rows, cols, batch, mode, radius, W, eps, scale, out, s); break;
-    case 3: launch_t<_Float16, 128>(I, rows, cols, batch, mode, radius, W, eps, scale, out, s); break;
-    default: return hipErrorInvalidValue;
-    }
+    const bool known = dispatch_frame_type(dtype_in, [&](auto t) {
+        using T = decltype(t);
+        // f64 math: half the strip's width in about the same LDS
+        constexpr int TW = sizeof(typename FrameMath<T>::type) == 8 ? 64 : 128;
+        launch_t<T, TW>(I, rows, cols, batch, mode, radius, W, eps, scale, out, s);
+    });
+    if (!known) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -34,14 +34,13 @@
 #include <algorithm>
 
 #include "hsflow_device.h"
+#include "hsflow_frame_types.h"
 #include "hsflow_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace hsflow {
 namespace {
-
-__device__ __forceinline__ int clampi(int p, int len) { return min(max(p, 0), len - 1); }
 
 // grid (ceil(cols / 64), ceil(rows / 4), batch), block (64, 4)
 __global__ __launch_bounds__(256) void hs_diffusivity_kernel(const float *__restrict__ u,

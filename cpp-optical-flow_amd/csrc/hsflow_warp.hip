@@ -7,8 +7,9 @@
 //       gx, gy = 3x3 Sobel of I0, reflect-101 -- K1's arithmetic (sobel_at),
 //                so the planes equal K1's bit for bit;
 //       I1w    = I1 sampled bilinearly at (y + 8 v0, x + 8 u0), border
-//                replicated; 8 is the gain of the reference's unnormalised
-//                Sobel (hornSchunck.cpp:27-28): one unit of (u, v) is 8 px;
+//                replicated: the sampler (hsflow_sampler.h); 8 is the gain of
+//                the reference's unnormalised Sobel (hornSchunck.cpp:27-28):
+//                one unit of (u, v) is 8 px;
 //       gt'    = ((I1w - I0) - gx u0) - gy v0.
 //     The Jacobi kernels then run hornSchunck.cpp:56-74 unchanged from these
 //     f32 planes (flags[pair] != 0), warm-started from (u0, v0): the update
@@ -22,25 +23,22 @@
 #include <stdint.h>
 
 #include "hsflow_internal.h"
+#include "hsflow_sampler.h"
 
 namespace hsflow {
 namespace {
 
-// K1's per-pixel arithmetic (hsflow_kernels.hip: reflect101, GradMath,
-// sobel_at), restated here term for term: that file and its headers are the
-// Jacobi kernels' sources, whose md5 the committed counter profiles are
-// tied to (bench.py kernel_source_md5), so they stay untouched.  The sums
-// associate as K1's do; tests/test_warped.py holds the two bit for bit.
+// K1's per-pixel arithmetic (hsflow_kernels.hip: reflect101, sobel_at; its
+// GradMath is FrameMath), restated here term for term: that file and its
+// headers are the Jacobi kernels' sources, whose md5 the committed counter
+// profiles are tied to (bench.py kernel_source_md5), so they stay untouched.
+// The sums associate as K1's do; tests/test_warped.py holds the two bit for bit.
 __device__ __forceinline__ int reflect101(int p, int len) {
     // OpenCV borderInterpolate(BORDER_REFLECT_101) for |overshoot| <= 1.
     if (len == 1) return 0;
     p = p < 0 ? -p : p;
     return p >= len ? 2 * (len - 1) - p : p;
 }
-
-// double for CV_64FC1 frames (Sobel sums in float64, one rounding), else float
-template <typename T> struct GradMath { using type = float; };
-template <> struct GradMath<double> { using type = double; };
 
 // Sobel dx, dy (ksize 3, reflect-101) of frame a at (r, c) and its centre
 // pixel z_0, hornSchunck.cpp:27-28
@@ -59,26 +57,13 @@ __device__ __forceinline__ void sobel_at(const T *a, int rows, int cols, int r, 
     dy = (p_m - m_m) + (F)2 * (p_0 - m_0) + (p_p - m_p);
 }
 
-// Displacement d (pixels) along an axis of length n: clamped to [-n, n] while
-// still a float, so NaN (-> -n), +-inf and huge flows never reach the
-// float -> int conversion and every tap index below stays inside the plane.
-// Returns floor(d); frac = d - floor(d), exact in f32.
-__device__ __forceinline__ int split_disp(float d, int n, float &frac) {
-    d = fminf(fmaxf(d, -(float)n), (float)n);
-    const float fl = floorf(d);
-    frac = d - fl;
-    return (int)fl;
-}
-
-__device__ __forceinline__ int clampi(int p, int len) { return min(max(p, 0), len - 1); }
-
 // block 64 x 4, one pixel per thread; grid (ceil(cols/64), ceil(rows/4), batch)
 template <typename T>
 __global__ __launch_bounds__(256) void hs_warp_gradients_kernel(
     const T *__restrict__ I0, const T *__restrict__ I1, const float *__restrict__ u0,
     const float *__restrict__ v0, int rows, int cols, float *__restrict__ gx,
     float *__restrict__ gy, float *__restrict__ gt, uint32_t *__restrict__ flags) {
-    using F = typename GradMath<T>::type;
+    using F = typename FrameMath<T>::type;
     // the pair's Jacobi passes read the f32 planes, never the packed word
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0)
         flags[blockIdx.z] = 1u;
@@ -93,18 +78,11 @@ __global__ __launch_bounds__(256) void hs_warp_gradients_kernel(
     sobel_at(a, rows, cols, y, x, dx, dy, z_0);
 
     const float u = u0[o], v = v0[o];
-    float fx, fy;
-    const int ix = split_disp(8.0f * u, cols, fx);
-    const int iy = split_disp(8.0f * v, rows, fy);
-    // |ix| <= cols, |iy| <= rows: the sums cannot overflow
-    const int xa = clampi(x + ix, cols), xb = clampi(x + ix + 1, cols);
-    const T *top = b + (size_t)clampi(y + iy, rows) * cols;
-    const T *bot = b + (size_t)clampi(y + iy + 1, rows) * cols;
-    const F ta = (F)top[xa], tb = (F)top[xb], ba = (F)bot[xa], bb = (F)bot[xb];
-    // exact at fx = fy = 0: zero flow gives I1w = I1 and gt' = I1 - I0
-    const F t = ta + (F)fx * (tb - ta);
-    const F w = ba + (F)fx * (bb - ba);
-    const F I1w = t + (F)fy * (w - t);
+    bool in;
+    int nearest;  // neither is used: dead code
+    const sampler::Taps t = sampler::sample_taps(rows, cols, x, y, u, v, in, nearest);
+    // exact at zero flow: I1w = I1 and gt' = I1 - I0
+    const F I1w = sampler::sample_plane(b, cols, t);
     const F gtw = ((I1w - z_0) - dx * (F)u) - dy * (F)v;
 
     gx[o] = (float)dx;
@@ -127,13 +105,10 @@ hipError_t launch_warp_gradients(const void *I0, const void *I1, int dtype_in, i
                                  int cols, int batch, const float *u0, const float *v0,
                                  float *gx, float *gy, float *gt, uint32_t *flags,
                                  hipStream_t s) {
-    switch (dtype_in) {
-    case 0: launch_t<uint8_t>(I0, I1, u0, v0, rows, cols, batch, gx, gy, gt, flags, s); break;
-    case 1: launch_t<float>(I0, I1, u0, v0, rows, cols, batch, gx, gy, gt, flags, s); break;
-    case 2: launch_t<double>(I0, I1, u0, v0, rows, cols, batch, gx, gy, gt, flags, s); break;
-    case 3: launch_t<_Float16>(I0, I1, u0, v0, rows, cols, batch, gx, gy, gt, flags, s); break;
-    default: return hipErrorInvalidValue;
-    }
+    const bool known = dispatch_frame_type(dtype_in, [&](auto t) {
+        launch_t<decltype(t)>(I0, I1, u0, v0, rows, cols, batch, gx, gy, gt, flags, s);
+    });
+    if (!known) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
