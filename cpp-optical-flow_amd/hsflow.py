@@ -19,6 +19,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes
+import math
 import os
 import subprocess
 
@@ -59,42 +60,6 @@ MEDIAN_SIZES = (3, 5)
 MAX_TIMES = 16
 FLAG_I0_OUT, FLAG_I1_OUT, FLAG_FWD_FAILED, FLAG_BWD_FAILED = 1, 2, 4, 8
 
-# every symbol include/hsflow.h declares
-EXPORTS = (
-    "hsflow_version", "hsflow_status_string", "hsflow_create", "hsflow_destroy",
-    "hsflow_last_error", "hsflow_stream", "hsflow_flow", "hsflow_gradients",
-    "hsflow_workspace_bytes", "hsflow_flow_device", "hsflow_gradients_device",
-    "hsflow_jacobi_device", "hsflow_set_iters_per_launch", "hsflow_iters_per_launch",
-    "hsflow_bgr_to_gray", "hsflow_synth_pair", "hsflow_set_max_streams",
-    "hsflow_pyramid_level_size", "hsflow_pyramid_workspace_bytes",
-    "hsflow_flow_pyramid_device", "hsflow_flow_pyramid", "hsflow_bgr_to_gray_device",
-    "hsflow_flow_bgr", "hsflow_pyramid_build_device", "hsflow_upflow_device",
-    "hsflow_set_jacobi_kernel", "hsflow_build_flags", "hsflow_flow_multi",
-    "hsflow_download_device", "hsflow_jacobi_kernel_name", "hsflow_set_strip_rows",
-    "hsflow_max_streams", "hsflow_set_output_hugepages", "hsflow_strip_seg_rows",
-    "hsflow_flow_multi_release", "hsflow_warp_gradients_device",
-    "hsflow_flow_warped_device", "hsflow_flow_warped",
-    "hsflow_flow_consistency_device", "hsflow_flow_bidir_workspace_bytes",
-    "hsflow_flow_bidir_device", "hsflow_flow_bidir",
-    "hsflow_flow_median_device", "hsflow_flow_warped_median_device",
-    "hsflow_flow_warped_median", "hsflow_flow_bidir_median_device",
-    "hsflow_flow_bidir_median",
-    "hsflow_warp_image_device", "hsflow_frame_interp_device",
-    "hsflow_flow_interp_workspace_bytes", "hsflow_flow_interp_device", "hsflow_flow_interp",
-    "hsflow_set_first_pass_fusion", "hsflow_first_pass_fusion",
-    "hsflow_first_pass_launches",
-    "hsflow_warp_image_bgr_device", "hsflow_frame_interp_bgr_device",
-    "hsflow_flow_interp_bgr_workspace_bytes", "hsflow_flow_interp_bgr_device",
-    "hsflow_flow_interp_bgr", "hsflow_set_interp_bgr_loads",
-    "hsflow_prefilter_device", "hsflow_prefilter_planes_bytes",
-    "hsflow_flow_warped_pf_device", "hsflow_flow_bidir_pf_device",
-    "hsflow_flow_interp_pf_device", "hsflow_flow_interp_bgr_pf_device",
-    "hsflow_ctx_set_prefilter", "hsflow_ctx_prefilter",
-    "hsflow_flow_diffusivity_device", "hsflow_jacobi_weighted_device",
-    "hsflow_flow_warped_sm_device", "hsflow_flow_bidir_sm_device",
-    "hsflow_flow_interp_sm_device", "hsflow_flow_interp_bgr_sm_device",
-    "hsflow_ctx_set_smoothness", "hsflow_ctx_smoothness",
-)
 
 # modes of the brightness-robust prefilter (HSFLOW_PREFILTER_*)
 PREFILTER_NONE, PREFILTER_HIGHPASS, PREFILTER_NORMALIZE = 0, 1, 2
@@ -113,22 +78,13 @@ class Prefilter(collections.namedtuple("Prefilter", "mode sigma eps scale")):
     scale * v / (sqrt(G*(v v)) + eps) (include/hsflow.h).  It lowers the
     contrast the solver sees: use alpha ~ 100 with median=5."""
     __slots__ = ()
+    _C, _GET, _SET = _CPrefilter, "hsflow_ctx_prefilter", "hsflow_ctx_set_prefilter"
 
     def __new__(cls, mode, sigma=4.0, eps=4.0, scale=32.0):
         return super().__new__(cls, int(mode), float(sigma), float(eps), float(scale))
 
     def _c(self):
-        return _CPrefilter(self.mode, self.sigma, self.eps, self.scale)
-
-
-def _pf_arg(prefilter):
-    """(keep-alive struct, pointer or None) of a Prefilter / None."""
-    if prefilter is None:
-        return None, None
-    if not isinstance(prefilter, Prefilter):
-        prefilter = Prefilter(*prefilter)
-    c = prefilter._c()
-    return c, ctypes.byref(c)
+        return self._C(*self)
 
 
 # smoothness terms of the warped solves (HSFLOW_SMOOTH_*)
@@ -147,21 +103,23 @@ class Smoothness(collections.namedtuple("Smoothness", "mode lam")):
     px per px, at which the weight is 1/sqrt(2); 0.1 .. 0.3.  The window must
     be 3 or 5.  Use alpha ~ 100 with median=5 and 4 warps."""
     __slots__ = ()
+    _C, _GET, _SET = _CSmoothness, "hsflow_ctx_smoothness", "hsflow_ctx_set_smoothness"
 
     def __new__(cls, mode=SMOOTH_FLOW_DRIVEN, lam=0.3):
         return super().__new__(cls, int(mode), float(lam))
 
     def _c(self):
-        return _CSmoothness(self.mode, self.lam)
+        return self._C(*self)
 
 
-def _sm_arg(smoothness):
-    """(keep-alive struct, pointer or None) of a Smoothness / None."""
-    if smoothness is None:
+def _option(kind, value):
+    """(keep-alive struct, pointer or None) of an option of `kind` (Prefilter
+    or Smoothness): an instance, a plain tuple of its fields, or None."""
+    if value is None:
         return None, None
-    if not isinstance(smoothness, Smoothness):
-        smoothness = Smoothness(*smoothness)
-    c = smoothness._c()
+    if not isinstance(value, kind):
+        value = kind(*value)
+    c = value._c()
     return c, ctypes.byref(c)
 
 
@@ -178,9 +136,124 @@ class HsflowError(RuntimeError):
         self.status = status
 
 
+def _prototypes():
+    """name -> (restype, argtypes) of every symbol include/hsflow.h declares.
+    The argument runs the entry points share are named once and the entries
+    composed from them, in the header's order."""
+    i, f, d, vp, sz = (ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
+                       ctypes.c_size_t)
+    ip, fp, vpp, text = ctypes.POINTER(i), ctypes.POINTER(f), ctypes.POINTER(vp), ctypes.c_char_p
+    pf, sm = [ctypes.POINTER(_CPrefilter)], [ctypes.POINTER(_CSmoothness)]
+    shape = [i, i, i]                              # rows, cols, batch
+    dev_pair = [vp, vp, i] + shape                 # I0, I1, dtype, rows, cols, batch
+    dev_bgr_pair = [vp, vp] + shape                # bgr0, bgr1, rows, cols, batch
+    host_pair = [vp, vp, vp, i, i, i, sz, sz]      # ctx, prev, next, dtype, rows, cols, steps
+    host_bgr_pair = [vp, vp, vp, i, i, sz, sz]     # ctx, bgr0, bgr1, rows, cols, steps
+    plain, plain_d = [i, i, f], [i, i, d]          # window, iters, alpha
+    pyramid, pyramid_d = [i] + plain, [i] + plain_d            # levels, ...
+    warped, warped_d = [i, i] + plain, [i, i] + plain_d        # levels, warps, ...
+    solve, solve_d = [i, i, i] + plain, [i, i, i] + plain_d    # levels, warps, median, ...
+    thresholds = [f, f]                            # rel, abs
+    uv, host_uv = [vp, vp], [vp, vp, i, sz]        # u, v (host: + out dtype, step)
+    flows = [vp] * 4                               # uf, vf, ub, vb
+    bidir_out = flows + [vp] * 6                   # + err, mask, counts each way
+    host_bidir_out = flows + [i, sz, vp, vp, sz, vp]   # + dtype, step, masks, step, counts
+    times_out = [fp, i, vp, i, vp, vp]             # times, n, out, out dtype, flags, trusted
+    host_times_out = [fp, i, vpp, i, sz, vpp, sz, vp]  # planes and their steps
+    tail = [vp, sz, vp]                            # workspace, bytes, stream
+    sized = (sz, shape + [i])                      # a workspace size of a shape and levels
+    return {
+        "hsflow_version": (i, []),
+        "hsflow_status_string": (text, [i]),
+        "hsflow_build_flags": (i, []),
+        "hsflow_create": (i, [vpp, i]),
+        "hsflow_destroy": (None, [vp]),
+        "hsflow_last_error": (text, [vp]),
+        "hsflow_stream": (vp, [vp]),
+        "hsflow_flow": (i, host_pair + plain_d + host_uv),
+        "hsflow_flow_multi": (i, [ip, i, i, vpp, vpp, i, i, i, sz, sz] + plain_d
+                              + [vpp, vpp, i, sz]),
+        "hsflow_flow_multi_release": (None, []),
+        "hsflow_gradients": (i, host_pair + [vp, vp, vp, i, sz]),
+        "hsflow_workspace_bytes": (sz, shape),
+        "hsflow_flow_device": (i, dev_pair + plain + uv + tail),
+        "hsflow_gradients_device": (i, dev_pair + [vp, vp, vp] + tail),
+        "hsflow_jacobi_device": (i, shape + plain + [i] + uv + tail),
+        "hsflow_set_iters_per_launch": (i, [i]),
+        "hsflow_iters_per_launch": (i, shape + [i]),
+        "hsflow_set_jacobi_kernel": (i, [i]),
+        "hsflow_set_strip_rows": (i, [i]),
+        "hsflow_jacobi_kernel_name": (text, shape + [i]),
+        "hsflow_strip_seg_rows": (i, shape + [i]),
+        "hsflow_set_max_streams": (i, [i]),
+        "hsflow_max_streams": (i, []),
+        "hsflow_set_first_pass_fusion": (i, [i]),
+        "hsflow_first_pass_fusion": (i, []),
+        "hsflow_first_pass_launches": (ctypes.c_longlong, []),
+        "hsflow_set_output_hugepages": (i, [i]),
+        "hsflow_download_device": (i, [vp, vp, sz, vp]),
+        "hsflow_pyramid_level_size": (i, [i, i, i, ip, ip]),
+        "hsflow_pyramid_workspace_bytes": sized,
+        "hsflow_flow_pyramid_device": (i, dev_pair + pyramid + uv + tail),
+        "hsflow_flow_pyramid": (i, host_pair + pyramid_d + host_uv),
+        "hsflow_pyramid_build_device": (i, dev_pair + [i, vpp, vpp] + tail),
+        "hsflow_upflow_device": (i, [vp, vp, i, i, vp, vp] + shape + [vp]),
+        "hsflow_warp_gradients_device": (i, dev_pair + uv + [vp, vp, vp] + tail),
+        "hsflow_flow_warped_device": (i, dev_pair + warped + uv + tail),
+        "hsflow_flow_warped": (i, host_pair + warped_d + host_uv),
+        "hsflow_flow_consistency_device": (i, flows + shape + thresholds + [vp, vp, vp, vp]),
+        "hsflow_flow_bidir_workspace_bytes": sized,
+        "hsflow_flow_bidir_device": (i, dev_pair + warped + thresholds + bidir_out + tail),
+        "hsflow_flow_bidir": (i, host_pair + warped_d + thresholds + host_bidir_out),
+        "hsflow_flow_median_device": (i, uv + shape + [i] + uv + [vp]),
+        "hsflow_flow_warped_median_device": (i, dev_pair + solve + uv + tail),
+        "hsflow_flow_warped_median": (i, host_pair + solve_d + host_uv),
+        "hsflow_flow_bidir_median_device": (i, dev_pair + solve + thresholds + bidir_out + tail),
+        "hsflow_flow_bidir_median": (i, host_pair + solve_d + thresholds + host_bidir_out),
+        "hsflow_warp_image_device": (i, [vp, i] + shape + uv + [vp, vp, vp]),
+        "hsflow_frame_interp_device": (i, dev_pair + flows + [vp, vp] + times_out + [vp]),
+        "hsflow_flow_interp_workspace_bytes": sized,
+        "hsflow_flow_interp_device": (i, dev_pair + solve + thresholds + times_out + tail),
+        "hsflow_flow_interp": (i, host_pair + solve_d + thresholds + host_times_out),
+        "hsflow_warp_image_bgr_device": (i, [vp] + shape + uv + [vp, i, vp, vp]),
+        "hsflow_frame_interp_bgr_device": (i, dev_bgr_pair + flows + [vp, vp] + times_out + [vp]),
+        "hsflow_flow_interp_bgr_workspace_bytes": sized,
+        "hsflow_flow_interp_bgr_device": (i, dev_bgr_pair + solve + thresholds + times_out + tail),
+        "hsflow_flow_interp_bgr": (i, host_bgr_pair + solve_d + thresholds + host_times_out),
+        "hsflow_set_interp_bgr_loads": (i, [i]),
+        "hsflow_prefilter_device": (i, [vp, i] + shape + pf + [vp, vp]),
+        "hsflow_prefilter_planes_bytes": (sz, shape),
+        "hsflow_flow_warped_pf_device": (i, dev_pair + solve + uv + pf + tail),
+        "hsflow_flow_bidir_pf_device": (i, dev_pair + solve + thresholds + bidir_out + pf + tail),
+        "hsflow_flow_interp_pf_device": (i, dev_pair + solve + thresholds + times_out + pf + tail),
+        "hsflow_flow_interp_bgr_pf_device": (i, dev_bgr_pair + solve + thresholds + times_out + pf
+                                             + tail),
+        "hsflow_ctx_set_prefilter": (i, [vp] + pf),
+        "hsflow_ctx_prefilter": (i, [vp] + pf),
+        "hsflow_flow_diffusivity_device": (i, uv + shape + [f, vp, vp]),
+        "hsflow_jacobi_weighted_device": (i, shape + plain + [vp] + uv + tail),
+        "hsflow_flow_warped_sm_device": (i, dev_pair + solve + uv + pf + sm + tail),
+        "hsflow_flow_bidir_sm_device": (i, dev_pair + solve + thresholds + bidir_out + pf + sm
+                                        + tail),
+        "hsflow_flow_interp_sm_device": (i, dev_pair + solve + thresholds + times_out + pf + sm
+                                         + tail),
+        "hsflow_flow_interp_bgr_sm_device": (i, dev_bgr_pair + solve + thresholds + times_out + pf
+                                             + sm + tail),
+        "hsflow_ctx_set_smoothness": (i, [vp] + sm),
+        "hsflow_ctx_smoothness": (i, [vp] + sm),
+        "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
+        "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
+        "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),
+        "hsflow_synth_pair": (i, [ctypes.c_uint64, i, i, i, i, vp, vp, vp, vp]),
+    }
+
+
+_PROTOTYPES = _prototypes()
+# every symbol include/hsflow.h declares
+EXPORTS = tuple(_PROTOTYPES)
+
 _lib = None
 _vp = ctypes.c_void_p
-_sz = ctypes.c_size_t
 
 
 def build(force: bool = False) -> str:
@@ -198,148 +271,9 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: run `make -C {_HERE}` "
                           "(or __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
-    i = ctypes.c_int
-    L.hsflow_version.restype = i
-    L.hsflow_status_string.restype = ctypes.c_char_p
-    L.hsflow_status_string.argtypes = [i]
-    L.hsflow_create.argtypes = [ctypes.POINTER(_vp), i]
-    L.hsflow_destroy.argtypes = [_vp]
-    L.hsflow_destroy.restype = None
-    L.hsflow_last_error.argtypes = [_vp]
-    L.hsflow_last_error.restype = ctypes.c_char_p
-    L.hsflow_stream.argtypes = [_vp]
-    L.hsflow_stream.restype = _vp
-    L.hsflow_build_flags.restype = i
-    L.hsflow_flow.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, ctypes.c_double,
-                              _vp, _vp, i, _sz]
-    L.hsflow_gradients.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, _vp, _vp, _vp, i,
-                                   _sz]
-    L.hsflow_workspace_bytes.argtypes = [i, i, i]
-    L.hsflow_workspace_bytes.restype = _sz
-    L.hsflow_flow_device.argtypes = [_vp, _vp, i, i, i, i, i, i, ctypes.c_float,
-                                     _vp, _vp, _vp, _sz, _vp]
-    L.hsflow_gradients_device.argtypes = [_vp, _vp, i, i, i, i, _vp, _vp, _vp,
-                                          _vp, _sz, _vp]
-    L.hsflow_jacobi_device.argtypes = [i, i, i, i, i, ctypes.c_float, i, _vp, _vp,
-                                       _vp, _sz, _vp]
-    L.hsflow_set_iters_per_launch.argtypes = [i]
-    L.hsflow_iters_per_launch.argtypes = [i, i, i, i]
-    L.hsflow_set_max_streams.argtypes = [i]
-    L.hsflow_strip_seg_rows.argtypes = [i, i, i, i]
-    L.hsflow_strip_seg_rows.restype = i
-    L.hsflow_set_output_hugepages.argtypes = [i]
-    L.hsflow_set_output_hugepages.restype = i
-    L.hsflow_max_streams.argtypes = []
-    L.hsflow_set_first_pass_fusion.argtypes = [i]
-    L.hsflow_first_pass_fusion.argtypes = []
-    L.hsflow_first_pass_launches.argtypes = []
-    L.hsflow_first_pass_launches.restype = ctypes.c_longlong
-    L.hsflow_set_jacobi_kernel.argtypes = [i]
-    L.hsflow_set_strip_rows.argtypes = [i]
-    L.hsflow_jacobi_kernel_name.argtypes = [i, i, i, i]
-    L.hsflow_jacobi_kernel_name.restype = ctypes.c_char_p
-    L.hsflow_pyramid_level_size.argtypes = [i, i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
-    L.hsflow_pyramid_workspace_bytes.argtypes = [i, i, i, i]
-    L.hsflow_pyramid_workspace_bytes.restype = _sz
-    L.hsflow_flow_pyramid_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i,
-                                             ctypes.c_float, _vp, _vp, _vp, _sz, _vp]
-    L.hsflow_flow_pyramid.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i,
-                                      ctypes.c_double, _vp, _vp, i, _sz]
-    L.hsflow_warp_gradients_device.argtypes = [_vp, _vp, i, i, i, i, _vp, _vp, _vp, _vp,
-                                               _vp, _vp, _sz, _vp]
-    L.hsflow_flow_warped_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i,
-                                            ctypes.c_float, _vp, _vp, _vp, _sz, _vp]
-    L.hsflow_flow_warped.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i,
-                                     ctypes.c_double, _vp, _vp, i, _sz]
-    f = ctypes.c_float
-    L.hsflow_flow_consistency_device.argtypes = [_vp, _vp, _vp, _vp, i, i, i, f, f, _vp, _vp,
-                                                 _vp, _vp]
-    L.hsflow_flow_bidir_workspace_bytes.argtypes = [i, i, i, i]
-    L.hsflow_flow_bidir_workspace_bytes.restype = _sz
-    L.hsflow_flow_bidir_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f,
-                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _vp, _sz, _vp]
-    L.hsflow_flow_bidir.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i,
-                                    ctypes.c_double, f, f, _vp, _vp, _vp, _vp, i, _sz, _vp,
-                                    _vp, _sz, _vp]
-    L.hsflow_flow_median_device.argtypes = [_vp, _vp, i, i, i, i, _vp, _vp, _vp]
-    L.hsflow_flow_warped_median_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f,
-                                                   _vp, _vp, _vp, _sz, _vp]
-    L.hsflow_flow_warped_median.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
-                                            ctypes.c_double, _vp, _vp, i, _sz]
-    L.hsflow_flow_bidir_median_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f,
-                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                  _vp, _vp, _sz, _vp]
-    L.hsflow_flow_bidir_median.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
-                                           ctypes.c_double, f, f, _vp, _vp, _vp, _vp, i, _sz,
-                                           _vp, _vp, _sz, _vp]
-    fp = ctypes.POINTER(f)
-    L.hsflow_warp_image_device.argtypes = [_vp, i, i, i, i, _vp, _vp, _vp, _vp, _vp]
-    L.hsflow_frame_interp_device.argtypes = [_vp, _vp, i, i, i, i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                             fp, i, _vp, i, _vp, _vp, _vp]
-    L.hsflow_flow_interp_workspace_bytes.argtypes = [i, i, i, i]
-    L.hsflow_flow_interp_workspace_bytes.restype = _sz
-    L.hsflow_flow_interp_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f, fp, i,
-                                            _vp, i, _vp, _vp, _vp, _sz, _vp]
-    L.hsflow_flow_interp.argtypes = [_vp, _vp, _vp, i, i, i, _sz, _sz, i, i, i, i, i,
-                                     ctypes.c_double, f, f, fp, i, ctypes.POINTER(_vp), i, _sz,
-                                     ctypes.POINTER(_vp), _sz, _vp]
-    L.hsflow_warp_image_bgr_device.argtypes = [_vp, i, i, i, _vp, _vp, _vp, i, _vp, _vp]
-    L.hsflow_frame_interp_bgr_device.argtypes = [_vp, _vp, i, i, i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                 fp, i, _vp, i, _vp, _vp, _vp]
-    L.hsflow_flow_interp_bgr_workspace_bytes.argtypes = [i, i, i, i]
-    L.hsflow_flow_interp_bgr_workspace_bytes.restype = _sz
-    L.hsflow_flow_interp_bgr_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f, fp, i,
-                                                _vp, i, _vp, _vp, _vp, _sz, _vp]
-    L.hsflow_flow_interp_bgr.argtypes = [_vp, _vp, _vp, i, i, _sz, _sz, i, i, i, i, i,
-                                         ctypes.c_double, f, f, fp, i, ctypes.POINTER(_vp), i,
-                                         _sz, ctypes.POINTER(_vp), _sz, _vp]
-    L.hsflow_set_interp_bgr_loads.argtypes = [i]
-    pfp = ctypes.POINTER(_CPrefilter)
-    L.hsflow_prefilter_device.argtypes = [_vp, i, i, i, i, pfp, _vp, _vp]
-    L.hsflow_prefilter_planes_bytes.argtypes = [i, i, i]
-    L.hsflow_prefilter_planes_bytes.restype = _sz
-    L.hsflow_flow_warped_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f,
-                                               _vp, _vp, pfp, _vp, _sz, _vp]
-    L.hsflow_flow_bidir_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f,
-                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                              _vp, pfp, _vp, _sz, _vp]
-    L.hsflow_flow_interp_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f, fp,
-                                               i, _vp, i, _vp, _vp, pfp, _vp, _sz, _vp]
-    L.hsflow_flow_interp_bgr_pf_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f, fp,
-                                                   i, _vp, i, _vp, _vp, pfp, _vp, _sz, _vp]
-    L.hsflow_ctx_set_prefilter.argtypes = [_vp, pfp]
-    L.hsflow_ctx_prefilter.argtypes = [_vp, pfp]
-    smp = ctypes.POINTER(_CSmoothness)
-    L.hsflow_flow_diffusivity_device.argtypes = [_vp, _vp, i, i, i, f, _vp, _vp]
-    L.hsflow_jacobi_weighted_device.argtypes = [i, i, i, i, i, f, _vp, _vp, _vp, _vp, _sz, _vp]
-    L.hsflow_flow_warped_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f,
-                                               _vp, _vp, pfp, smp, _vp, _sz, _vp]
-    L.hsflow_flow_bidir_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f,
-                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                              _vp, pfp, smp, _vp, _sz, _vp]
-    L.hsflow_flow_interp_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, i, f, f, f, fp,
-                                               i, _vp, i, _vp, _vp, pfp, smp, _vp, _sz, _vp]
-    L.hsflow_flow_interp_bgr_sm_device.argtypes = [_vp, _vp, i, i, i, i, i, i, i, i, f, f, f, fp,
-                                                   i, _vp, i, _vp, _vp, pfp, smp, _vp, _sz, _vp]
-    L.hsflow_ctx_set_smoothness.argtypes = [_vp, smp]
-    L.hsflow_ctx_smoothness.argtypes = [_vp, smp]
-    L.hsflow_pyramid_build_device.argtypes = [_vp, _vp, i, i, i, i, i,
-                                              ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                              _vp, _sz, _vp]
-    L.hsflow_upflow_device.argtypes = [_vp, _vp, i, i, _vp, _vp, i, i, i, _vp]
-    L.hsflow_bgr_to_gray_device.argtypes = [_vp, i, i, i, _vp, _vp]
-    L.hsflow_flow_bgr.argtypes = [_vp, _vp, _vp, i, i, _sz, _sz, i, i, ctypes.c_double,
-                                  _vp, _vp, i, _sz]
-    L.hsflow_bgr_to_gray.argtypes = [_vp, i, i, _sz, _vp, _sz]
-    L.hsflow_synth_pair.argtypes = [ctypes.c_uint64, i, i, i, i, _vp, _vp, _vp, _vp]
-    L.hsflow_download_device.argtypes = [_vp, _vp, _sz, _vp]
-    L.hsflow_flow_multi.argtypes = [ctypes.POINTER(i), i, i, ctypes.POINTER(_vp),
-                                    ctypes.POINTER(_vp), i, i, i, _sz, _sz, i, i,
-                                    ctypes.c_double, ctypes.POINTER(_vp),
-                                    ctypes.POINTER(_vp), i, _sz]
-    L.hsflow_flow_multi_release.argtypes = []
-    L.hsflow_flow_multi_release.restype = None
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -351,27 +285,23 @@ def _check(rc: int, ctx=None):
         raise HsflowError(rc, msg or L.hsflow_status_string(rc).decode())
 
 
+_DTYPE_CODES = {np.dtype(np.uint8): U8, np.dtype(np.float32): F32, np.dtype(np.float64): F64,
+                np.dtype(np.float16): F16}
+
+
 def _dtype_code(a: np.ndarray) -> int:
-    if a.dtype == np.uint8:
-        return U8
-    if a.dtype == np.float32:
-        return F32
-    if a.dtype == np.float64:
-        return F64
-    if a.dtype == np.float16:
-        return F16
-    raise HsflowError(HSFLOW_ERR_ARG, f"unsupported image dtype {a.dtype}")
+    code = _DTYPE_CODES.get(a.dtype)
+    if code is None:
+        raise HsflowError(HSFLOW_ERR_ARG, f"unsupported image dtype {a.dtype}")
+    return code
 
 
-def _common_dtype(a, b):
-    """Frames of different element types are both widened to float64, as
-    hornSchunck.cpp:23-24 converts each with convertTo(CV_64FC1); each frame
-    keeps its own row step."""
-    if a.dtype != b.dtype:
-        return a.astype(np.float64), b.astype(np.float64)
-    return a, b
+def _float_code(dtype) -> int:
+    """The code of a host output: float64, else float32."""
+    return F64 if dtype == np.float64 else F32
 
 
+# --------------------------------------------------- host frames and outputs
 def _as_image(a) -> np.ndarray:
     a = np.asarray(a)
     if a.ndim != 2:
@@ -382,11 +312,99 @@ def _as_image(a) -> np.ndarray:
     return a
 
 
+def _sizes_differ():
+    return HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
+
+
+def _host_pair(I0, I1):
+    """(a, b, rows, cols) of a pair of grey frames.  Frames of different
+    element types are both widened to float64, as hornSchunck.cpp:23-24
+    converts each with convertTo(CV_64FC1); each frame keeps its own row step."""
+    a, b = _as_image(I0), _as_image(I1)
+    if a.shape != b.shape:
+        raise _sizes_differ()
+    if a.dtype != b.dtype:
+        a, b = a.astype(np.float64), b.astype(np.float64)
+    return a, b, a.shape[0], a.shape[1]
+
+
+def _host_bgr(bgr, hint=""):
+    """A decoded 8-bit BGR frame, H x W x 3, as the library reads it: dense
+    pixels, strided rows accepted (anything else is copied)."""
+    x = np.asarray(bgr)
+    if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
+        raise HsflowError(HSFLOW_ERR_ARG, "need H x W x 3 BGR uint8" + hint)
+    if x.strides[1:] != (3, 1) or x.strides[0] < 3 * x.shape[1]:
+        x = np.ascontiguousarray(x)
+    return x
+
+
+def _host_bgr_pair(bgr0, bgr1, hint=""):
+    """(a, b, rows, cols) of a pair of BGR frames (_host_bgr) of one size."""
+    a, b = _host_bgr(bgr0, hint), _host_bgr(bgr1, hint)
+    if a.shape != b.shape:
+        raise _sizes_differ()
+    return a, b, a.shape[0], a.shape[1]
+
+
+def _pair_args(a, b):
+    """The arguments a host entry point takes for its pair of frames: the
+    pointers, the dtype code (grey frames only), rows, cols and both row steps."""
+    rows, cols = a.shape[:2]
+    if a.ndim == 2:
+        return a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0], b.strides[0]
+    return a.ctypes.data, b.ctypes.data, rows, cols, a.strides[0], b.strides[0]
+
+
 def _reusable(out, shape, dtype) -> bool:
     """(u, v) can take a solve's output in place: the create() rule."""
-    return all(isinstance(x, np.ndarray) and x.shape == tuple(shape) and
-               x.dtype == np.dtype(dtype) and x.flags.c_contiguous and x.flags.writeable
-               for x in out) and out[0] is not out[1]
+    shape, dtype = tuple(shape), np.dtype(dtype)
+    for x in out:
+        if not (isinstance(x, np.ndarray) and x.shape == shape and x.dtype == dtype and
+                x.flags.c_contiguous and x.flags.writeable):
+            return False
+    return out[0] is not out[1]
+
+
+def _host_uv(rows, cols, out_dtype, out=None):
+    """(u, v, args): the outputs of a host solve -- `out` where it can be
+    reused, else new arrays -- and the arguments the entry point takes for
+    them: both pointers, the dtype code and the row step."""
+    if out is not None and _reusable(out, (rows, cols), out_dtype):
+        u, v = out
+    else:
+        u = np.empty((rows, cols), out_dtype)
+        v = np.empty((rows, cols), out_dtype)
+    return u, v, (u.ctypes.data, v.ctypes.data, _float_code(u.dtype), u.strides[0])
+
+
+def _solve_args(levels, warps, median, window, iters, alpha):
+    return int(levels), int(warps), int(median), int(window), int(iters), float(alpha)
+
+
+def _times_array(times):
+    """`times` (a number or a sequence) as the C float array the library reads
+    at call time; the library checks the count and the range."""
+    t = np.atleast_1d(np.asarray(times, np.float64)).tolist()
+    return (ctypes.c_float * len(t))(*t)
+
+
+def _host_interp_out(times, shape, out_dtype, legal, with_flags):
+    """(out, flags, trusted, args) of a host interpolation of frames of
+    `shape` (rows, cols[, 3]): the outputs and the arguments the entry point
+    takes for them, from the times on.  `legal`: the dtypes out may have."""
+    tm = _times_array(times)
+    nt = len(tm)
+    out = np.empty((nt,) + shape, out_dtype)
+    if out.dtype not in legal:
+        raise HsflowError(HSFLOW_ERR_ARG, "out_dtype: need uint8, float32 or float64"
+                          if np.float64 in legal else "out_dtype: need uint8 or float32")
+    flags = np.empty((nt,) + shape[:2], np.uint8) if with_flags else None
+    trusted = np.zeros(nt, np.uint32) if with_flags else None
+    planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
+    fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
+    return out, flags, trusted, (tm, nt, planes, _dtype_code(out), out.strides[1] if nt else 0,
+                                 fplanes, shape[1], trusted.ctypes.data if with_flags else None)
 
 
 class Context:
@@ -423,61 +441,59 @@ class Context:
         self.close()
         return False
 
+    def _call(self, name, *args):
+        """The one path of a host entry point: on this context, status checked."""
+        _check(getattr(lib(), name)(self._p, *args), self._p)
+
+    def _get(self, kind):
+        c = kind._C()
+        _check(getattr(lib(), kind._GET)(self._p, ctypes.byref(c)))
+        return kind(*(getattr(c, f) for f in kind._fields)) if c.mode else None
+
+    def _set(self, kind, value):
+        self._call(kind._SET, _option(kind, value)[1])
+
+    @contextlib.contextmanager
+    def _setting_as(self, kind, value):
+        """`value` (a Prefilter or a Smoothness) on the context for one call,
+        the setting before it restored afterwards; None leaves the context's own."""
+        if value is None:
+            yield
+            return
+        was = self._get(kind)
+        self._set(kind, value)
+        try:
+            yield
+        finally:
+            self._set(kind, was)
+
+    def _call_with(self, prefilter, smoothness, name, *args):
+        """_call with `prefilter` and `smoothness` as the context's settings."""
+        with self._setting_as(Prefilter, prefilter), self._setting_as(Smoothness, smoothness):
+            rc = getattr(lib(), name)(self._p, *args)
+        _check(rc, self._p)
+
     def set_prefilter(self, prefilter=None):
         """The context's prefilter (hsflow_ctx_set_prefilter): flow_warped,
         flow_bidir, interpolate and interpolate_bgr run it on the frames first.
         None or mode 0 = off (default).  flow, flow_bgr, flow_pyramid and
         gradients are the reference's semantics and ignore it."""
-        _, p = _pf_arg(prefilter)
-        _check(lib().hsflow_ctx_set_prefilter(self._p, p), self._p)
+        self._set(Prefilter, prefilter)
 
     def prefilter(self):
         """The context's current Prefilter, None when off."""
-        c = _CPrefilter()
-        _check(lib().hsflow_ctx_prefilter(self._p, ctypes.byref(c)))
-        return Prefilter(c.mode, c.sigma, c.eps, c.scale) if c.mode else None
-
-    @contextlib.contextmanager
-    def _prefilter_as(self, prefilter):
-        """`prefilter` (a Prefilter) on the context for one call, the setting
-        before it restored afterwards; None leaves the context's own."""
-        if prefilter is None:
-            yield
-            return
-        was = self.prefilter()
-        self.set_prefilter(prefilter)
-        try:
-            yield
-        finally:
-            self.set_prefilter(was)
+        return self._get(Prefilter)
 
     def set_smoothness(self, smoothness=None):
         """The context's smoothness term (hsflow_ctx_set_smoothness) for
         flow_warped, flow_bidir, interpolate and interpolate_bgr.  None or mode
         0 = quadratic (default).  flow, flow_bgr, flow_pyramid and gradients are
         the reference's semantics and ignore it."""
-        _, p = _sm_arg(smoothness)
-        _check(lib().hsflow_ctx_set_smoothness(self._p, p), self._p)
+        self._set(Smoothness, smoothness)
 
     def smoothness(self):
         """The context's current Smoothness, None when quadratic."""
-        c = _CSmoothness()
-        _check(lib().hsflow_ctx_smoothness(self._p, ctypes.byref(c)))
-        return Smoothness(c.mode, c.lam) if c.mode else None
-
-    @contextlib.contextmanager
-    def _smoothness_as(self, smoothness):
-        """`smoothness` (a Smoothness) on the context for one call, the setting
-        before it restored afterwards; None leaves the context's own."""
-        if smoothness is None:
-            yield
-            return
-        was = self.smoothness()
-        self.set_smoothness(smoothness)
-        try:
-            yield
-        finally:
-            self.set_smoothness(was)
+        return self._get(Smoothness)
 
     def flow(self, I0, I1, window: int, iters: int, alpha: float, out_dtype=np.float64,
              out=None):
@@ -485,42 +501,19 @@ class Context:
         arrays of out_dtype written in place (cv::Mat::create() keeps an
         existing CV_64FC1 buffer of the right size the same way); else new
         arrays."""
-        a, b = _as_image(I0), _as_image(I1)
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        a, b = _common_dtype(a, b)
-        rows, cols = a.shape
-        if out is not None and _reusable(out, (rows, cols), out_dtype):
-            u, v = out
-        else:
-            u = np.empty((rows, cols), out_dtype)
-            v = np.empty((rows, cols), out_dtype)
-        code = F64 if u.dtype == np.float64 else F32
-        rc = lib().hsflow_flow(self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a),
-                               rows, cols, a.strides[0], b.strides[0], int(window),
-                               int(iters),
-                               float(alpha), u.ctypes.data, v.ctypes.data, code,
-                               u.strides[0])
-        _check(rc, self._p)
+        a, b, rows, cols = _host_pair(I0, I1)
+        u, v, uv = _host_uv(rows, cols, out_dtype, out)
+        self._call("hsflow_flow", *_pair_args(a, b), int(window), int(iters), float(alpha), *uv)
         return u, v
 
     def flow_pyramid(self, I0, I1, levels: int, window: int, iters: int, alpha: float,
                      out_dtype=np.float64):
         """Config 5 coarse-to-fine warm start (`iters` per level), see
         hsflow_flow_pyramid in include/hsflow.h."""
-        a, b = _as_image(I0), _as_image(I1)
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        a, b = _common_dtype(a, b)
-        rows, cols = a.shape
-        u = np.empty((rows, cols), out_dtype)
-        v = np.empty((rows, cols), out_dtype)
-        code = F64 if u.dtype == np.float64 else F32
-        rc = lib().hsflow_flow_pyramid(self._p, a.ctypes.data, b.ctypes.data,
-                                       _dtype_code(a), rows, cols, a.strides[0],
-                                       b.strides[0], int(levels), int(window), int(iters), float(alpha),
-                                       u.ctypes.data, v.ctypes.data, code, u.strides[0])
-        _check(rc, self._p)
+        a, b, rows, cols = _host_pair(I0, I1)
+        u, v, uv = _host_uv(rows, cols, out_dtype)
+        self._call("hsflow_flow_pyramid", *_pair_args(a, b), int(levels), int(window), int(iters),
+                   float(alpha), *uv)
         return u, v
 
     def flow_warped(self, I0, I1, levels: int, warps: int, window: int, iters: int,
@@ -534,20 +527,10 @@ class Context:
         0 = none.  prefilter: a Prefilter set on the context for this call
         (None: the context's own setting, off by default).  smoothness: a
         Smoothness, likewise (window 3 or 5 then)."""
-        a, b = _as_image(I0), _as_image(I1)
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        a, b = _common_dtype(a, b)
-        rows, cols = a.shape
-        u = np.empty((rows, cols), out_dtype)
-        v = np.empty((rows, cols), out_dtype)
-        code = F64 if u.dtype == np.float64 else F32
-        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
-            rc = lib().hsflow_flow_warped_median(
-                self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
-                b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
-                float(alpha), u.ctypes.data, v.ctypes.data, code, u.strides[0])
-        _check(rc, self._p)
+        a, b, rows, cols = _host_pair(I0, I1)
+        u, v, uv = _host_uv(rows, cols, out_dtype)
+        self._call_with(prefilter, smoothness, "hsflow_flow_warped_median", *_pair_args(a, b),
+                        *_solve_args(levels, warps, median, window, iters, alpha), *uv)
         return u, v
 
     def flow_bidir(self, I0, I1, levels: int, warps: int, window: int, iters: int,
@@ -564,11 +547,7 @@ class Context:
         planes' first `cols` columns receive u, v, ub, vb (a padded row step);
         `mask_out`: likewise uint8 [2, rows, >= cols] for the masks.  median,
         prefilter and smoothness as in flow_warped, for both directions."""
-        a, b = _as_image(I0), _as_image(I1)
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        a, b = _common_dtype(a, b)
-        rows, cols = a.shape
+        a, b, rows, cols = _host_pair(I0, I1)
         if out is None:
             out = np.empty((4, rows, cols), out_dtype)
         if mask_out is None:
@@ -581,23 +560,16 @@ class Context:
                 mask_out.shape[2] < cols or mask_out.dtype != np.uint8 or \
                 mask_out.strides[2] != 1:
             raise HsflowError(HSFLOW_ERR_ARG, f"mask_out: need uint8 [2, {rows}, >= {cols}]")
-        u, v, ub, vb = (out[k, :, :cols] for k in range(4))
-        mf, mb = mask_out[0, :, :cols], mask_out[1, :, :cols]
+        u, v = out[0, :, :cols], out[1, :, :cols]
+        ub, vb = (out[2, :, :cols], out[3, :, :cols]) if backward else (None, None)
+        mf, mb = (mask_out[0, :, :cols], mask_out[1, :, :cols]) if masks else (None, None)
         cnt = np.zeros((2, 3), np.uint32) if counts else None
-        code = F64 if out.dtype == np.float64 else F32
-        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
-            rc = lib().hsflow_flow_bidir_median(
-                self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
-                b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
-                float(alpha),
-                float(rel), float(abs), u.ctypes.data, v.ctypes.data,
-                ub.ctypes.data if backward else None, vb.ctypes.data if backward else None, code,
-                out.strides[1], mf.ctypes.data if masks else None,
-                mb.ctypes.data if masks else None, mask_out.strides[1],
-                cnt.ctypes.data if counts else None)
-        _check(rc, self._p)
-        return BidirHost(u, v, ub if backward else None, vb if backward else None,
-                         mf if masks else None, mb if masks else None, cnt)
+        ptr = (lambda x: x.ctypes.data if x is not None else None)
+        self._call_with(prefilter, smoothness, "hsflow_flow_bidir_median", *_pair_args(a, b),
+                        *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
+                        float(abs), ptr(u), ptr(v), ptr(ub), ptr(vb), _float_code(out.dtype),
+                        out.strides[1], ptr(mf), ptr(mb), mask_out.strides[1], ptr(cnt))
+        return BidirHost(u, v, ub, vb, mf, mb, cnt)
 
     def interpolate(self, I0, I1, times, levels: int, warps: int, window: int, iters: int,
                     alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
@@ -612,27 +584,12 @@ class Context:
         [len(times)], the pixels per frame with flags == 0.  prefilter as in
         flow_warped: the flows come from the prefiltered frames, the frames
         themselves are sampled.  smoothness as in flow_warped."""
-        a, b = _as_image(I0), _as_image(I1)
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        a, b = _common_dtype(a, b)
-        rows, cols = a.shape
-        tm = _times_array(times)
-        nt = len(tm)
-        out = np.empty((nt, rows, cols), out_dtype)
-        if out.dtype not in (np.uint8, np.float32, np.float64):
-            raise HsflowError(HSFLOW_ERR_ARG, "out_dtype: need uint8, float32 or float64")
-        flags = np.empty((nt, rows, cols), np.uint8) if with_flags else None
-        trusted = np.zeros(nt, np.uint32) if with_flags else None
-        planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
-        fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
-        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
-            rc = lib().hsflow_flow_interp(
-                self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a), rows, cols, a.strides[0],
-                b.strides[0], int(levels), int(warps), int(median), int(window), int(iters),
-                float(alpha), float(rel), float(abs), tm, nt, planes, _dtype_code(out),
-                out.strides[1], fplanes, cols, trusted.ctypes.data if with_flags else None)
-        _check(rc, self._p)
+        a, b, rows, cols = _host_pair(I0, I1)
+        out, flags, trusted, outs = _host_interp_out(times, (rows, cols), out_dtype,
+                                                     (np.uint8, np.float32, np.float64), with_flags)
+        self._call_with(prefilter, smoothness, "hsflow_flow_interp", *_pair_args(a, b),
+                        *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
+                        float(abs), *outs)
         return (out, flags, trusted) if with_flags else out
 
     def interpolate_bgr(self, bgr0, bgr1, times, levels: int, warps: int, window: int,
@@ -648,100 +605,33 @@ class Context:
         with_flags: (frames, flags, trusted) -- flags uint8 [len(times), rows,
         cols] and trusted uint32 [len(times)] as in interpolate.  prefilter as
         in flow_warped, run on the grey planes; smoothness as in flow_warped."""
-        a = np.asarray(bgr0)
-        b = np.asarray(bgr1)
-        for x in (a, b):
-            if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
-                raise HsflowError(HSFLOW_ERR_ARG, "need H x W x 3 BGR uint8 (grey frames: "
-                                  "Context.interpolate)")
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        if a.strides[1:] != (3, 1) or a.strides[0] < 3 * a.shape[1]:
-            a = np.ascontiguousarray(a)
-        if b.strides[1:] != (3, 1) or b.strides[0] < 3 * b.shape[1]:
-            b = np.ascontiguousarray(b)
-        rows, cols = a.shape[:2]
-        tm = _times_array(times)
-        nt = len(tm)
-        out = np.empty((nt, rows, cols, 3), out_dtype)
-        if out.dtype not in (np.uint8, np.float32):
-            raise HsflowError(HSFLOW_ERR_ARG, "out_dtype: need uint8 or float32")
-        flags = np.empty((nt, rows, cols), np.uint8) if with_flags else None
-        trusted = np.zeros(nt, np.uint32) if with_flags else None
-        planes = (_vp * nt)(*[out[k].ctypes.data for k in range(nt)])
-        fplanes = (_vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
-        with self._prefilter_as(prefilter), self._smoothness_as(smoothness):
-            rc = lib().hsflow_flow_interp_bgr(
-                self._p, a.ctypes.data, b.ctypes.data, rows, cols, a.strides[0], b.strides[0],
-                int(levels), int(warps), int(median), int(window), int(iters), float(alpha),
-                float(rel), float(abs), tm, nt, planes, _dtype_code(out),
-                out.strides[1] if nt else 0, fplanes, cols,
-                trusted.ctypes.data if with_flags else None)
-        _check(rc, self._p)
+        a, b, rows, cols = _host_bgr_pair(bgr0, bgr1, " (grey frames: Context.interpolate)")
+        out, flags, trusted, outs = _host_interp_out(times, (rows, cols, 3), out_dtype,
+                                                     (np.uint8, np.float32), with_flags)
+        self._call_with(prefilter, smoothness, "hsflow_flow_interp_bgr", *_pair_args(a, b),
+                        *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
+                        float(abs), *outs)
         return (out, flags, trusted) if with_flags else out
 
     def flow_bgr(self, bgr0, bgr1, window: int, iters: int, alpha: float,
                  out_dtype=np.float64):
         """main.cpp:50-51 + :13-14 + :97-98: decoded 8-bit BGR frames are
         uploaded as BGR and converted to gray on the GPU, then solved."""
-        a = np.asarray(bgr0)
-        b = np.asarray(bgr1)
-        for x in (a, b):
-            if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
-                raise HsflowError(HSFLOW_ERR_ARG, "need H x W x 3 BGR uint8")
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        if a.strides[1:] != (3, 1) or a.strides[0] < 3 * a.shape[1]:
-            a = np.ascontiguousarray(a)
-        if b.strides[1:] != (3, 1) or b.strides[0] < 3 * b.shape[1]:
-            b = np.ascontiguousarray(b)
-        rows, cols = a.shape[:2]
-        u = np.empty((rows, cols), out_dtype)
-        v = np.empty((rows, cols), out_dtype)
-        code = F64 if u.dtype == np.float64 else F32
-        rc = lib().hsflow_flow_bgr(self._p, a.ctypes.data, b.ctypes.data, rows, cols,
-                                   a.strides[0], b.strides[0], int(window), int(iters), float(alpha),
-                                   u.ctypes.data, v.ctypes.data, code, u.strides[0])
-        _check(rc, self._p)
+        a, b, rows, cols = _host_bgr_pair(bgr0, bgr1)
+        u, v, uv = _host_uv(rows, cols, out_dtype)
+        self._call("hsflow_flow_bgr", *_pair_args(a, b), int(window), int(iters), float(alpha),
+                   *uv)
         return u, v
 
     def gradients(self, I0, I1, out_dtype=np.float64):
-        a, b = _as_image(I0), _as_image(I1)
-        if a.shape != b.shape:
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
-        a, b = _common_dtype(a, b)
-        rows, cols = a.shape
+        a, b, rows, cols = _host_pair(I0, I1)
         gx, gy, gt = (np.empty((rows, cols), out_dtype) for _ in range(3))
-        code = F64 if gx.dtype == np.float64 else F32
-        rc = lib().hsflow_gradients(self._p, a.ctypes.data, b.ctypes.data, _dtype_code(a),
-                                    rows, cols, a.strides[0], b.strides[0], gx.ctypes.data,
-                                    gy.ctypes.data, gt.ctypes.data, code, gx.strides[0])
-        _check(rc, self._p)
+        self._call("hsflow_gradients", *_pair_args(a, b), gx.ctypes.data, gy.ctypes.data,
+                   gt.ctypes.data, _float_code(gx.dtype), gx.strides[0])
         return gx, gy, gt
 
 
 _default_ctx = None
-
-
-def download_device(dst, src, stream=None):
-    """Stream-ordered download of the CUDA tensor `src` into the pinned host
-    tensor `dst` (same byte size) through the runtime's DMA engines
-    (hsflow_download_device), so it overlaps Jacobi passes running on other
-    streams; torch's own copy_ of pinned memory runs as a blit kernel that
-    takes their workgroup slots."""
-    if src.numel() * src.element_size() != dst.numel() * dst.element_size():
-        raise HsflowError(HSFLOW_ERR_ARG, "download sizes differ")
-    if not (src.is_contiguous() and dst.is_contiguous()):
-        raise HsflowError(HSFLOW_ERR_ARG, "download tensors must be contiguous")
-    # a pageable dst would silently serialise the 'overlapped' copy, and a
-    # CUDA dst would get a device-to-host copy kind on a device pointer
-    if not src.is_cuda or dst.is_cuda or not dst.is_pinned():
-        raise HsflowError(HSFLOW_ERR_ARG,
-                          "download_device: src must be a CUDA tensor, dst pinned host memory")
-    with _on(src.device):
-        _check(lib().hsflow_download_device(dst.data_ptr(), src.data_ptr(),
-                                            src.numel() * src.element_size(),
-                                            _stream_ptr(stream, src.device)))
 
 
 def flow_multi(devices, pairs, window: int, iters: int, alpha: float,
@@ -757,7 +647,7 @@ def flow_multi(devices, pairs, window: int, iters: int, alpha: float,
     dt, st0, st1 = pairs[0][0].dtype, pairs[0][0].strides[0], pairs[0][1].strides[0]
     for a, b in pairs:
         if a.shape != (rows, cols) or b.shape != (rows, cols):
-            raise HsflowError(HSFLOW_ERR_SIZE, "Image sizes are different")
+            raise _sizes_differ()
         if a.dtype != dt or b.dtype != dt or a.strides[0] != st0 or b.strides[0] != st1:
             raise HsflowError(HSFLOW_ERR_ARG, "pairs must share dtype and row steps")
     out = [(np.empty((rows, cols), out_dtype), np.empty((rows, cols), out_dtype))
@@ -769,8 +659,7 @@ def flow_multi(devices, pairs, window: int, iters: int, alpha: float,
         devs, len(devices), n, P(*[a.ctypes.data for a, _ in pairs]),
         P(*[b.ctypes.data for _, b in pairs]), _dtype_code(pairs[0][0]), rows, cols, st0,
         st1, int(window), int(iters), float(alpha), P(*[u.ctypes.data for u, _ in out]),
-        P(*[v.ctypes.data for _, v in out]), F64 if out_dtype == np.float64 else F32,
-        out[0][0].strides[0])
+        P(*[v.ctypes.data for _, v in out]), _float_code(out_dtype), out[0][0].strides[0])
     _check(rc)
     return out
 
@@ -856,8 +745,9 @@ def _stream_ptr(stream, device=None):
     """hipStream_t of `stream`, or of the current stream of `device` (the
     tensors' device) when stream is None.  The library runs a call on the
     device its stream belongs to; the null stream (torch's default stream is
-    0 on every device) means the CURRENT device, so every wrapper below makes
-    the tensors' device current around its library call (_on)."""
+    0 on every device) means the CURRENT device, so _device_call, the one path
+    every wrapper below takes, makes the tensors' device current around the
+    library call (_on)."""
     if stream is None:
         return torch.cuda.current_stream(device).cuda_stream if torch is not None else None
     return getattr(stream, "cuda_stream", stream)
@@ -867,6 +757,34 @@ def _on(device):
     """Context that makes `device` current for one library call (a null
     stream runs on the current device, include/hsflow.h)."""
     return torch.cuda.device(device)
+
+
+def _device_call(name, device, stream, *args):
+    """The one path of a stream-ordered entry point: `device` (the tensors')
+    current, the arguments (ending in _ws_args where the entry point takes a
+    workspace), then the stream; status checked."""
+    with _on(device):
+        rc = getattr(lib(), name)(*args, _stream_ptr(stream, device))
+    _check(rc)
+
+
+def download_device(dst, src, stream=None):
+    """Stream-ordered download of the CUDA tensor `src` into the pinned host
+    tensor `dst` (same byte size) through the runtime's DMA engines
+    (hsflow_download_device), so it overlaps Jacobi passes running on other
+    streams; torch's own copy_ of pinned memory runs as a blit kernel that
+    takes their workgroup slots."""
+    if src.numel() * src.element_size() != dst.numel() * dst.element_size():
+        raise HsflowError(HSFLOW_ERR_ARG, "download sizes differ")
+    if not (src.is_contiguous() and dst.is_contiguous()):
+        raise HsflowError(HSFLOW_ERR_ARG, "download tensors must be contiguous")
+    # a pageable dst would silently serialise the 'overlapped' copy, and a
+    # CUDA dst would get a device-to-host copy kind on a device pointer
+    if not src.is_cuda or dst.is_cuda or not dst.is_pinned():
+        raise HsflowError(HSFLOW_ERR_ARG,
+                          "download_device: src must be a CUDA tensor, dst pinned host memory")
+    _device_call("hsflow_download_device", src.device, stream, dst.data_ptr(), src.data_ptr(),
+                 src.numel() * src.element_size())
 
 
 def build_flags() -> int:
@@ -900,17 +818,47 @@ def alloc_workspace(rows: int, cols: int, batch: int = 1, device="cuda"):
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+def pyramid_level_size(rows: int, cols: int, level: int):
+    r, c = ctypes.c_int(), ctypes.c_int()
+    _check(lib().hsflow_pyramid_level_size(rows, cols, level, ctypes.byref(r),
+                                           ctypes.byref(c)))
+    return r.value, c.value
+
+
+def pyramid_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -> int:
+    return int(lib().hsflow_pyramid_workspace_bytes(rows, cols, batch, levels))
+
+
+_TENSOR_CODES = {} if torch is None else {torch.uint8: U8, torch.float32: F32, torch.float16: F16,
+                                          torch.float64: F64}
+
+
 def _tensor_dtype(t) -> int:
-    if t.dtype == torch.uint8:
-        return U8
-    if t.dtype == torch.float32:
-        return F32
-    if t.dtype == torch.float16:
-        return F16
-    if t.dtype == torch.float64:
-        return F64
-    raise HsflowError(HSFLOW_ERR_ARG,
-                      f"device input dtype {t.dtype} (want uint8/float16/float32/float64)")
+    code = _TENSOR_CODES.get(t.dtype)
+    if code is None:
+        raise HsflowError(HSFLOW_ERR_ARG,
+                          f"device input dtype {t.dtype} (want uint8/float16/float32/float64)")
+    return code
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _ws_args(workspace):
+    return workspace.data_ptr(), workspace.numel()
+
+
+def _out_code(out) -> int:
+    """The code of a warped or interpolated device output: uint8, else float32."""
+    return U8 if out.dtype == torch.uint8 else F32
+
+
+def _dims(shape):
+    """(rows, cols, batch) of a tensor shape [..., rows, cols]: batch is the
+    product of the leading dimensions."""
+    rows, cols = shape[-2:]
+    return rows, cols, math.prod(shape[:-2])
 
 
 def _check_dense(t, shape, name):
@@ -929,70 +877,105 @@ def _check_plane(t, shape, batch, name):
                           f"{batch} x {shape[0]} x {shape[1]}")
 
 
+def _check_planes(dims, **planes):
+    for name, t in planes.items():
+        _check_plane(t, dims[:2], dims[2], name)
+
+
+def _frame(I, name="I"):
+    """(rows, cols, batch) of the dense frames I, [B, H, W] or [H, W]."""
+    dims = _dims(I.shape)
+    _check_dense(I, dims[:2], name)
+    return dims
+
+
+def _frame_pair(I0, I1, same=True):
+    """(rows, cols, batch) of the dense frames I0 and I1, of one shape and
+    dtype unless not `same` (the entry points that convert each on its own)."""
+    dims = _frame(I0, "I0")
+    _check_dense(I1, dims[:2], "I1")
+    if same and (I1.dtype != I0.dtype or I1.shape != I0.shape):
+        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
+    return dims
+
+
+def _plane(t, like, dims, name):
+    """The float32 plane `t`, a new one of the shape of `like` when None; checked."""
+    if t is None:
+        t = torch.empty(like.shape, dtype=torch.float32, device=like.device)
+    _check_plane(t, dims[:2], dims[2], name)
+    return t
+
+
+def _workspace(workspace, device, size_fn, *size_args, prefilter=None):
+    """The given workspace, or size_fn(rows, cols, batch[, levels]) bytes on
+    `device`, with the prefilter's planes where one is on."""
+    if workspace is None:
+        n = size_fn(*size_args) + _pf_extra(prefilter, *size_args[:3])
+        workspace = torch.empty(n, dtype=torch.uint8, device=device)
+    return workspace
+
+
+def _check_output(want, shape, dtype, device, name):
+    """An optional output of the consistency check: None / False = not asked
+    for, True = allocate, else a contiguous CUDA tensor of `shape`, `dtype`."""
+    if want is None or want is False:
+        return None
+    if want is True:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not want.is_cuda or want.dtype != dtype or not want.is_contiguous() or \
+            tuple(want.shape) != tuple(shape):
+        raise HsflowError(HSFLOW_ERR_ARG, f"{name}: need a contiguous {dtype} CUDA tensor "
+                          f"{tuple(shape)}")
+    return want
+
+
+def _out_frames(out, shape, out_dtype, device):
+    """The `out` of a colour warp or an interpolation: the given tensor, or a
+    new one of out_dtype (float32 when None); float32 or uint8, of `shape`."""
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype or torch.float32, device=device)
+    if out.dtype not in (torch.float32, torch.uint8):
+        raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
+    return _check_output(out, shape, out.dtype, device, "out")
+
+
+def _interp_outputs(frames, channels, nt, out, out_dtype, flags, trusted):
+    """out / flags / trusted of an interpolation of `nt` times of `frames`,
+    [B, H, W] + channels or [H, W] + channels (channels () or (3,)):
+    [B, nt, H, W] + channels, [B, nt, H, W] and [B, nt]."""
+    plane = tuple(frames.shape[:frames.dim() - len(channels)])
+    shape = plane[:-2] + (nt,) + plane[-2:]
+    out = _out_frames(out, shape + channels, out_dtype, frames.device)
+    flags = _check_output(flags, shape, torch.uint8, frames.device, "flags")
+    trusted = _check_output(trusted, (math.prod(plane[:-2]), nt), torch.int32, frames.device,
+                            "trusted")
+    return out, flags, trusted
+
+
 def flow_device(I0, I1, window: int, iters: int, alpha: float, u=None, v=None,
                 workspace=None, stream=None):
     """Stream-ordered solve on torch CUDA tensors [B, H, W] (or [H, W]).
     Returns (u, v) float32 tensors.  No host synchronisation."""
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    if I1.dtype != I0.dtype or I1.shape != I0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
-    if u is None:
-        u = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
-    if v is None:
-        v = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
-    _check_plane(u, (rows, cols), batch, "u")
-    _check_plane(v, (rows, cols), batch, "v")
-    if workspace is None:
-        workspace = alloc_workspace(rows, cols, batch, I0.device)
-    with _on(I0.device):
-        rc = lib().hsflow_flow_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows,
-                                      cols, batch, int(window), int(iters), float(alpha),
-                                      u.data_ptr(), v.data_ptr(), workspace.data_ptr(),
-                                      workspace.numel(), _stream_ptr(stream, I0.device))
-    _check(rc)
+    dims = _frame_pair(I0, I1)
+    u, v = _plane(u, I0, dims, "u"), _plane(v, I0, dims, "v")
+    workspace = _workspace(workspace, I0.device, workspace_bytes, *dims)
+    _device_call("hsflow_flow_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims, int(window), int(iters), float(alpha), u.data_ptr(),
+                 v.data_ptr(), *_ws_args(workspace))
     return u, v
-
-
-def pyramid_level_size(rows: int, cols: int, level: int):
-    r, c = ctypes.c_int(), ctypes.c_int()
-    _check(lib().hsflow_pyramid_level_size(rows, cols, level, ctypes.byref(r),
-                                           ctypes.byref(c)))
-    return r.value, c.value
-
-
-def pyramid_workspace_bytes(rows: int, cols: int, batch: int, levels: int) -> int:
-    return int(lib().hsflow_pyramid_workspace_bytes(rows, cols, batch, levels))
 
 
 def flow_pyramid_device(I0, I1, levels: int, window: int, iters: int, alpha: float,
                         u=None, v=None, workspace=None, stream=None):
     """Config 5: coarse-to-fine warm start on torch CUDA tensors [B, H, W]
     (uint8 / float16 / float32), `iters` Jacobi iterations per level."""
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    if I1.dtype != I0.dtype or I1.shape != I0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
-    if u is None:
-        u = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
-    if v is None:
-        v = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
-    _check_plane(u, (rows, cols), batch, "u")
-    _check_plane(v, (rows, cols), batch, "v")
-    if workspace is None:
-        n = pyramid_workspace_bytes(rows, cols, batch, levels)
-        workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
-    with _on(I0.device):
-        rc = lib().hsflow_flow_pyramid_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0),
-                                              rows, cols, batch, int(levels), int(window),
-                                              int(iters), float(alpha), u.data_ptr(),
-                                              v.data_ptr(), workspace.data_ptr(),
-                                              workspace.numel(), _stream_ptr(stream, I0.device))
-    _check(rc)
+    dims = _frame_pair(I0, I1)
+    u, v = _plane(u, I0, dims, "u"), _plane(v, I0, dims, "v")
+    workspace = _workspace(workspace, I0.device, pyramid_workspace_bytes, *dims, levels)
+    _device_call("hsflow_flow_pyramid_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims, int(levels), int(window), int(iters), float(alpha),
+                 u.data_ptr(), v.data_ptr(), *_ws_args(workspace))
     return u, v
 
 
@@ -1011,46 +994,16 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
     Smoothness; SMOOTH_FLOW_DRIVEN runs the g-weighted iterations
     (hsflow_flow_warped_sm_device; window 3 or 5, no more workspace).
     Stream-ordered."""
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    if I1.dtype != I0.dtype or I1.shape != I0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
-    if u is None:
-        u = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
-    if v is None:
-        v = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
-    _check_plane(u, (rows, cols), batch, "u")
-    _check_plane(v, (rows, cols), batch, "v")
-    keep, pf = _pf_arg(prefilter)
-    keep_sm, sm = _sm_arg(smoothness)
-    if workspace is None:
-        n = pyramid_workspace_bytes(rows, cols, batch, levels) + \
-            _pf_extra(prefilter, rows, cols, batch)
-        workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
-    with _on(I0.device):
-        rc = lib().hsflow_flow_warped_sm_device(
-            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
-            int(warps), int(median), int(window), int(iters), float(alpha), u.data_ptr(),
-            v.data_ptr(), pf, sm, workspace.data_ptr(), workspace.numel(),
-            _stream_ptr(stream, I0.device))
-    _check(rc)
+    dims = _frame_pair(I0, I1)
+    u, v = _plane(u, I0, dims, "u"), _plane(v, I0, dims, "v")
+    pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
+    workspace = _workspace(workspace, I0.device, pyramid_workspace_bytes, *dims, levels,
+                           prefilter=prefilter)
+    _device_call("hsflow_flow_warped_sm_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims,
+                 *_solve_args(levels, warps, median, window, iters, alpha), u.data_ptr(),
+                 v.data_ptr(), pf, sm, *_ws_args(workspace))
     return u, v
-
-
-def _check_output(want, shape, dtype, device, name):
-    """An optional output of the consistency check: None / False = not asked
-    for, True = allocate, else a contiguous CUDA tensor of `shape`, `dtype`."""
-    if want is None or want is False:
-        return None
-    if want is True:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if not want.is_cuda or want.dtype != dtype or not want.is_contiguous() or \
-            tuple(want.shape) != tuple(shape):
-        raise HsflowError(HSFLOW_ERR_ARG, f"{name}: need a contiguous {dtype} CUDA tensor "
-                          f"{tuple(shape)}")
-    return want
 
 
 def consistency_device(uf, vf, ub, vb, rel: float = CONSISTENCY_REL,
@@ -1063,20 +1016,14 @@ def consistency_device(uf, vf, ub, vb, rel: float = CONSISTENCY_REL,
     like uf (CONSISTENT / INCONSISTENT / OUT_OF_FRAME), int32 [B, 3] (pixels
     per class; the library's uint32 words); at least one.  Returns (err, mask,
     counts), None for those not asked for.  Stream-ordered."""
-    rows, cols = uf.shape[-2:]
-    batch = int(np.prod(uf.shape[:-2])) if uf.dim() > 2 else 1
-    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
-        _check_plane(t, (rows, cols), batch, name)
+    dims = _dims(uf.shape)
+    _check_planes(dims, uf=uf, vf=vf, ub=ub, vb=vb)
     err = _check_output(err, uf.shape, torch.float32, uf.device, "err")
     mask = _check_output(mask, uf.shape, torch.uint8, uf.device, "mask")
-    counts = _check_output(counts, (batch, 3), torch.int32, uf.device, "counts")
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(uf.device):
-        rc = lib().hsflow_flow_consistency_device(
-            uf.data_ptr(), vf.data_ptr(), ub.data_ptr(), vb.data_ptr(), rows, cols, batch,
-            float(rel), float(abs), ptr(err), ptr(mask), ptr(counts),
-            _stream_ptr(stream, uf.device))
-    _check(rc)
+    counts = _check_output(counts, (dims[2], 3), torch.int32, uf.device, "counts")
+    _device_call("hsflow_flow_consistency_device", uf.device, stream, uf.data_ptr(), vf.data_ptr(),
+                 ub.data_ptr(), vb.data_ptr(), *dims, float(rel), float(abs), _ptr(err),
+                 _ptr(mask), _ptr(counts))
     return err, mask, counts
 
 
@@ -1087,19 +1034,11 @@ def median_device(u, v, ksize: int, u_out=None, v_out=None, stream=None):
     for bit (hsflow_flow_median_device in include/hsflow.h).  Out of place:
     u_out, v_out are allocated unless given and must not overlap u or v.
     Returns (u_out, v_out).  Stream-ordered."""
-    rows, cols = u.shape[-2:]
-    batch = int(np.prod(u.shape[:-2])) if u.dim() > 2 else 1
-    if u_out is None:
-        u_out = torch.empty(u.shape, dtype=torch.float32, device=u.device)
-    if v_out is None:
-        v_out = torch.empty(u.shape, dtype=torch.float32, device=u.device)
-    for t, name in ((u, "u"), (v, "v"), (u_out, "u_out"), (v_out, "v_out")):
-        _check_plane(t, (rows, cols), batch, name)
-    with _on(u.device):
-        rc = lib().hsflow_flow_median_device(u.data_ptr(), v.data_ptr(), rows, cols, batch,
-                                             int(ksize), u_out.data_ptr(), v_out.data_ptr(),
-                                             _stream_ptr(stream, u.device))
-    _check(rc)
+    dims = _dims(u.shape)
+    _check_planes(dims, u=u, v=v)
+    u_out, v_out = _plane(u_out, u, dims, "u_out"), _plane(v_out, u, dims, "v_out")
+    _device_call("hsflow_flow_median_device", u.device, stream, u.data_ptr(), v.data_ptr(), *dims,
+                 int(ksize), u_out.data_ptr(), v_out.data_ptr())
     return u_out, v_out
 
 
@@ -1122,51 +1061,27 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
     median and prefilter (hsflow_flow_bidir_pf_device; prefilter_planes_bytes
     more workspace) as in flow_warped_device, for both directions.
     Stream-ordered."""
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    if I1.dtype != I0.dtype or I1.shape != I0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
-    flows = []
-    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
-        if t is None:
-            t = torch.empty(I0.shape, dtype=torch.float32, device=I0.device)
-        _check_plane(t, (rows, cols), batch, name)
-        flows.append(t)
+    dims = _frame_pair(I0, I1)
+    flows = [_plane(t, I0, dims, name)
+             for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb"))]
     outs = []
     for want, name in ((err_f, "err_f"), (mask_f, "mask_f"), (counts_f, "counts_f"),
                        (err_b, "err_b"), (mask_b, "mask_b"), (counts_b, "counts_b")):
         if name.startswith("counts"):
-            outs.append(_check_output(want, (batch, 3), torch.int32, I0.device, name))
+            outs.append(_check_output(want, (dims[2], 3), torch.int32, I0.device, name))
         else:
             outs.append(_check_output(
                 want, I0.shape, torch.float32 if name.startswith("err") else torch.uint8,
                 I0.device, name))
-    keep, pf = _pf_arg(prefilter)
-    keep_sm, sm = _sm_arg(smoothness)
-    if workspace is None:
-        n = bidir_workspace_bytes(rows, cols, batch, levels) + \
-            _pf_extra(prefilter, rows, cols, batch)
-        workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(I0.device):
-        rc = lib().hsflow_flow_bidir_sm_device(
-            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
-            int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
-            float(abs),
-            *[t.data_ptr() for t in flows], *[ptr(t) for t in outs], pf, sm,
-            workspace.data_ptr(),
-            workspace.numel(), _stream_ptr(stream, I0.device))
-    _check(rc)
+    pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
+    workspace = _workspace(workspace, I0.device, bidir_workspace_bytes, *dims, levels,
+                           prefilter=prefilter)
+    _device_call("hsflow_flow_bidir_sm_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims,
+                 *_solve_args(levels, warps, median, window, iters, alpha), float(rel), float(abs),
+                 *[t.data_ptr() for t in flows], *[_ptr(t) for t in outs], pf, sm,
+                 *_ws_args(workspace))
     return BidirDevice(*flows, *outs)
-
-
-def _times_array(times):
-    """`times` (a number or a sequence) as the C float array the library reads
-    at call time; the library checks the count and the range."""
-    t = [float(x) for x in np.atleast_1d(np.asarray(times, np.float64))]
-    return (ctypes.c_float * len(t))(*t)
 
 
 def warp_image_device(I, u, v, out=None, oof=None, stream=None):
@@ -1177,38 +1092,21 @@ def warp_image_device(I, u, v, out=None, oof=None, stream=None):
     include/hsflow.h).  oof: True / a uint8 tensor like I to get 1 where the
     target leaves the frame by more than half a pixel.  Returns out (float32),
     or (out, oof) when oof was asked for.  Stream-ordered."""
-    rows, cols = I.shape[-2:]
-    batch = int(np.prod(I.shape[:-2])) if I.dim() > 2 else 1
-    _check_dense(I, (rows, cols), "I")
-    _check_plane(u, (rows, cols), batch, "u")
-    _check_plane(v, (rows, cols), batch, "v")
-    if out is None:
-        out = torch.empty(I.shape, dtype=torch.float32, device=I.device)
-    _check_plane(out, (rows, cols), batch, "out")
+    dims = _frame(I)
+    _check_planes(dims, u=u, v=v)
+    out = _plane(out, I, dims, "out")
     oof = _check_output(oof, I.shape, torch.uint8, I.device, "oof")
-    with _on(I.device):
-        rc = lib().hsflow_warp_image_device(
-            I.data_ptr(), _tensor_dtype(I), rows, cols, batch, u.data_ptr(), v.data_ptr(),
-            out.data_ptr(), oof.data_ptr() if oof is not None else None,
-            _stream_ptr(stream, I.device))
-    _check(rc)
+    _device_call("hsflow_warp_image_device", I.device, stream, I.data_ptr(), _tensor_dtype(I),
+                 *dims, u.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(oof))
     return out if oof is None else (out, oof)
 
 
-def _interp_outputs(I0, nt, out, out_dtype, flags, trusted):
-    """out / flags / trusted of an interpolation of `nt` times of the frames
-    I0 ([B, H, W] or [H, W]): [B, nt, H, W] ([nt, H, W]) and [B, nt]."""
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    shape = tuple(I0.shape[:-2]) + (nt, rows, cols)
-    if out is None:
-        out = torch.empty(shape, dtype=out_dtype, device=I0.device)
-    if out.dtype not in (torch.float32, torch.uint8):
-        raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
-    out = _check_output(out, shape, out.dtype, I0.device, "out")
-    flags = _check_output(flags, shape, torch.uint8, I0.device, "flags")
-    trusted = _check_output(trusted, (batch, nt), torch.int32, I0.device, "trusted")
-    return out, flags, trusted
+def _check_masks(shape, device, mask_f, mask_b):
+    """The uint8 masks of the forward-backward check where given, of `shape`
+    ([B, H, W], the frames' planes)."""
+    for t, name in ((mask_f, "mask_f"), (mask_b, "mask_b")):
+        if t is not None:
+            _check_output(t, shape, torch.uint8, device, name)
 
 
 def frame_interp_device(I0, I1, uf, vf, ub, vb, times, mask_f=None, mask_b=None, out=None,
@@ -1222,29 +1120,15 @@ def frame_interp_device(I0, I1, uf, vf, ub, vb, times, mask_f=None, mask_b=None,
     uint8 like out, FLAG_* bits; trusted (True / tensor): int32 [B, len(times)]
     (the library's uint32 words), pixels with flags == 0.  Returns (out, flags,
     trusted), None for those not asked for.  Stream-ordered."""
-    if out_dtype is None:
-        out_dtype = torch.float32
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    if I1.dtype != I0.dtype or I1.shape != I0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
-    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
-        _check_plane(t, (rows, cols), batch, name)
-    for t, name in ((mask_f, "mask_f"), (mask_b, "mask_b")):
-        if t is not None:
-            _check_output(t, I0.shape, torch.uint8, I0.device, name)
+    dims = _frame_pair(I0, I1)
+    _check_planes(dims, uf=uf, vf=vf, ub=ub, vb=vb)
+    _check_masks(I0.shape, I0.device, mask_f, mask_b)
     tm = _times_array(times)
-    out, flags, trusted = _interp_outputs(I0, len(tm), out, out_dtype, flags, trusted)
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(I0.device):
-        rc = lib().hsflow_frame_interp_device(
-            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, uf.data_ptr(),
-            vf.data_ptr(), ub.data_ptr(), vb.data_ptr(), ptr(mask_f), ptr(mask_b), tm, len(tm),
-            out.data_ptr(), U8 if out.dtype == torch.uint8 else F32, ptr(flags), ptr(trusted),
-            _stream_ptr(stream, I0.device))
-    _check(rc)
+    out, flags, trusted = _interp_outputs(I0, (), len(tm), out, out_dtype, flags, trusted)
+    _device_call("hsflow_frame_interp_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims, uf.data_ptr(), vf.data_ptr(), ub.data_ptr(),
+                 vb.data_ptr(), _ptr(mask_f), _ptr(mask_b), tm, len(tm), out.data_ptr(),
+                 _out_code(out), _ptr(flags), _ptr(trusted))
     return out, flags, trusted
 
 
@@ -1265,31 +1149,17 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
     frames themselves are sampled (hsflow_flow_interp_pf_device;
     prefilter_planes_bytes more workspace).  Returns (out, flags, trusted) as
     frame_interp_device.  Stream-ordered."""
-    if out_dtype is None:
-        out_dtype = torch.float32
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    if I1.dtype != I0.dtype or I1.shape != I0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
+    dims = _frame_pair(I0, I1)
     tm = _times_array(times)
-    out, flags, trusted = _interp_outputs(I0, len(tm), out, out_dtype, flags, trusted)
-    keep, pf = _pf_arg(prefilter)
-    keep_sm, sm = _sm_arg(smoothness)
-    if workspace is None:
-        n = flow_interp_workspace_bytes(rows, cols, batch, levels) + \
-            _pf_extra(prefilter, rows, cols, batch)
-        workspace = torch.empty(n, dtype=torch.uint8, device=I0.device)
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(I0.device):
-        rc = lib().hsflow_flow_interp_sm_device(
-            I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0), rows, cols, batch, int(levels),
-            int(warps), int(median), int(window), int(iters), float(alpha), float(rel),
-            float(abs), tm, len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32,
-            ptr(flags), ptr(trusted), pf, sm, workspace.data_ptr(), workspace.numel(),
-            _stream_ptr(stream, I0.device))
-    _check(rc)
+    out, flags, trusted = _interp_outputs(I0, (), len(tm), out, out_dtype, flags, trusted)
+    pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
+    workspace = _workspace(workspace, I0.device, flow_interp_workspace_bytes, *dims, levels,
+                           prefilter=prefilter)
+    _device_call("hsflow_flow_interp_sm_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims,
+                 *_solve_args(levels, warps, median, window, iters, alpha), float(rel), float(abs),
+                 tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags), _ptr(trusted), pf, sm,
+                 *_ws_args(workspace))
     return out, flags, trusted
 
 
@@ -1300,22 +1170,16 @@ def _check_bgr(t, name):
             t.dim() not in (3, 4) or t.shape[-1] != 3 or not t.is_cuda or not t.is_contiguous():
         raise HsflowError(HSFLOW_ERR_ARG, f"{name}: need a contiguous uint8 CUDA tensor "
                           "[B, H, W, 3] or [H, W, 3]")
-    return t.shape[-3], t.shape[-2], (t.shape[0] if t.dim() == 4 else 1)
+    return _dims(t.shape[:-1])
 
 
-def _bgr_interp_outputs(bgr0, nt, out, out_dtype, flags, trusted):
-    """out / flags / trusted of a BGR interpolation of `nt` times:
-    [B, nt, H, W, 3] ([nt, H, W, 3]), [B, nt, H, W] and [B, nt]."""
-    rows, cols, batch = _check_bgr(bgr0, "bgr0")
-    lead = tuple(bgr0.shape[:-3])
-    if out is None:
-        out = torch.empty(lead + (nt, rows, cols, 3), dtype=out_dtype, device=bgr0.device)
-    if out.dtype not in (torch.float32, torch.uint8):
-        raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
-    out = _check_output(out, lead + (nt, rows, cols, 3), out.dtype, bgr0.device, "out")
-    flags = _check_output(flags, lead + (nt, rows, cols), torch.uint8, bgr0.device, "flags")
-    trusted = _check_output(trusted, (batch, nt), torch.int32, bgr0.device, "trusted")
-    return out, flags, trusted
+def _bgr_pair(bgr0, bgr1):
+    """(rows, cols, batch) of the BGR frames bgr0 and bgr1, of one shape."""
+    dims = _check_bgr(bgr0, "bgr0")
+    _check_bgr(bgr1, "bgr1")
+    if bgr1.shape != bgr0.shape:
+        raise HsflowError(HSFLOW_ERR_SIZE, "bgr0/bgr1 differ in shape")
+    return dims
 
 
 def warp_image_bgr_device(bgr, u, v, out=None, out_dtype=None, oof=None, stream=None):
@@ -1325,21 +1189,12 @@ def warp_image_bgr_device(bgr, u, v, out=None, out_dtype=None, oof=None, stream=
     gives its plane (hsflow_warp_image_bgr_device in include/hsflow.h).  out:
     float32 (default) or uint8, like bgr; oof: True / a uint8 tensor [B, H, W].
     Returns out, or (out, oof) when oof was asked for.  Stream-ordered."""
-    rows, cols, batch = _check_bgr(bgr, "bgr")
-    _check_plane(u, (rows, cols), batch, "u")
-    _check_plane(v, (rows, cols), batch, "v")
-    if out is None:
-        out = torch.empty(bgr.shape, dtype=out_dtype or torch.float32, device=bgr.device)
-    if out.dtype not in (torch.float32, torch.uint8):
-        raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
-    out = _check_output(out, bgr.shape, out.dtype, bgr.device, "out")
+    dims = _check_bgr(bgr, "bgr")
+    _check_planes(dims, u=u, v=v)
+    out = _out_frames(out, bgr.shape, out_dtype, bgr.device)
     oof = _check_output(oof, bgr.shape[:-1], torch.uint8, bgr.device, "oof")
-    with _on(bgr.device):
-        rc = lib().hsflow_warp_image_bgr_device(
-            bgr.data_ptr(), rows, cols, batch, u.data_ptr(), v.data_ptr(), out.data_ptr(),
-            U8 if out.dtype == torch.uint8 else F32, oof.data_ptr() if oof is not None else None,
-            _stream_ptr(stream, bgr.device))
-    _check(rc)
+    _device_call("hsflow_warp_image_bgr_device", bgr.device, stream, bgr.data_ptr(), *dims,
+                 u.data_ptr(), v.data_ptr(), out.data_ptr(), _out_code(out), _ptr(oof))
     return out if oof is None else (out, oof)
 
 
@@ -1352,27 +1207,15 @@ def frame_interp_bgr_device(bgr0, bgr1, uf, vf, ub, vb, times, mask_f=None, mask
     flags [B, len(times), H, W] and trusted [B, len(times)] are per pixel
     (hsflow_frame_interp_bgr_device in include/hsflow.h).  Returns (out, flags,
     trusted), None for those not asked for.  Stream-ordered."""
-    if out_dtype is None:
-        out_dtype = torch.float32
-    rows, cols, batch = _check_bgr(bgr0, "bgr0")
-    _check_bgr(bgr1, "bgr1")
-    if bgr1.shape != bgr0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "bgr0/bgr1 differ in shape")
-    for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb")):
-        _check_plane(t, (rows, cols), batch, name)
-    for t, name in ((mask_f, "mask_f"), (mask_b, "mask_b")):
-        if t is not None:
-            _check_output(t, bgr0.shape[:-1], torch.uint8, bgr0.device, name)
+    dims = _bgr_pair(bgr0, bgr1)
+    _check_planes(dims, uf=uf, vf=vf, ub=ub, vb=vb)
+    _check_masks(bgr0.shape[:-1], bgr0.device, mask_f, mask_b)
     tm = _times_array(times)
-    out, flags, trusted = _bgr_interp_outputs(bgr0, len(tm), out, out_dtype, flags, trusted)
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(bgr0.device):
-        rc = lib().hsflow_frame_interp_bgr_device(
-            bgr0.data_ptr(), bgr1.data_ptr(), rows, cols, batch, uf.data_ptr(), vf.data_ptr(),
-            ub.data_ptr(), vb.data_ptr(), ptr(mask_f), ptr(mask_b), tm, len(tm), out.data_ptr(),
-            U8 if out.dtype == torch.uint8 else F32, ptr(flags), ptr(trusted),
-            _stream_ptr(stream, bgr0.device))
-    _check(rc)
+    out, flags, trusted = _interp_outputs(bgr0, (3,), len(tm), out, out_dtype, flags, trusted)
+    _device_call("hsflow_frame_interp_bgr_device", bgr0.device, stream, bgr0.data_ptr(),
+                 bgr1.data_ptr(), *dims, uf.data_ptr(), vf.data_ptr(), ub.data_ptr(),
+                 vb.data_ptr(), _ptr(mask_f), _ptr(mask_b), tm, len(tm), out.data_ptr(),
+                 _out_code(out), _ptr(flags), _ptr(trusted))
     return out, flags, trusted
 
 
@@ -1393,29 +1236,16 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
     solve (hsflow_flow_interp_bgr_pf_device; prefilter_planes_bytes more
     workspace).  Returns (out, flags, trusted) as frame_interp_bgr_device.
     Stream-ordered."""
-    if out_dtype is None:
-        out_dtype = torch.float32
-    rows, cols, batch = _check_bgr(bgr0, "bgr0")
-    _check_bgr(bgr1, "bgr1")
-    if bgr1.shape != bgr0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "bgr0/bgr1 differ in shape")
+    dims = _bgr_pair(bgr0, bgr1)
     tm = _times_array(times)
-    out, flags, trusted = _bgr_interp_outputs(bgr0, len(tm), out, out_dtype, flags, trusted)
-    keep, pf = _pf_arg(prefilter)
-    keep_sm, sm = _sm_arg(smoothness)
-    if workspace is None:
-        n = flow_interp_bgr_workspace_bytes(rows, cols, batch, levels) + \
-            _pf_extra(prefilter, rows, cols, batch)
-        workspace = torch.empty(n, dtype=torch.uint8, device=bgr0.device)
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(bgr0.device):
-        rc = lib().hsflow_flow_interp_bgr_sm_device(
-            bgr0.data_ptr(), bgr1.data_ptr(), rows, cols, batch, int(levels), int(warps),
-            int(median), int(window), int(iters), float(alpha), float(rel), float(abs), tm,
-            len(tm), out.data_ptr(), U8 if out.dtype == torch.uint8 else F32, ptr(flags),
-            ptr(trusted), pf, sm, workspace.data_ptr(), workspace.numel(),
-            _stream_ptr(stream, bgr0.device))
-    _check(rc)
+    out, flags, trusted = _interp_outputs(bgr0, (3,), len(tm), out, out_dtype, flags, trusted)
+    pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
+    workspace = _workspace(workspace, bgr0.device, flow_interp_bgr_workspace_bytes, *dims, levels,
+                           prefilter=prefilter)
+    _device_call("hsflow_flow_interp_bgr_sm_device", bgr0.device, stream, bgr0.data_ptr(),
+                 bgr1.data_ptr(), *dims, *_solve_args(levels, warps, median, window, iters, alpha),
+                 float(rel), float(abs), tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags),
+                 _ptr(trusted), pf, sm, *_ws_args(workspace))
     return out, flags, trusted
 
 
@@ -1435,19 +1265,12 @@ def prefilter_device(I, prefilter, out=None, stream=None):
     float64) -> float32 of the same shape: v = I - G*I (PREFILTER_HIGHPASS) or
     scale * v / (sqrt(G*(v v)) + eps) (PREFILTER_NORMALIZE).  `out` must not
     overlap I.  One launch, no workspace.  Stream-ordered."""
-    rows, cols = I.shape[-2:]
-    batch = int(np.prod(I.shape[:-2])) if I.dim() > 2 else 1
-    _check_dense(I, (rows, cols), "I")
+    dims = _frame(I)
     if prefilter is None:
         raise HsflowError(HSFLOW_ERR_ARG, "prefilter_device needs a Prefilter")
-    if out is None:
-        out = torch.empty(I.shape, dtype=torch.float32, device=I.device)
-    _check_plane(out, (rows, cols), batch, "out")
-    keep, pf = _pf_arg(prefilter)
-    with _on(I.device):
-        rc = lib().hsflow_prefilter_device(I.data_ptr(), _tensor_dtype(I), rows, cols, batch, pf,
-                                           out.data_ptr(), _stream_ptr(stream, I.device))
-    _check(rc)
+    out = _plane(out, I, dims, "out")
+    _device_call("hsflow_prefilter_device", I.device, stream, I.data_ptr(), _tensor_dtype(I),
+                 *dims, _option(Prefilter, prefilter)[1], out.data_ptr())
     return out
 
 
@@ -1463,50 +1286,32 @@ def warp_gradients_device(I0, I1, u0, v0, workspace, gx=None, gy=None, gt=None, 
     frames' shape) into the workspace's f32 planes, optionally also into
     gx/gy/gt; jacobi_device(warm_start=True) on (u0, v0) then runs one warp's
     iterations.  gx, gy equal gradients_device's planes bit for bit."""
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    if I1.dtype != I0.dtype or I1.shape != I0.shape:
-        raise HsflowError(HSFLOW_ERR_SIZE, "I0/I1 differ in shape or dtype")
-    _check_plane(u0, (rows, cols), batch, "u0")
-    _check_plane(v0, (rows, cols), batch, "v0")
+    dims = _frame_pair(I0, I1)
+    _check_planes(dims, u0=u0, v0=v0)
     for t, name in ((gx, "gx"), (gy, "gy"), (gt, "gt")):
         if t is not None:
-            _check_plane(t, (rows, cols), batch, name)
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(I0.device):
-        rc = lib().hsflow_warp_gradients_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0),
-                                                rows, cols, batch, u0.data_ptr(), v0.data_ptr(),
-                                                ptr(gx), ptr(gy), ptr(gt), workspace.data_ptr(),
-                                                workspace.numel(),
-                                                _stream_ptr(stream, I0.device))
-    _check(rc)
+            _check_plane(t, dims[:2], dims[2], name)
+    _device_call("hsflow_warp_gradients_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims, u0.data_ptr(), v0.data_ptr(), _ptr(gx), _ptr(gy),
+                 _ptr(gt), *_ws_args(workspace))
 
 
 def pyramid_build_device(I0, I1, levels: int, workspace=None, stream=None):
     """Levels 1..levels-1 of both frames (f32 tensors [B, h_l, w_l]), the
     same planes hsflow_flow_pyramid_device builds internally."""
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
+    dims = _frame_pair(I0, I1, same=False)
     lead = tuple(I0.shape[:-2])
     P0, P1 = [], []
     for l in range(1, levels):
-        r, c = pyramid_level_size(rows, cols, l)
+        r, c = pyramid_level_size(dims[0], dims[1], l)
         P0.append(torch.empty(lead + (r, c), dtype=torch.float32, device=I0.device))
         P1.append(torch.empty(lead + (r, c), dtype=torch.float32, device=I0.device))
-    if workspace is None:
-        workspace = alloc_workspace(rows, cols, batch, I0.device)
+    workspace = _workspace(workspace, I0.device, workspace_bytes, *dims)
     n = max(1, levels - 1)
     a0 = (_vp * n)(*[t.data_ptr() for t in P0]) if P0 else (_vp * 1)()
     a1 = (_vp * n)(*[t.data_ptr() for t in P1]) if P1 else (_vp * 1)()
-    with _on(I0.device):
-        _check(lib().hsflow_pyramid_build_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0),
-                                                 rows, cols, batch, int(levels), a0, a1,
-                                                 workspace.data_ptr(), workspace.numel(),
-                                                 _stream_ptr(stream, I0.device)))
+    _device_call("hsflow_pyramid_build_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims, int(levels), a0, a1, *_ws_args(workspace))
     return P0, P1
 
 
@@ -1515,39 +1320,24 @@ def upflow_device(uc, vc, u, v, stream=None):
     uc, vc are dense [rows, cols] / [rc, cc] views (row slices allowed)."""
     rc, cc = uc.shape[-2:]
     rows, cols = u.shape[-2:]
-    for t, name, shape in ((uc, "uc", (rc, cc)), (vc, "vc", (rc, cc)), (u, "u", (rows, cols)),
-                           (v, "v", (rows, cols))):
-        _check_plane(t, shape, 1, name)
-    with _on(u.device):
-        _check(lib().hsflow_upflow_device(uc.data_ptr(), vc.data_ptr(), rc, cc, u.data_ptr(),
-                                          v.data_ptr(), rows, cols, 1,
-                                          _stream_ptr(stream, u.device)))
+    _check_planes((rc, cc, 1), uc=uc, vc=vc)
+    _check_planes((rows, cols, 1), u=u, v=v)
+    _device_call("hsflow_upflow_device", u.device, stream, uc.data_ptr(), vc.data_ptr(), rc, cc,
+                 u.data_ptr(), v.data_ptr(), rows, cols, 1)
 
 
 def gradients_device(I0, I1, workspace, gx=None, gy=None, gt=None, stream=None):
-    rows, cols = I0.shape[-2:]
-    batch = int(np.prod(I0.shape[:-2])) if I0.dim() > 2 else 1
-    _check_dense(I0, (rows, cols), "I0")
-    _check_dense(I1, (rows, cols), "I1")
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
-    with _on(I0.device):
-        rc = lib().hsflow_gradients_device(I0.data_ptr(), I1.data_ptr(), _tensor_dtype(I0),
-                                           rows, cols, batch, ptr(gx), ptr(gy), ptr(gt),
-                                           workspace.data_ptr(), workspace.numel(),
-                                           _stream_ptr(stream, I0.device))
-    _check(rc)
+    dims = _frame_pair(I0, I1, same=False)
+    _device_call("hsflow_gradients_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+                 _tensor_dtype(I0), *dims, _ptr(gx), _ptr(gy), _ptr(gt), *_ws_args(workspace))
 
 
 def jacobi_device(rows, cols, batch, window, iters, alpha, u, v, workspace,
                   warm_start=False, stream=None):
-    _check_plane(u, (rows, cols), batch, "u")
-    _check_plane(v, (rows, cols), batch, "v")
-    with _on(u.device):
-        rc = lib().hsflow_jacobi_device(int(rows), int(cols), int(batch), int(window),
-                                        int(iters), float(alpha), int(bool(warm_start)),
-                                        u.data_ptr(), v.data_ptr(), workspace.data_ptr(),
-                                        workspace.numel(), _stream_ptr(stream, u.device))
-    _check(rc)
+    _check_planes((rows, cols, batch), u=u, v=v)
+    _device_call("hsflow_jacobi_device", u.device, stream, int(rows), int(cols), int(batch),
+                 int(window), int(iters), float(alpha), int(bool(warm_start)), u.data_ptr(),
+                 v.data_ptr(), *_ws_args(workspace))
 
 
 def diffusivity_device(u, v, lam: float, g=None, stream=None):
@@ -1556,17 +1346,11 @@ def diffusivity_device(u, v, lam: float, g=None, stream=None):
     CUDA tensors [B, H, W] (or [H, W]) in solver units, central differences,
     border replicated.  g is allocated unless given and must not overlap u or
     v.  Returns g.  Stream-ordered."""
-    rows, cols = u.shape[-2:]
-    batch = int(np.prod(u.shape[:-2])) if u.dim() > 2 else 1
-    if g is None:
-        g = torch.empty(u.shape, dtype=torch.float32, device=u.device)
-    for t, name in ((u, "u"), (v, "v"), (g, "g")):
-        _check_plane(t, (rows, cols), batch, name)
-    with _on(u.device):
-        rc = lib().hsflow_flow_diffusivity_device(u.data_ptr(), v.data_ptr(), rows, cols, batch,
-                                                  float(lam), g.data_ptr(),
-                                                  _stream_ptr(stream, u.device))
-    _check(rc)
+    dims = _dims(u.shape)
+    _check_planes(dims, u=u, v=v)
+    g = _plane(g, u, dims, "g")
+    _device_call("hsflow_flow_diffusivity_device", u.device, stream, u.data_ptr(), v.data_ptr(),
+                 *dims, float(lam), g.data_ptr())
     return g
 
 
@@ -1575,14 +1359,10 @@ def jacobi_weighted_device(rows, cols, batch, window, iters, alpha, g, u, v, wor
     """`iters` g-weighted iterations warm-started from (u, v), in place, from
     the f32 gradient planes warp_gradients_device left in `workspace`
     (hsflow_jacobi_weighted_device in include/hsflow.h); window 3 or 5."""
-    for t, name in ((g, "g"), (u, "u"), (v, "v")):
-        _check_plane(t, (rows, cols), batch, name)
-    with _on(u.device):
-        rc = lib().hsflow_jacobi_weighted_device(int(rows), int(cols), int(batch), int(window),
-                                                 int(iters), float(alpha), g.data_ptr(),
-                                                 u.data_ptr(), v.data_ptr(), workspace.data_ptr(),
-                                                 workspace.numel(), _stream_ptr(stream, u.device))
-    _check(rc)
+    _check_planes((rows, cols, batch), g=g, u=u, v=v)
+    _device_call("hsflow_jacobi_weighted_device", u.device, stream, int(rows), int(cols),
+                 int(batch), int(window), int(iters), float(alpha), g.data_ptr(), u.data_ptr(),
+                 v.data_ptr(), *_ws_args(workspace))
 
 
 def set_iters_per_launch(k: int):
@@ -1675,9 +1455,7 @@ def iters_per_launch(rows, cols, batch, window) -> int:
 # ------------------------------------------------------------------ host utils
 def bgr_to_gray(bgr) -> np.ndarray:
     """main.cpp:13-14 cvtColor(BGR2GRAY), OpenCV 4.x 15-bit fixed point."""
-    bgr = np.ascontiguousarray(bgr, np.uint8)
-    if bgr.ndim != 3 or bgr.shape[2] != 3:
-        raise HsflowError(HSFLOW_ERR_ARG, "need H x W x 3 BGR uint8")
+    bgr = _host_bgr(np.asarray(bgr, np.uint8))
     rows, cols = bgr.shape[:2]
     out = np.empty((rows, cols), np.uint8)
     _check(lib().hsflow_bgr_to_gray(bgr.ctypes.data, rows, cols, bgr.strides[0],
@@ -1691,17 +1469,15 @@ def bgr_to_gray_device(bgr, gray=None, stream=None):
     if bgr.dtype != torch.uint8 or bgr.dim() < 3 or bgr.shape[-1] != 3 or \
             not bgr.is_cuda or not bgr.is_contiguous():
         raise HsflowError(HSFLOW_ERR_ARG, "need a contiguous uint8 CUDA tensor [..., H, W, 3]")
-    rows, cols = bgr.shape[-3], bgr.shape[-2]
-    batch = int(np.prod(bgr.shape[:-3])) if bgr.dim() > 3 else 1
+    rows, cols, batch = _dims(bgr.shape[:-1])
     if gray is None:
         gray = torch.empty(bgr.shape[:-1], dtype=torch.uint8, device=bgr.device)
     if gray.dtype != torch.uint8 or not gray.is_cuda or not gray.is_contiguous() or \
             gray.numel() < batch * rows * cols or gray.device != bgr.device:
         raise HsflowError(HSFLOW_ERR_ARG, "gray: need a contiguous uint8 CUDA tensor of "
                           f"{batch} x {rows} x {cols} on {bgr.device}")
-    with _on(bgr.device):
-        _check(lib().hsflow_bgr_to_gray_device(bgr.data_ptr(), rows, cols, batch,
-                                               gray.data_ptr(), _stream_ptr(stream, bgr.device)))
+    _device_call("hsflow_bgr_to_gray_device", bgr.device, stream, bgr.data_ptr(), rows, cols,
+                 batch, gray.data_ptr())
     return gray
 
 

@@ -29,6 +29,35 @@ def test_library_exports_every_declared_symbol():
     assert sorted(hsflow.EXPORTS) == syms
 
 
+RETURN_TYPES = {"int": ctypes.c_int, "void": None, "size_t": ctypes.c_size_t,
+                "long long": ctypes.c_longlong, "const char *": ctypes.c_char_p,
+                "void *": ctypes.c_void_p}
+
+
+def header_declarations():
+    """name -> (return type as ctypes has it, number of parameters) of every
+    declaration of include/hsflow.h."""
+    txt = open(os.path.join(ROOT, "include", "hsflow.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return {name: (RETURN_TYPES[" ".join(ret.split())],
+                   0 if params.strip() == "void" else params.count(",") + 1)
+            for ret, name, params in
+            re.findall(r"^([\w \t*]+?)\s*\b(hsflow_\w+)\s*\(([^()]*)\)\s*;", txt, flags=re.M)}
+
+
+def test_every_export_has_a_prototype_of_the_headers_length():
+    """The binding's prototype table against the header: every declared symbol
+    has a full prototype, with the declaration's return type and as many
+    argtypes as it has parameters, and the loaded library carries them."""
+    declared = header_declarations()
+    assert sorted(declared) == header_symbols() == sorted(hsflow._PROTOTYPES)
+    assert {r for r, _ in declared.values()} == set(RETURN_TYPES.values())
+    L = hsflow.lib()
+    for name, (restype, argtypes) in hsflow._PROTOTYPES.items():
+        assert (restype, len(argtypes)) == declared[name], name
+        assert getattr(L, name).argtypes == argtypes and getattr(L, name).restype == restype, name
+
+
 def test_version_and_status_strings():
     L = hsflow.lib()
     assert L.hsflow_version() == 20000
