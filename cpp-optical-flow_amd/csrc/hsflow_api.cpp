@@ -139,6 +139,31 @@ int g_first_fusion = 1;
 // hsflow_first_pass_launches: fused first passes launched so far
 std::atomic<long long> g_first_launches{0};
 
+// hsflow_set_uv_interleave: between two full-depth K4 passes the state is
+// kept interleaved (1, default; hsflow_strips.hip) or planar (0)
+int g_uv_interleave = 1;
+// hsflow_uv_interleave_launches: passes launched so far that wrote it interleaved
+std::atomic<long long> g_uv_launches{0};
+
+// The passes of a solve that write their state interleaved: pass p does iff
+// pass p + 1 is a full-depth K4 pass (which then reads it so), that is every
+// full-depth pass but the last one -- the last pass of a solve, and the one
+// in front of a shorter K2 pass, write planes.  `first_planar`: pass 0 is a
+// fused first pass whose frames do not take the loads its interleaved body
+// is built on.
+struct UvPlan {
+    bool on;
+    int full;  // full-depth passes
+    bool writes(int pass, bool first_planar = false) const {
+        return on && pass + 1 < full && !(pass == 0 && first_planar);
+    }
+};
+UvPlan plan_uv(const PassPlan &plan, int window, int rows, int cols, int iters) {
+    const bool on = g_uv_interleave && plan.strip &&
+                    hsflow::strip_interleave_ok(window, plan.kb, rows, cols);
+    return {on, plan.strip ? iters / plan.kb : 0};
+}
+
 // KJ's depth: the caller's (hsflow_set_iters_per_launch) where KJ is built for
 // it, else the window's default
 int weighted_kb(int window) {
@@ -263,6 +288,12 @@ int run_passes(hsflow_ctx *ctx, const JacobiSpec &J, float *u, float *v, const W
     // hands the frames down only when it expects this one) the chain runs K1
     // itself in front of its passes.
     const bool fuse = fr && strip && !warm && iters >= kb;
+    // The state between two full-depth K4 passes is interleaved (UvPlan), in
+    // the same planes: the ping-pong above is what it was.  A K2 pass, the
+    // caller's (u, v) on the way in and the last pass's output are planar.
+    const UvPlan uv = plan_uv(plan, window, rows, cols, iters);
+    const bool first_planar =
+        fuse && !hsflow::strip_first_wide(fr->I0, fr->I1, fr->dtype);
     if (fr && fr->dtype != HSFLOW_U8)
         HIP_TRY(ctx, hipMemsetAsync(w.flags, 0, (size_t)batch * 4, s));
     if (fr && !fuse) {
@@ -277,6 +308,9 @@ int run_passes(hsflow_ctx *ctx, const JacobiSpec &J, float *u, float *v, const W
         a.v_in = src_v;
         a.u_out = dst_is_user(pass) ? u : w.u2;
         a.v_out = dst_is_user(pass) ? v : w.v2;
+        a.il_in = (pass > 0 && uv.writes(pass - 1, first_planar)) ? 1 : 0;
+        a.il_out = uv.writes(pass, first_planar) ? 1 : 0;
+        if (a.il_out) g_uv_launches.fetch_add(1, std::memory_order_relaxed);
         if (fuse && pass == 0) {
             const hsflow::FirstArgs f{fr->I0, fr->I1, w.gpack, w.flags, 0};
             hipError_t e =
@@ -854,6 +888,26 @@ int hsflow_first_pass_fusion(void) { return g_first_fusion; }
 
 long long hsflow_first_pass_launches(void) {
     return g_first_launches.load(std::memory_order_relaxed);
+}
+
+int hsflow_set_uv_interleave(int on) {
+    g_uv_interleave = on ? 1 : 0;
+    return HSFLOW_OK;
+}
+
+int hsflow_uv_interleave(void) { return g_uv_interleave; }
+
+int hsflow_uv_interleave_passes(int rows, int cols, int batch, int window, int iters) {
+    if (window < 1 || window > HSFLOW_MAX_WINDOW || iters < 0 || !sizes_ok(rows, cols, batch))
+        return HSFLOW_ERR_ARG;
+    const UvPlan uv = plan_uv(plan_passes(window, true, rows, cols, batch), window, rows, cols, iters);
+    int n = 0;
+    for (int pass = 0; pass < uv.full; ++pass) n += uv.writes(pass) ? 1 : 0;
+    return n;
+}
+
+long long hsflow_uv_interleave_launches(void) {
+    return g_uv_launches.load(std::memory_order_relaxed);
 }
 
 int hsflow_set_output_hugepages(int on) {

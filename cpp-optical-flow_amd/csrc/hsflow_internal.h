@@ -24,6 +24,9 @@ struct JacobiArgs {
     int seg_rows;              // K4 strip kernel: output rows per segment
     int write_through;         // store u', v' write-through (sc1) instead of nt: launches
                                // that do not fill the chip (fill_limited)
+    int il_in, il_out;         // K4: the input / output state is interleaved: row r as
+                               // {u0, u1, v0, v1} groups in the u plane (r even) or the v
+                               // plane (r odd) at the offset of row r & ~1 (hsflow_strips.hip)
 };
 
 // What the fused first pass of a cold K4 solve takes besides JacobiArgs: the
@@ -131,6 +134,11 @@ hipError_t launch_jacobi_weighted(JacobiArgs a, const float *g, int W, int KB, h
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);
+// the state between two K4 passes of this shape may be interleaved
+// (JacobiArgs::il_in / il_out); a fused first pass writes it only from frames
+// that are strip_first_wide
+bool strip_interleave_ok(int W, int KB, int rows, int cols);
+bool strip_first_wide(const void *I0, const void *I1, int dtype_in);
 hipError_t launch_jacobi_strip(JacobiArgs a, int W, int KB, int seg_rows, hipStream_t s);
 // pass 0 of a cold solve with K1 fused in (a.u_in / a.v_in ignored: u = v = 0);
 // dtype_in HSFLOW_U8, F16 or F32

@@ -31,6 +31,19 @@
 // (op_setup / op_update_mean), so K4 and K2 give identical bits for every
 // pass, and a solve may mix them (K2 runs the passes K4 does not cover).
 //
+// Between two K4 passes the state may be kept interleaved (strip_body's IIN /
+// IOUT; even rows and columns): a lane's registers {u0, u1, v0, v1} go out
+// and come back as one 16-byte access instead of two 8-byte ones to two
+// planes.  The interleaved state lives in the two planes it replaces, so the
+// workspace and the ping-pong between (u, v) and (u2, v2) stay as they are:
+// row r is cols / 2 such 16-byte groups, 8 cols bytes, in the u plane when r
+// is even and in the v plane when r is odd, at byte offset (r >> 1) * 8 cols
+// = (r & ~1) * 4 cols -- the planar offset of row r & ~1.  A stream's rows
+// alternate in parity from a first row whose parity the direction fixes, so
+// the plane of every access is a compile-time choice between two resources
+// picked once per wave, and the row offsets cost no scalar work beyond the
+// planar ones.  Same registers, same arithmetic: the same bits.
+//
 // Outside the image u = v = 0 (BORDER_CONSTANT, hornSchunck.cpp:60-61):
 // columns through the window-mean factor (0 outside, as in K2's border
 // body), rows by a wave-uniform select.  Rows of a stage that precede its
@@ -145,11 +158,21 @@ __device__ __forceinline__ f2v ld2(__amdgpu_buffer_rsrc_t r, int vo_e, int vo_o,
     }
 }
 
-template <bool X2, bool G32>
+// IIN: (u, v) as one 16-byte group from the row's plane `ruv` (offsets vo_uv,
+// so_uv); the gradients are planar either way
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+template <bool X2, bool G32, bool IIN>
 __device__ __forceinline__ void load_row(RowIn<G32> &d, const Rsrc &rs, int vo_e, int vo_o,
-                                         int so) {
-    d.u = ld2<X2>(rs.u, vo_e, vo_o, so);
-    d.v = ld2<X2>(rs.v, vo_e, vo_o, so);
+                                         int so, __amdgpu_buffer_rsrc_t ruv, int vo_uv,
+                                         int so_uv) {
+    if constexpr (IIN) {
+        const u4v a = __builtin_amdgcn_raw_buffer_load_b128(ruv, vo_uv, so_uv, 0);
+        d.u = f2v{__uint_as_float(a.x), __uint_as_float(a.y)};
+        d.v = f2v{__uint_as_float(a.z), __uint_as_float(a.w)};
+    } else {
+        d.u = ld2<X2>(rs.u, vo_e, vo_o, so);
+        d.v = ld2<X2>(rs.v, vo_e, vo_o, so);
+    }
     if constexpr (G32) {
         d.gx = ld2<X2>(rs.gx, vo_e, vo_o, so);
         d.gy = ld2<X2>(rs.gy, vo_e, vo_o, so);
@@ -293,13 +316,19 @@ __device__ __forceinline__ bool integral_u8(float x) {
 // K1's outputs: the packed word of the rows and lanes it stores (every
 // pixel of the pair exactly once) and, returned for the kernel's one atomic
 // per wave, whether any of its pixels fails K1's integrality test.
-template <int W, int KB, int D, int U, bool X2, bool G32, bool WT, typename FT = void>
+//
+// IIN / IOUT: the input / output state is interleaved (the file's head).
+template <int W, int KB, int D, int U, bool X2, bool G32, bool WT, typename FT = void,
+          bool IIN = false, bool IOUT = false>
 __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, int plane_bytes,
                                            int c0, int a, int b, int dir,
                                            const FirstArgs &fa = FirstArgs{}) {
     constexpr bool FIRST = !std::is_void<FT>::value;
     constexpr int ES = FrameElem<FT>::size;
     static_assert(!(FIRST && G32), "the first pass builds its operator from the frames");
+    static_assert(!(FIRST && IIN), "the first pass reads no state");
+    static_assert(!(IIN || IOUT) || (X2 && (KB * (W / 2)) % 2 == 0),
+                  "interleaved rows: an even width, stage rows of the step's parity");
     constexpr int A = W - W / 2 - 1, AR = W / 2;
     static_assert(A == AR, "K4 is built for odd windows");
     constexpr int L = KB * AR;  // operator ring: the rows t - AR .. t - KB AR
@@ -324,6 +353,9 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
     const bool st_lane = lane >= HLc / 2 && lane < (128 - HRc) / 2;
     const int st_e = (st_lane && ce) ? c4 : kOOB;
     const int st_o = (st_lane && co) ? c4 + 4 : kOOB;
+    // interleaved state: 16 bytes per column pair
+    const int ld_uv = ce ? 2 * c4 : kOOB;
+    const int st_uv = (st_lane && ce) ? 2 * c4 : kOOB;
 
     Rsrc rs;
     rs.u = __builtin_amdgcn_make_buffer_rsrc((void *)(p.u_in ? p.u_in + pbase : p.u_out + pbase),
@@ -342,6 +374,21 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
                                               0x00020000);
     rs.vo = __builtin_amdgcn_make_buffer_rsrc((void *)(p.v_out + pbase), 0, plane_bytes,
                                               0x00020000);
+    // interleaved state: the plane of a step's row, by the step's parity (a
+    // downward stream starts at an even row, an upward one at an odd row; U
+    // and KB AR are even, so step k of every block, and the stage-KB row it
+    // stores, have the parity of k, flipped upwards)
+    const float *in_u = p.u_in ? p.u_in + pbase : p.u_out + pbase;
+    const float *in_v = p.v_in ? p.v_in + pbase : p.v_out + pbase;
+    const int in_bytes = (IIN && p.u_in) ? plane_bytes : 0, out_bytes = IOUT ? plane_bytes : 0;
+    const __amdgpu_buffer_rsrc_t rin[2] = {
+        __builtin_amdgcn_make_buffer_rsrc((void *)(dir > 0 ? in_u : in_v), 0, in_bytes, 0x00020000),
+        __builtin_amdgcn_make_buffer_rsrc((void *)(dir > 0 ? in_v : in_u), 0, in_bytes, 0x00020000)};
+    const __amdgpu_buffer_rsrc_t rout[2] = {
+        __builtin_amdgcn_make_buffer_rsrc((void *)((dir > 0 ? p.u_out : p.v_out) + pbase), 0,
+                                          out_bytes, 0x00020000),
+        __builtin_amdgcn_make_buffer_rsrc((void *)((dir > 0 ? p.v_out : p.u_out) + pbase), 0,
+                                          out_bytes, 0x00020000)};
     // first pass: the pair's frames (ES bytes per element) and its packed plane
     const int fplane_bytes = plane_bytes / 4 * ES;
     const __amdgpu_buffer_rsrc_t rs_i0 = __builtin_amdgcn_make_buffer_rsrc(
@@ -388,7 +435,14 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
     auto row_off = [&](int r) {
         return (unsigned)r < (unsigned)rows ? r * row_bytes : (int)0x80000000;
     };
-    auto issue = [&](RowIn<G32> &d, int r) { load_row<X2, G32>(d, rs, ld_e, ld_o, row_off(r)); };
+    // interleaved: row r at the planar offset of row r & ~1, in r's plane
+    auto row_off_il = [&](int r) {
+        return (unsigned)r < (unsigned)rows ? (r & ~1) * row_bytes : (int)0x80000000;
+    };
+    // kpar: the parity of the row's step
+    auto issue = [&](RowIn<G32> &d, int r, int kpar) {
+        load_row<X2, G32, IIN>(d, rs, ld_e, ld_o, row_off(r), rin[kpar], ld_uv, row_off_il(r));
+    };
 
     // first pass: the slot of row r holds I0's row r + dir and I1's row r;
     // rp, rz = I0's rows r - dir and r, converted (the Sobel's ring)
@@ -414,7 +468,7 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
         rz = cvtf<FT, X2>(w_z);
     } else {
 #pragma unroll
-        for (int k = 0; k < D; ++k) issue(buf[k], t_first + dir * k);
+        for (int k = 0; k < D; ++k) issue(buf[k], t_first + dir * k, k & 1);
     }
 
     const f2v z = {0.f, 0.f};
@@ -459,6 +513,8 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
         // byte offset of the block's first stage-KB row (PLAIN blocks)
         const int ob = PLAIN ? (tb - dir * (KB * AR)) * row_bytes : 0;
         const int fob = PLAIN ? (tb - dir * (KB * AR)) * frow_bytes : 0;  // the same, frames
+        // the same, interleaved state: step j's row at ob_il + (j & ~1) drb
+        const int ob_il = PLAIN ? ((tb & ~1) - dir * (KB * AR)) * row_bytes : 0;
 #pragma unroll
         for (int k = 0; k < U; ++k) {
             const int t = tb + dir * k;
@@ -481,9 +537,11 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
             } else {
                 cur = buf[k % D];
                 if constexpr (PLAIN)
-                    load_row<X2, G32>(buf[k % D], rs, ld_e, ld_o, ob + (k + KB * AR + D) * drb);
+                    load_row<X2, G32, IIN>(buf[k % D], rs, ld_e, ld_o,
+                                           ob + (k + KB * AR + D) * drb, rin[(k + D) & 1], ld_uv,
+                                           ob_il + ((k + KB * AR + D) & ~1) * drb);
                 else
-                    issue(buf[k % D], t + dir * D);
+                    issue(buf[k % D], t + dir * D, (k + D) & 1);
             }
             // 2. level-0 horizontal sums of row t
             f2v hu, hv;
@@ -534,7 +592,26 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
                     // full-chip launches 3 % (profiles/r03_store_policy_ab.txt)
                     {
                         constexpr int AUX = WT ? 16 : 2;
-                        if constexpr (X2) {
+                        if constexpr (IOUT) {
+                            const int so_il = PLAIN ? ob_il + (k & ~1) * drb
+                                                    : (sin ? (y & ~1) * row_bytes : (int)0x80000000);
+                            // The row's offset is added into voffset (one VALU
+                            // add per row), soffset 0.  With the offset in an
+                            // SGPR soffset the compiler's hazard recogniser
+                            // leaves no wait state between a store of more than
+                            // 8 bytes and a VALU write of its data registers
+                            // (it takes that form to be free of the hazard), the
+                            // f32-gradient body of the in-and-out pass got such
+                            // pairs, and on gfx950 the stored rows were wrong in
+                            // one lane of every 16 (tests/test_strips_uv.py,
+                            // the mixed batch).  This form it pads where needed.
+                            // Out-of-range offsets stay so: kOOB + so_il < 2^32,
+                            // and 2^31 + any lane offset is past the plane.
+                            __builtin_amdgcn_raw_buffer_store_b128(
+                                u4v{__float_as_uint(nu.x), __float_as_uint(nu.y),
+                                    __float_as_uint(nv.x), __float_as_uint(nv.y)},
+                                rout[k & 1], (int)((unsigned)st_uv + (unsigned)so_il), 0, AUX);
+                        } else if constexpr (X2) {
                             __builtin_amdgcn_raw_buffer_store_b64(
                                 u2v{__float_as_uint(nu.x), __float_as_uint(nu.y)}, rs.uo, oe, so,
                                 AUX);
@@ -661,7 +738,9 @@ __device__ __forceinline__ bool strip_body(const JacobiArgs &p, size_t pbase, in
 // (strips fastest), so the strips that share halo columns run side by side;
 // the XCD-aware remap gives each XCD a contiguous run of them (its L2
 // serves the shared halo columns and the rows two segments both read).
-template <int W, int KB, int D, int U, int WPE, bool WT>
+// IL: the state is interleaved on the way in (bit 0) / out (bit 1); the
+// launcher gives such passes an even width.
+template <int W, int KB, int D, int U, int WPE, bool WT, int IL = 0>
 __global__ __launch_bounds__(64, WPE) void hs_jacobi_strip_kernel(const JacobiArgs p) {
     const int nblk = gridDim.x;
     const int lin = blockIdx.x;
@@ -687,7 +766,15 @@ __global__ __launch_bounds__(64, WPE) void hs_jacobi_strip_kernel(const JacobiAr
     // for one of them) or both at their ends, instead of one at its start
     // and the other at its end, a whole stream apart
     const int dir = (seg & 1) ? -1 : 1;
-    if (g32) {
+    if constexpr (IL != 0) {
+        constexpr bool IIN = (IL & 1) != 0, IOUT = (IL & 2) != 0;
+        if (g32)
+            strip_body<W, KB, D, U, true, true, WT, void, IIN, IOUT>(p, pbase, plane_bytes, c0, a,
+                                                                     b, dir);
+        else
+            strip_body<W, KB, D, U, true, false, WT, void, IIN, IOUT>(p, pbase, plane_bytes, c0,
+                                                                      a, b, dir);
+    } else if (g32) {
         if ((p.cols & 1) == 0)
             strip_body<W, KB, D, U, true, true, WT>(p, pbase, plane_bytes, c0, a, b, dir);
         else
@@ -705,7 +792,7 @@ __global__ __launch_bounds__(64, WPE) void hs_jacobi_strip_kernel(const JacobiAr
 // leaves the pair's packed gradients and its flag as K1 does: 8-bit frames a
 // plain 0 from one wave of the pair, the others one atomic OR per wave that
 // saw a non-integral pixel (the flags are zero before the launch).
-template <int W, int KB, int D, int U, int WPE, bool WT, typename FT>
+template <int W, int KB, int D, int U, int WPE, bool WT, typename FT, bool IOUT = false>
 __global__ __launch_bounds__(64, WPE) void hs_jacobi_strip_first_kernel(const JacobiArgs p,
                                                                         const FirstArgs f) {
     const int nblk = gridDim.x;
@@ -728,7 +815,10 @@ __global__ __launch_bounds__(64, WPE) void hs_jacobi_strip_first_kernel(const Ja
     const int plane_bytes = p.rows * p.cols * 4;
     const int dir = (seg & 1) ? -1 : 1;
     bool bad;
-    if ((p.cols & 1) == 0 && f.wide)
+    if constexpr (IOUT)  // an even width and frames that take wide loads (the launcher)
+        bad = strip_body<W, KB, D, U, true, false, WT, FT, false, true>(p, pbase, plane_bytes, c0,
+                                                                        a, b, dir, f);
+    else if ((p.cols & 1) == 0 && f.wide)
         bad = strip_body<W, KB, D, U, true, false, WT, FT>(p, pbase, plane_bytes, c0, a, b, dir, f);
     else
         bad = strip_body<W, KB, D, U, false, false, WT, FT>(p, pbase, plane_bytes, c0, a, b, dir,
@@ -750,26 +840,48 @@ template <> struct StripCfg<5, 5> { static constexpr int D = 5, U = 10, WPE = 2;
 template <> struct StripCfg<5, 4> { static constexpr int D = 2, U = 8, WPE = 3; };
 template <> struct StripCfg<3, 8> { static constexpr int D = 2, U = 8, WPE = 2; };
 
-template <int W, int KB>
+template <int W, int KB, int IL = 0>
 void launch_cfg(const JacobiArgs &a, dim3 grd, bool wt, hipStream_t s) {
     using C = StripCfg<W, KB>;
     if (wt)
-        hipLaunchKernelGGL((hs_jacobi_strip_kernel<W, KB, C::D, C::U, C::WPE, true>), grd,
+        hipLaunchKernelGGL((hs_jacobi_strip_kernel<W, KB, C::D, C::U, C::WPE, true, IL>), grd,
                            dim3(64), 0, s, a);
     else
-        hipLaunchKernelGGL((hs_jacobi_strip_kernel<W, KB, C::D, C::U, C::WPE, false>), grd,
+        hipLaunchKernelGGL((hs_jacobi_strip_kernel<W, KB, C::D, C::U, C::WPE, false, IL>), grd,
                            dim3(64), 0, s, a);
+}
+
+// the pass with its state interleaved on the way in, out or both
+template <int W, int KB>
+void launch_cfg_il(const JacobiArgs &a, dim3 grd, bool wt, hipStream_t s) {
+    const int il = (a.il_in ? 1 : 0) | (a.il_out ? 2 : 0);
+    if (il == 1)
+        launch_cfg<W, KB, 1>(a, grd, wt, s);
+    else if (il == 2)
+        launch_cfg<W, KB, 2>(a, grd, wt, s);
+    else
+        launch_cfg<W, KB, 3>(a, grd, wt, s);
+}
+
+template <int W, int KB, typename FT, bool IOUT>
+void launch_first_il(const JacobiArgs &a, const FirstArgs &f, dim3 grd, bool wt, hipStream_t s) {
+    using C = StripCfg<W, KB>;
+    if (wt)
+        hipLaunchKernelGGL(
+            (hs_jacobi_strip_first_kernel<W, KB, C::D, C::U, C::WPE, true, FT, IOUT>), grd,
+            dim3(64), 0, s, a, f);
+    else
+        hipLaunchKernelGGL(
+            (hs_jacobi_strip_first_kernel<W, KB, C::D, C::U, C::WPE, false, FT, IOUT>), grd,
+            dim3(64), 0, s, a, f);
 }
 
 template <int W, int KB, typename FT>
 void launch_first_t(const JacobiArgs &a, const FirstArgs &f, dim3 grd, bool wt, hipStream_t s) {
-    using C = StripCfg<W, KB>;
-    if (wt)
-        hipLaunchKernelGGL((hs_jacobi_strip_first_kernel<W, KB, C::D, C::U, C::WPE, true, FT>),
-                           grd, dim3(64), 0, s, a, f);
-    else
-        hipLaunchKernelGGL((hs_jacobi_strip_first_kernel<W, KB, C::D, C::U, C::WPE, false, FT>),
-                           grd, dim3(64), 0, s, a, f);
+    if constexpr ((W == 5 && KB == 6) || (W == 3 && KB == 8)) {  // strip_interleave_ok
+        if (a.il_out) return launch_first_il<W, KB, FT, true>(a, f, grd, wt, s);
+    }
+    launch_first_il<W, KB, FT, false>(a, f, grd, wt, s);
 }
 
 template <int W, int KB>
@@ -805,6 +917,20 @@ bool strip_grid(JacobiArgs &a, int W, int KB, int seg_rows, dim3 *grd) {
 // the chip), w = 3 at KB 8
 bool strip_supported(int W, int KB) {
     return (W == 5 && KB >= 4 && KB <= 6) || (W == 3 && KB == 8);
+}
+
+// The interleaved state between passes: built for the two default depths
+// (the shallower w = 5 passes stay planar), and it must fit the two planes it
+// replaces row for row -- even rows in one, odd rows in the other, 8 cols
+// bytes each -- so the height and the width are even.
+bool strip_interleave_ok(int W, int KB, int rows, int cols) {
+    return ((W == 5 && KB == 6) || (W == 3 && KB == 8)) && rows % 2 == 0 && cols % 2 == 0;
+}
+
+// the frames of a fused first pass take one load per column pair
+bool strip_first_wide(const void *I0, const void *I1, int dtype_in) {
+    const uintptr_t es2 = dtype_in == 0 ? 1 : (dtype_in == 3 ? 4 : 8);
+    return (((uintptr_t)I0 | (uintptr_t)I1) & (es2 - 1)) == 0;
 }
 
 // Segment rows for a launch.  Each wave streams N rows plus the KB (W - 1)
@@ -919,6 +1045,14 @@ hipError_t launch_jacobi_strip(JacobiArgs a, int W, int KB, int seg_rows, hipStr
     dim3 grd;
     if (!strip_grid(a, W, KB, seg_rows, &grd)) return hipErrorInvalidValue;
     const bool wt = a.write_through != 0;
+    if (a.il_in || a.il_out) {
+        if (!strip_interleave_ok(W, KB, a.rows, a.cols)) return hipErrorInvalidValue;
+        if (W == 5)
+            launch_cfg_il<5, 6>(a, grd, wt, s);
+        else
+            launch_cfg_il<3, 8>(a, grd, wt, s);
+        return hipGetLastError();
+    }
     if (W == 5 && KB == 6)
         launch_cfg<5, 6>(a, grd, wt, s);
     else if (W == 5 && KB == 5)
@@ -941,8 +1075,11 @@ hipError_t launch_jacobi_strip_first(JacobiArgs a, FirstArgs f, int dtype_in, in
     dim3 grd;
     if (!strip_grid(a, W, KB, seg_rows, &grd)) return hipErrorInvalidValue;
     a.u_in = a.v_in = nullptr;
-    const uintptr_t es2 = dtype_in == 0 ? 1 : (dtype_in == 3 ? 4 : 8);
-    f.wide = (((uintptr_t)f.I0 | (uintptr_t)f.I1) & (es2 - 1)) == 0 ? 1 : 0;
+    a.il_in = 0;
+    f.wide = strip_first_wide(f.I0, f.I1, dtype_in) ? 1 : 0;
+    // an interleaved output takes the body with one load per column pair
+    if (a.il_out && !(strip_interleave_ok(W, KB, a.rows, a.cols) && f.wide))
+        return hipErrorInvalidValue;
     const bool wt = a.write_through != 0;
     if (W == 5 && KB == 6) return launch_first_cfg<5, 6>(a, f, dtype_in, grd, wt, s);
     if (W == 5 && KB == 5) return launch_first_cfg<5, 5>(a, f, dtype_in, grd, wt, s);

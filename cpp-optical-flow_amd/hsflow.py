@@ -190,6 +190,13 @@ def _prototypes():
         "hsflow_set_first_pass_fusion": (i, [i]),
         "hsflow_first_pass_fusion": (i, []),
         "hsflow_first_pass_launches": (ctypes.c_longlong, []),
+        # the interleaved (u, v) between K4 passes: the switch, the plan of a
+        # shape (rows, cols, batch, window, iters) and the launch counter;
+        # called through lib()
+        "hsflow_set_uv_interleave": (i, [i]),
+        "hsflow_uv_interleave": (i, []),
+        "hsflow_uv_interleave_passes": (i, shape + [i, i]),
+        "hsflow_uv_interleave_launches": (ctypes.c_longlong, []),
         "hsflow_set_output_hugepages": (i, [i]),
         "hsflow_download_device": (i, [vp, vp, sz, vp]),
         "hsflow_pyramid_level_size": (i, [i, i, i, ip, ip]),

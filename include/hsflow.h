@@ -211,6 +211,31 @@ int hsflow_first_pass_fusion(void);
  * tells whether it fused. */
 long long hsflow_first_pass_launches(void);
 
+/* Between two full-depth K4 passes a solve keeps (u, v) interleaved: each
+ * column pair's {u0, u1, v0, v1} as one 16-byte group, the even rows in the
+ * plane that otherwise holds u and the odd rows in the one that holds v, so a
+ * pass moves the state with one 16-byte access per lane where it took two
+ * 8-byte ones.  It needs an even height and width (the interleaved rows must
+ * fit the two planes they replace; the workspace is what it was) and K4 at
+ * its default depth; other shapes, K2 passes, the caller's (u, v) on the way
+ * in and every result are planar.  on = 1 (default), 0 keeps every pass
+ * planar.  Identical bits either way.  During a solve the caller's u and v
+ * hold intermediate state in either form, as before.  Process-wide; not
+ * thread-safe against running solves.  hsflow_uv_interleave returns the
+ * current setting. */
+int hsflow_set_uv_interleave(int on);
+int hsflow_uv_interleave(void);
+/* How many passes of a Jacobi solve of this shape write their state
+ * interleaved under the current settings: every full-depth K4 pass but the
+ * last one, 0 where the solve stays planar.  Host only: nothing is launched.
+ * (A fused first pass on frames that are not aligned to two elements writes
+ * planes: one less.)  HSFLOW_ERR_ARG (< 0) for a bad shape. */
+int hsflow_uv_interleave_passes(int rows, int cols, int batch, int window, int iters);
+/* Passes launched so far that wrote their state interleaved (per
+ * stream-ordered chain, as hsflow_first_pass_launches).  For tests and
+ * profiles. */
+long long hsflow_uv_interleave_launches(void);
+
 /* Huge-page advice on f64 outputs of the host-buffer calls (hsflow_flow,
  * hsflow_flow_bgr, hsflow_flow_pyramid, hsflow_flow_multi with
  * dtype_out = HSFLOW_F64): before widening the downloaded f32 rows into
