@@ -816,6 +816,7 @@ void hsflow_destroy(hsflow_ctx *ctx) {
     if (ctx->d_in) (void)hipFree(ctx->d_in);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
+    if (ctx->d_pred) (void)hipFree(ctx->d_pred);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     for (hipEvent_t e : ctx->dl_ev) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

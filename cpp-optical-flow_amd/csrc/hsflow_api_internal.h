@@ -32,6 +32,15 @@ struct hsflow_ctx {
     // hsflow_ctx_set_smoothness: the smoothness term of the same calls' solves
     // (mode 0: the quadratic one)
     hsflow_smoothness sm{0, 0.0f};
+    // hsflow_ctx_set_temporal: sequence mode of the bidirectional host-buffer
+    // calls.  d_pred (grow-only) holds KP's four planes uf, vf, ub, vb of the
+    // last such call, each align_up(pred_rows * pred_cols * 4) bytes;
+    // pred_valid: they are the start of the next call of that size
+    int temporal = 0;
+    void *d_pred = nullptr;
+    size_t d_pred_bytes = 0;
+    int pred_rows = 0, pred_cols = 0;
+    bool pred_valid = false;
 };
 
 namespace hsflow::host {

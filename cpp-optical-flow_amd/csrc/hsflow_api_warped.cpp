@@ -25,6 +25,7 @@ struct SolveSpec {
     float alpha;
     const hsflow_prefilter *pf;   // null or mode 0: the frames as they are
     const hsflow_smoothness *sm;  // null or mode 0: the quadratic term
+    const hsflow_flow_init *init;  // null or no plane: every solve starts cold
 };
 
 // the outputs of one direction's consistency check (KC); each may be null
@@ -274,6 +275,129 @@ int check_thresholds(hsflow_ctx *ctx, float rel, float abs_thr) {
     return HSFLOW_OK;
 }
 
+// ---- temporal warm start: the start of a solve --------------------------------
+// the workspace a call whose own layout takes `own` bytes needs
+size_t ws_need(const SolveSpec &S, size_t own) {
+    return pf_on(S.pf) ? align_up(own) + pf_planes_bytes(S.rows, S.cols, S.batch) : own;
+}
+
+// some solve of the call starts from a given flow: the forward one, or for a
+// bidirectional call (`bidir`) the backward one
+bool init_on(const SolveSpec &S, bool bidir) {
+    return S.init && (S.init->uf || (bidir && S.init->ub));
+}
+
+// The init's checks, the last of a call's: whole pairs, and where one is
+// given the workspace's size first, then the planes against the outputs and
+// the `need` bytes of the workspace.  The warped call reads only (uf, vf).
+int check_init(hsflow_ctx *ctx, const SolveSpec &S, bool bidir, const ByteRange *outs, int n_outs,
+               const void *ws, size_t ws_bytes, size_t need) {
+    const hsflow_flow_init *in = S.init;
+    if (!in) return HSFLOW_OK;
+    if (!in->uf != !in->vf || (bidir && !in->ub != !in->vb))
+        return fail(ctx, HSFLOW_ERR_ARG, "init flow: one plane of a pair without the other");
+    if (!init_on(S, bidir)) return HSFLOW_OK;
+    int rc = check_workspace(ctx, ws_bytes, need);
+    if (rc) return rc;
+    const size_t pb = (size_t)S.rows * S.cols * S.batch * 4;
+    const ByteRange planes[4] = {{in->uf, pb}, {in->vf, pb}, {bidir ? in->ub : nullptr, pb},
+                                 {bidir ? in->vb : nullptr, pb}};
+    for (const ByteRange &p : planes) {
+        if (bytes_overlap(p.p, p.n, ws, need))
+            return fail(ctx, HSFLOW_ERR_ARG, "init flow overlaps the workspace");
+        for (int o = 0; o < n_outs; ++o)
+            if (bytes_overlap(p.p, p.n, outs[o].p, outs[o].n))
+                return fail(ctx, HSFLOW_ERR_ARG, "init flow overlaps an output");
+    }
+    return HSFLOW_OK;
+}
+
+// KD alone
+int downflow_impl(hsflow_ctx *ctx, const float *u, const float *v, int rows, int cols, float *uc,
+                  float *vc, int rc, int cc, int batch, hipStream_t s) {
+    int bad = check_sizes(ctx, rows, cols, batch);
+    if (bad) return bad;
+    if (!u || !v || !uc || !vc) return null_pointer(ctx);
+    if (rc != (rows + 1) / 2 || cc != (cols + 1) / 2)
+        return fail(ctx, HSFLOW_ERR_ARG, "level size %dx%d is not %dx%d, the next level of %dx%d",
+                    rc, cc, (rows + 1) / 2, (cols + 1) / 2, rows, cols);
+    const size_t pb = (size_t)rows * cols * batch * 4, cb = (size_t)rc * cc * batch * 4;
+    const ByteRange in[2] = {{u, pb}, {v, pb}}, outs[2] = {{uc, cb}, {vc, cb}};
+    if (!outputs_disjoint(in, 2, outs, 2))
+        return fail(ctx, HSFLOW_ERR_ARG, "downflow outputs overlap the inputs or each other");
+    hipError_t e = hsflow::launch_downflow(u, v, rows, cols, uc, vc, rc, cc, batch, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "downflow launch");
+    return HSFLOW_OK;
+}
+
+// KP alone
+int predict_impl(hsflow_ctx *ctx, const float *ub, const float *vb, int rows, int cols, int batch,
+                 float *uf_next, float *vf_next, float *ub_next, float *vb_next, hipStream_t s) {
+    int rc = check_sizes(ctx, rows, cols, batch);
+    if (rc) return rc;
+    if (!ub || !vb) return null_pointer(ctx);
+    if (!uf_next != !vf_next || !ub_next != !vb_next)
+        return fail(ctx, HSFLOW_ERR_ARG, "predict: one plane of an output pair without the other");
+    if (!uf_next && !ub_next)
+        return fail(ctx, HSFLOW_ERR_ARG, "no output: both predicted pairs are null");
+    const size_t pb = (size_t)rows * cols * batch * 4;
+    const ByteRange in[2] = {{ub, pb}, {vb, pb}};
+    const ByteRange outs[4] = {{uf_next, pb}, {vf_next, pb}, {ub_next, pb}, {vb_next, pb}};
+    if (!outputs_disjoint(in, 2, outs, 4))
+        return fail(ctx, HSFLOW_ERR_ARG, "predicted flows overlap the inputs or each other");
+    hipError_t e = hsflow::launch_flow_predict(ub, vb, rows, cols, batch, uf_next, vf_next,
+                                               ub_next, vb_next, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "flow predict launch");
+    return HSFLOW_OK;
+}
+
+// ---- sequence mode of the bidirectional host-buffer calls ----------------------
+size_t pred_plane_bytes(int rows, int cols) { return align_up((size_t)rows * cols * 4); }
+
+void pred_planes(const hsflow_ctx *ctx, int rows, int cols, float **p) {
+    for (int k = 0; k < 4; ++k)
+        p[k] = (float *)((char *)ctx->d_pred + k * pred_plane_bytes(rows, cols));
+}
+
+// The stored prediction leaves the context, whatever the call does next (a
+// failed call drops it); where the mode is on and it has the call's size, it
+// is the call's start.
+bool take_prediction(hsflow_ctx *ctx, int rows, int cols, hsflow_flow_init *init) {
+    const bool fits = ctx->temporal && ctx->pred_valid && ctx->pred_rows == rows &&
+                      ctx->pred_cols == cols;
+    ctx->pred_valid = false;
+    if (!fits) return false;
+    float *p[4];
+    pred_planes(ctx, rows, cols, p);
+    *init = hsflow_flow_init{p[0], p[1], p[2], p[3]};
+    return true;
+}
+
+// the context's four planes, large enough for this size (the device is current)
+int grow_prediction(hsflow_ctx *ctx, int rows, int cols) {
+    if (!ctx->temporal) return HSFLOW_OK;
+    return grow(ctx, &ctx->d_pred, &ctx->d_pred_bytes, 4 * pred_plane_bytes(rows, cols));
+}
+
+// KP of the solve's (ub, vb) into them, on the context's stream: the solve
+// that started from them has read them by then
+int predict_run(hsflow_ctx *ctx, const float *ub, const float *vb, int rows, int cols) {
+    if (!ctx->temporal) return HSFLOW_OK;
+    float *p[4];
+    pred_planes(ctx, rows, cols, p);
+    hipError_t e =
+        hsflow::launch_flow_predict(ub, vb, rows, cols, 1, p[0], p[1], p[2], p[3], ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "flow predict launch");
+    ctx->pred_rows = rows, ctx->pred_cols = cols;
+    return HSFLOW_OK;
+}
+
+// the call has succeeded: its prediction is the next call's start
+int keep_prediction(hsflow_ctx *ctx, int rc) {
+    if (!rc && ctx->temporal) ctx->pred_valid = true;
+    return rc;
+}
+
 // The frames the solve sees, for a call whose own workspace layout is the
 // first `own` bytes of ws: the workspace's size with the prefilter's planes
 // behind that layout, the frames against the workspace (they must not share a
@@ -287,7 +411,7 @@ int solve_frames(hsflow_ctx *ctx, const SolveSpec &S, const PfPlan &P, const Fra
                  hipStream_t s) {
     const bool pf = pf_on(S.pf);
     const size_t n = (size_t)S.rows * S.cols * S.batch;
-    const size_t need = pf ? align_up(own) + pf_planes_bytes(S.rows, S.cols, S.batch) : own;
+    const size_t need = ws_need(S, own);
     int rc = check_workspace(ctx, ws_bytes, need);
     if (rc) return rc;
     const size_t fb = n * (grey ? 3 : elem_size(in.dtype));
@@ -349,21 +473,39 @@ int warp_gradients_impl(hsflow_ctx *ctx, const Frames &fr, int rows, int cols, i
 // the filter always has.  With a smoothness mode on, KG turns each warp's
 // (u, v) into weights -- in the Jacobi workspace's packed gradient plane, which
 // a warped solve never reads (KW sets flags[pair] = 1) -- and the iterations
-// are KJ's weighted ones; off, the launches are unchanged.
-int warped_run(hsflow_ctx *ctx, const SolveSpec &S, const Frames &F, float *u, float *v, void *ws,
-               hipStream_t s) {
+// are KJ's weighted ones; off, the launches are unchanged.  (iu, iv): the
+// start at full resolution, both or neither: KD takes it level by level into
+// the workspace's per-level (u, v) planes -- upflow overwrites all but the
+// coarsest later -- and the coarsest level starts from the last of them
+// instead of zero (levels = 1: from a copy); null launches what it always has.
+int warped_run(hsflow_ctx *ctx, const SolveSpec &S, const Frames &F, float *u, float *v,
+               const float *iu, const float *iv, void *ws, hipStream_t s) {
     const int batch = S.batch, levels = S.levels;
     const PyrLayout L = pyr_layout(S.rows, S.cols, batch, levels);
     char *base = (char *)ws;
     int rc = build_levels(ctx, F, S.rows, S.cols, batch, L, ws, s);
     if (rc) return rc;
+    if (iu && levels == 1) {
+        const size_t n = (size_t)S.rows * S.cols * batch;
+        HIP_TRY(ctx, hipMemcpyAsync(u, iu, n * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(v, iv, n * 4, hipMemcpyDeviceToDevice, s));
+    }
+    for (int l = 1; iu && l < levels; ++l) {
+        float *ul = (float *)(base + L.off[l][2]), *vl = (float *)(base + L.off[l][3]);
+        hipError_t e = hsflow::launch_downflow(iu, iv, L.R[l - 1], L.C[l - 1], ul, vl, L.R[l],
+                                               L.C[l], batch, s);
+        if (e != hipSuccess) return hip_fail(ctx, e, "downflow launch");
+        iu = ul, iv = vl;
+    }
     for (int l = levels - 1; l >= 0; --l) {
         float *ul = l ? (float *)(base + L.off[l][2]) : u;
         float *vl = l ? (float *)(base + L.off[l][3]) : v;
         const size_t n = (size_t)L.R[l] * L.C[l] * batch;
         if (l == levels - 1) {
-            HIP_TRY(ctx, hipMemsetAsync(ul, 0, n * 4, s));
-            HIP_TRY(ctx, hipMemsetAsync(vl, 0, n * 4, s));
+            if (!iu) {
+                HIP_TRY(ctx, hipMemsetAsync(ul, 0, n * 4, s));
+                HIP_TRY(ctx, hipMemsetAsync(vl, 0, n * 4, s));
+            }
         } else {
             hipError_t e = hsflow::launch_upflow(
                 (const float *)(base + L.off[l + 1][2]), (const float *)(base + L.off[l + 1][3]),
@@ -401,11 +543,16 @@ int warped_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &in, float *u,
     int rc = check_solve(ctx, S, in.dtype, &P);
     if (rc) return rc;
     if (!in.I0 || !in.I1 || !u || !v || !ws) return null_pointer(ctx);
+    const size_t own = pyr_layout(S.rows, S.cols, S.batch, S.levels).bytes;
+    const size_t pb = (size_t)S.rows * S.cols * S.batch * 4;
+    const ByteRange outs[2] = {{u, pb}, {v, pb}};
+    if ((rc = check_init(ctx, S, false, outs, 2, ws, ws_bytes, ws_need(S, own)))) return rc;
     Frames F;
-    rc = solve_frames(ctx, S, P, in, nullptr, ws, ws_bytes,
-                      pyr_layout(S.rows, S.cols, S.batch, S.levels).bytes, &F, s);
+    rc = solve_frames(ctx, S, P, in, nullptr, ws, ws_bytes, own, &F, s);
     if (rc) return rc;
-    return warped_run(ctx, S, F, u, v, ws, s);
+    const bool warm = init_on(S, false);
+    return warped_run(ctx, S, F, u, v, warm ? S.init->uf : nullptr, warm ? S.init->vf : nullptr,
+                      ws, s);
 }
 
 // ---- bidirectional warped solve + forward-backward check -------------------
@@ -437,9 +584,12 @@ int consistency_impl(hsflow_ctx *ctx, const float *uf, const float *vf, const fl
 // construction) in the one pyramid workspace, then KC per direction asked for.
 int bidir_run(hsflow_ctx *ctx, const SolveSpec &S, const Frames &F, const BidirOut &B, void *ws,
               hipStream_t s) {
-    int rc = warped_run(ctx, S, F, B.uf, B.vf, ws, s);
+    const hsflow_flow_init none{nullptr, nullptr, nullptr, nullptr};
+    const hsflow_flow_init &I = S.init ? *S.init : none;  // a null pair: that direction cold
+    int rc = warped_run(ctx, S, F, B.uf, B.vf, I.uf, I.vf, ws, s);
     if (rc) return rc;
-    if ((rc = warped_run(ctx, S, Frames{F.I1, F.I0, F.dtype}, B.ub, B.vb, ws, s))) return rc;
+    rc = warped_run(ctx, S, Frames{F.I1, F.I0, F.dtype}, B.ub, B.vb, I.ub, I.vb, ws, s);
+    if (rc) return rc;
     if (B.f.err || B.f.mask || B.f.counts) {
         rc = consistency_run(ctx, B.uf, B.vf, B.ub, B.vb, S.rows, S.cols, S.batch, B.rel,
                              B.abs_thr, B.f, s);
@@ -459,9 +609,14 @@ int bidir_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &in, const Bidi
     if (rc) return rc;
     if (!in.I0 || !in.I1 || !B.uf || !B.vf || !B.ub || !B.vb || !ws) return null_pointer(ctx);
     if ((rc = check_thresholds(ctx, B.rel, B.abs_thr))) return rc;
+    const size_t own = pyr_layout(S.rows, S.cols, S.batch, S.levels).bytes;
+    const size_t n = (size_t)S.rows * S.cols * S.batch, cb = (size_t)S.batch * 3 * 4;
+    const ByteRange outs[10] = {{B.uf, n * 4},    {B.vf, n * 4},   {B.ub, n * 4},    {B.vb, n * 4},
+                                {B.f.err, n * 4}, {B.f.mask, n},   {B.f.counts, cb},
+                                {B.b.err, n * 4}, {B.b.mask, n},   {B.b.counts, cb}};
+    if ((rc = check_init(ctx, S, true, outs, 10, ws, ws_bytes, ws_need(S, own)))) return rc;
     Frames F;
-    rc = solve_frames(ctx, S, P, in, nullptr, ws, ws_bytes,
-                      pyr_layout(S.rows, S.cols, S.batch, S.levels).bytes, &F, s);
+    rc = solve_frames(ctx, S, P, in, nullptr, ws, ws_bytes, own, &F, s);
     if (rc) return rc;
     return bidir_run(ctx, S, F, B, ws, s);
 }
@@ -610,6 +765,7 @@ int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Fr
     if (!outputs_disjoint(ins, 3, outs, 3))
         return fail(ctx, HSFLOW_ERR_ARG,
                     "interpolation outputs overlap the frames, the workspace or each other");
+    if ((rc = check_init(ctx, S, true, outs, 3, ws, ws_bytes, need))) return rc;
     char *base = (char *)ws;
     uint8_t *const grey[2] = {(uint8_t *)(base + L.gray[0]), (uint8_t *)(base + L.gray[1])};
     Frames F;
@@ -634,12 +790,18 @@ int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Fr
 // HSFLOW_F64 output and fails at once on a null context; the BGR call takes
 // U8 and F32 only and checks its arguments before the context, so that they
 // can be checked where there is no device.
-int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &S, int channels, const void *I0,
+// In sequence mode (hsflow_ctx_set_temporal) the solve starts from the
+// context's stored prediction and KP of its (ub, vb), which lie in the
+// workspace, follows it on the stream ahead of the downloads.
+int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const void *I0,
                      const void *I1, int dtype_in, size_t step0, size_t step1, float rel,
                      float abs_thr, const HostInterpOut &O) {
     const bool bgr = channels == 3;
+    SolveSpec S = spec;
     const int rows = S.rows, cols = S.cols, nt = O.nt;
     if (!bgr && !ctx) return HSFLOW_ERR_ARG;
+    hsflow_flow_init init;
+    if (ctx && take_prediction(ctx, rows, cols, &init)) S.init = &init;
     int rc = check_interp_args(ctx, O.times, nt, O.dtype_out, !bgr);
     if (rc) return rc;
     if (bgr) {
@@ -675,7 +837,7 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &S, int channels, const vo
     char *in0, *in1;
     rc = stage_pair(ctx, I0, I1, bgr ? 3 : elem_size(dtype_in), rows, cols, step0, step1,
                     ob + flb + kAlign, wsb, &in0, &in1);
-    if (rc) return rc;
+    if (rc || (rc = grow_prediction(ctx, rows, cols))) return rc;
     char *dout = (char *)ctx->d_out;
     uint8_t *dfl = (uint8_t *)(dout + ob);
     uint32_t *dtr = (uint32_t *)(dout + ob + flb);
@@ -683,6 +845,10 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &S, int channels, const vo
                       O.trusted ? dtr : nullptr};
     rc = flow_interp_impl(ctx, S, channels, Frames{in0, in1, dtype_in}, rel, abs_thr, D, ctx->d_ws,
                           ctx->d_ws_bytes, ctx->stream);
+    if (rc) return rc;
+    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, channels);
+    rc = predict_run(ctx, (const float *)((char *)ctx->d_ws + L.flow[2]),
+                     (const float *)((char *)ctx->d_ws + L.flow[3]), rows, cols);
     if (rc) return rc;
     if (O.flags)
         for (int k = 0; k < nt; ++k)
@@ -697,13 +863,14 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &S, int channels, const vo
             HIP_TRY(ctx, hipMemcpy2DAsync(O.out[k], O.out_step, dout + k * n * channels, row, row,
                                           rows, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return HSFLOW_OK;
+        return keep_prediction(ctx, HSFLOW_OK);
     }
     // f32 (widened to f64 on the way for the grey call): a plane is rows x
     // channels * cols floats
     const float *srcs[HSFLOW_MAX_TIMES];
     for (int k = 0; k < nt; ++k) srcs[k] = (const float *)dout + k * n * channels;
-    return download_planes(ctx, srcs, O.out, nt, rows, cols * channels, O.dtype_out, O.out_step);
+    return keep_prediction(ctx, download_planes(ctx, srcs, O.out, nt, rows, cols * channels,
+                                                O.dtype_out, O.out_step));
 }
 
 // a host form's spec: one pair, the context's prefilter and smoothness
@@ -711,7 +878,8 @@ SolveSpec host_spec(const hsflow_ctx *ctx, int rows, int cols, int levels, int w
                     int window, int iters, double alpha) {
     return SolveSpec{rows,  cols,         1,                        levels,
                      warps, median,       window,                   iters,
-                     (float)alpha,        ctx ? &ctx->pf : nullptr, ctx ? &ctx->sm : nullptr};
+                     (float)alpha,        ctx ? &ctx->pf : nullptr, ctx ? &ctx->sm : nullptr,
+                     nullptr};
 }
 
 }  // namespace
@@ -728,18 +896,29 @@ int hsflow_warp_gradients_device(const void *I0, const void *I1, int dtype_in, i
                                workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-int hsflow_flow_warped_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
-                                 int batch, int levels, int warps, int median, int window,
-                                 int iters, float alpha, float *u, float *v,
-                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
-                                 void *workspace, size_t workspace_bytes, void *stream) {
+int hsflow_flow_warped_init_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                   int cols, int batch, int levels, int warps, int median,
+                                   int window, int iters, float alpha, float *u, float *v,
+                                   const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                   const hsflow_flow_init *init, void *workspace,
+                                   size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm};
+    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
     return warped_impl(nullptr, S, Frames{I0, I1, dtype_in}, u, v, workspace, workspace_bytes,
                        (hipStream_t)stream);
 }
 
 // the earlier entry points: the same solve with the later options off
+int hsflow_flow_warped_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int warps, int median, int window,
+                                 int iters, float alpha, float *u, float *v,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    return hsflow_flow_warped_init_device(I0, I1, dtype_in, rows, cols, batch, levels, warps,
+                                          median, window, iters, alpha, u, v, pf, sm, nullptr,
+                                          workspace, workspace_bytes, stream);
+}
+
 int hsflow_flow_warped_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                  int batch, int levels, int warps, int median, int window,
                                  int iters, float alpha, float *u, float *v,
@@ -830,6 +1009,22 @@ int hsflow_flow_consistency_device(const float *uf, const float *vf, const float
                             CheckOut{err, mask, counts}, (hipStream_t)stream);
 }
 
+int hsflow_flow_bidir_init_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                  int batch, int levels, int warps, int median, int window,
+                                  int iters, float alpha, float rel, float abs_thr, float *uf,
+                                  float *vf, float *ub, float *vb, float *err_f, uint8_t *mask_f,
+                                  uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                  uint32_t *counts_b, const hsflow_prefilter *pf,
+                                  const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
+    const BidirOut B{uf,  vf, ub, vb, {err_f, mask_f, counts_f}, {err_b, mask_b, counts_b},
+                     rel, abs_thr};
+    return bidir_impl(nullptr, S, Frames{I0, I1, dtype_in}, B, workspace, workspace_bytes,
+                      (hipStream_t)stream);
+}
+
 int hsflow_flow_bidir_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                 int batch, int levels, int warps, int median, int window,
                                 int iters, float alpha, float rel, float abs_thr, float *uf,
@@ -838,12 +1033,10 @@ int hsflow_flow_bidir_sm_device(const void *I0, const void *I1, int dtype_in, in
                                 uint32_t *counts_b, const hsflow_prefilter *pf,
                                 const hsflow_smoothness *sm, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm};
-    const BidirOut B{uf,  vf, ub, vb, {err_f, mask_f, counts_f}, {err_b, mask_b, counts_b},
-                     rel, abs_thr};
-    return bidir_impl(nullptr, S, Frames{I0, I1, dtype_in}, B, workspace, workspace_bytes,
-                      (hipStream_t)stream);
+    return hsflow_flow_bidir_init_device(I0, I1, dtype_in, rows, cols, batch, levels, warps,
+                                         median, window, iters, alpha, rel, abs_thr, uf, vf, ub,
+                                         vb, err_f, mask_f, counts_f, err_b, mask_b, counts_b, pf,
+                                         sm, nullptr, workspace, workspace_bytes, stream);
 }
 
 int hsflow_flow_bidir_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
@@ -886,7 +1079,8 @@ int hsflow_flow_bidir_device(const void *I0, const void *I1, int dtype_in, int r
 
 // The host-buffer form of the bidirectional solve: hsflow_flow_warped_median's
 // upload and download around bidir_impl; the masks and counts come down on
-// the same stream ahead of the flows, whose download drains it.
+// the same stream ahead of the flows, whose download drains it.  In sequence
+// mode the solve starts from the stored prediction and KP of (ub, vb) follows it.
 int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in,
                              int rows, int cols, size_t in_step0, size_t in_step1, int levels,
                              int warps, int median, int window, int iters, double alpha,
@@ -894,7 +1088,9 @@ int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, in
                              int dtype_out, size_t out_step, uint8_t *mask_f, uint8_t *mask_b,
                              size_t mask_step, uint32_t *counts) {
     if (!ctx) return HSFLOW_ERR_ARG;
-    const SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
+    SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
+    hsflow_flow_init init;
+    if (take_prediction(ctx, rows, cols, &init)) S.init = &init;
     int rc = check_host_args(ctx, I0, I1, dtype_in, rows, cols, in_step0, in_step1,
                              dtype_out, out_step);
     if (rc) return rc;
@@ -912,7 +1108,7 @@ int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, in
     char *in0, *in1;
     rc = stage_pair(ctx, I0, I1, elem_size(dtype_in), rows, cols, in_step0, in_step1,
                     fb * 4 + mb * 2 + kAlign, wsb, &in0, &in1);
-    if (rc) return rc;
+    if (rc || (rc = grow_prediction(ctx, rows, cols))) return rc;
     char *out = (char *)ctx->d_out;
     float *d[4] = {(float *)out, (float *)(out + fb), (float *)(out + 2 * fb),
                    (float *)(out + 3 * fb)};
@@ -923,7 +1119,7 @@ int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, in
     const BidirOut B{d[0], d[1], d[2], d[3], cf, cb, rel, abs_thr};
     rc = bidir_impl(ctx, S, Frames{in0, in1, dtype_in}, B, ctx->d_ws, ctx->d_ws_bytes,
                     ctx->stream);
-    if (rc) return rc;
+    if (rc || (rc = predict_run(ctx, d[2], d[3], rows, cols))) return rc;
     if (mask_f)
         HIP_TRY(ctx, hipMemcpy2DAsync(mask_f, mask_step, dmf, (size_t)cols, (size_t)cols, rows,
                                       hipMemcpyDeviceToHost, ctx->stream));
@@ -938,7 +1134,8 @@ int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, in
     int np = 2;
     if (ub) srcs[np] = d[2], dsts[np++] = ub;
     if (vb) srcs[np] = d[3], dsts[np++] = vb;
-    return download_planes(ctx, srcs, dsts, np, rows, cols, dtype_out, out_step);
+    return keep_prediction(ctx, download_planes(ctx, srcs, dsts, np, rows, cols, dtype_out,
+                                                out_step));
 }
 
 int hsflow_flow_bidir(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_in, int rows,
@@ -976,6 +1173,20 @@ size_t hsflow_flow_interp_workspace_bytes(int rows, int cols, int batch, int lev
     return interp_layout(rows, cols, batch, levels, 1).bytes;
 }
 
+int hsflow_flow_interp_init_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                   int cols, int batch, int levels, int warps, int median,
+                                   int window, int iters, float alpha, float rel, float abs_thr,
+                                   const float *times, int nt, void *out, int dtype_out,
+                                   uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                   const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
+    return flow_interp_impl(nullptr, S, 1, Frames{I0, I1, dtype_in}, rel, abs_thr,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            workspace_bytes, (hipStream_t)stream);
+}
+
 int hsflow_flow_interp_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                  int batch, int levels, int warps, int median, int window,
                                  int iters, float alpha, float rel, float abs_thr,
@@ -983,11 +1194,10 @@ int hsflow_flow_interp_sm_device(const void *I0, const void *I1, int dtype_in, i
                                  uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
                                  const hsflow_smoothness *sm, void *workspace,
                                  size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm};
-    return flow_interp_impl(nullptr, S, 1, Frames{I0, I1, dtype_in}, rel, abs_thr,
-                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
-                            workspace_bytes, (hipStream_t)stream);
+    return hsflow_flow_interp_init_device(I0, I1, dtype_in, rows, cols, batch, levels, warps,
+                                          median, window, iters, alpha, rel, abs_thr, times, nt,
+                                          out, dtype_out, flags, trusted, pf, sm, nullptr,
+                                          workspace, workspace_bytes, stream);
 }
 
 int hsflow_flow_interp_pf_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
@@ -1051,6 +1261,21 @@ size_t hsflow_flow_interp_bgr_workspace_bytes(int rows, int cols, int batch, int
     return interp_layout(rows, cols, batch, levels, 3).bytes;
 }
 
+int hsflow_flow_interp_bgr_init_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                                       int cols, int batch, int levels, int warps, int median,
+                                       int window, int iters, float alpha, float rel,
+                                       float abs_thr, const float *times, int nt, void *out,
+                                       int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                       const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                       const hsflow_flow_init *init, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
+    return flow_interp_impl(nullptr, S, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rel, abs_thr,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            workspace_bytes, (hipStream_t)stream);
+}
+
 int hsflow_flow_interp_bgr_sm_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
                                      int batch, int levels, int warps, int median, int window,
                                      int iters, float alpha, float rel, float abs_thr,
@@ -1058,11 +1283,10 @@ int hsflow_flow_interp_bgr_sm_device(const uint8_t *bgr0, const uint8_t *bgr1, i
                                      uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
                                      const hsflow_smoothness *sm, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm};
-    return flow_interp_impl(nullptr, S, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rel, abs_thr,
-                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
-                            workspace_bytes, (hipStream_t)stream);
+    return hsflow_flow_interp_bgr_init_device(bgr0, bgr1, rows, cols, batch, levels, warps, median,
+                                              window, iters, alpha, rel, abs_thr, times, nt, out,
+                                              dtype_out, flags, trusted, pf, sm, nullptr,
+                                              workspace, workspace_bytes, stream);
 }
 
 int hsflow_flow_interp_bgr_pf_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
@@ -1161,6 +1385,38 @@ int hsflow_ctx_set_smoothness(hsflow_ctx *ctx, const hsflow_smoothness *sm) {
 int hsflow_ctx_smoothness(const hsflow_ctx *ctx, hsflow_smoothness *sm) {
     if (!ctx || !sm) return fail(nullptr, HSFLOW_ERR_ARG, "null %s", ctx ? "smoothness" : "context");
     *sm = ctx->sm;
+    return HSFLOW_OK;
+}
+
+int hsflow_downflow_device(const float *u, const float *v, int rows, int cols, float *uc,
+                           float *vc, int rc, int cc, int batch, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return downflow_impl(nullptr, u, v, rows, cols, uc, vc, rc, cc, batch, (hipStream_t)stream);
+}
+
+int hsflow_flow_predict_device(const float *ub, const float *vb, int rows, int cols, int batch,
+                               float *uf_next, float *vf_next, float *ub_next, float *vb_next,
+                               void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return predict_impl(nullptr, ub, vb, rows, cols, batch, uf_next, vf_next, ub_next, vb_next,
+                        (hipStream_t)stream);
+}
+
+int hsflow_ctx_set_temporal(hsflow_ctx *ctx, int on) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    ctx->temporal = on ? 1 : 0;
+    ctx->pred_valid = false;
+    return HSFLOW_OK;
+}
+
+int hsflow_ctx_temporal(const hsflow_ctx *ctx) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    return ctx->temporal;
+}
+
+int hsflow_ctx_temporal_reset(hsflow_ctx *ctx) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    ctx->pred_valid = false;
     return HSFLOW_OK;
 }
 

@@ -131,6 +131,17 @@ hipError_t launch_diffusivity(const float *u, const float *v, int rows, int cols
 bool weighted_kb_supported(int W, int KB);
 int weighted_default_kb(int W);
 hipError_t launch_jacobi_weighted(JacobiArgs a, const float *g, int W, int KB, hipStream_t s);
+// KD (hsflow_temporal.hip): a flow plane pair one level down, KU's
+// counterpart: uc = the mean of the 2 x 2 block (border replicated) halved;
+// rc, cc must be ceil(rows / 2), ceil(cols / 2)
+hipError_t launch_downflow(const float *u, const float *v, int rows, int cols, float *uc,
+                           float *vc, int rc, int cc, int batch, hipStream_t s);
+// KP (hsflow_temporal.hip): pair k's backward flow (ub, vb) -> the start of
+// pair k+1: (uf_next, vf_next) = -(ub, vb), (ub_next, vb_next) = (ub, vb)
+// sampled at (y + 8 vb, x + 8 ub), KR's bits; either output pair may be null
+hipError_t launch_flow_predict(const float *ub, const float *vb, int rows, int cols, int batch,
+                               float *uf_next, float *vf_next, float *ub_next, float *vb_next,
+                               hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

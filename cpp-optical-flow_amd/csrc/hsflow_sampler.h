@@ -1,7 +1,8 @@
 // hsflow_sampler.h -- the one text of sampling a plane at (y + 8 v, x + 8 u),
-// for the six kernels that do it: KW (hsflow_warp.hip), KC
-// (hsflow_consistency.hip), KR / KI (hsflow_interp.hip) and their colour forms
-// KRC / KIC (hsflow_interp_bgr.hip).  The displacement split, the tap
+// for the seven kernels that do it: KW (hsflow_warp.hip), KC
+// (hsflow_consistency.hip), KR / KI (hsflow_interp.hip), their colour forms
+// KRC / KIC (hsflow_interp_bgr.hip) and KP (hsflow_temporal.hip), which samples
+// a flow by itself.  The displacement split, the tap
 // positions, the three lerps and the frame test; a tile's pixel -> (x, y); the
 // quad store of a u8 plane; and the frame interpolation itself, KI's blend,
 // rounding, times and kernel over a frame policy.  Device code only.

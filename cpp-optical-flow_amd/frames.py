@@ -27,6 +27,7 @@ conversion on the GPU (hsflow_bgr_to_gray_device) and libhsflow as solver;
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -327,7 +328,7 @@ def solve_stream(src, pairs: Sequence[Tuple[int, int]], window: int, iters: int,
 # ------------------------------------------------------- frame interpolation
 def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int, iters: int,
                          alpha: float, median: int = 0, context=None, prefilter=None,
-                         smoothness=None):
+                         smoothness=None, temporal: bool = False):
     """A colour source at `factor` times its frame rate: a generator of
     (len(src) - 1) * factor + 1 BGR uint8 frames.  Every factor-th one is a
     source frame itself, untouched; between two consecutive source frames come
@@ -338,7 +339,13 @@ def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int,
     `context`: an hsflow.Context to run on (default: hsflow.default_context()).
     `prefilter`: an hsflow.Prefilter for every pair's solve (exposure steps,
     fades, flicker), as in Context.interpolate_bgr.  `smoothness`: an
-    hsflow.Smoothness for every pair's solve (sharp motion boundaries)."""
+    hsflow.Smoothness for every pair's solve (sharp motion boundaries).
+    `temporal`: run the clip in the context's sequence mode (temporal.sequence):
+    every pair but the first starts from the flow predicted from the pair
+    before it, so fewer warps do (keep `levels` and halve `warps` when motion
+    may change; levels = 1 only for steady motion; a clip with a scene cut is
+    two calls).  The context's own setting is restored when the generator ends
+    or is closed.  False solves every pair cold."""
     factor = int(factor)
     if factor < 1:
         raise ValueError("factor must be at least 1")
@@ -348,22 +355,27 @@ def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int,
     prev = _bgr_frame(src, 0)
     yield prev
     times = [j / factor for j in range(1, factor)]
-    ctx = context
-    for i in range(1, n):
-        nxt = _bgr_frame(src, i)
-        if nxt.shape != prev.shape:
-            raise FrameError("Image sizes are different")  # main.cpp:70-73
-        if times:
-            if ctx is None:
-                import hsflow
-                ctx = hsflow.default_context()
-            mid = ctx.interpolate_bgr(prev, nxt, times, levels, warps, window, iters, alpha,
-                                      median=median, out_dtype=np.uint8, prefilter=prefilter,
-                                      smoothness=smoothness)
-            for k in range(len(times)):
-                yield mid[k]
-        yield nxt
-        prev = nxt
+    ctx, started = context, False
+    with contextlib.ExitStack() as mode:
+        for i in range(1, n):
+            nxt = _bgr_frame(src, i)
+            if nxt.shape != prev.shape:
+                raise FrameError("Image sizes are different")  # main.cpp:70-73
+            if times:
+                if ctx is None:
+                    import hsflow
+                    ctx = hsflow.default_context()
+                if temporal and not started:
+                    import temporal as seq
+                    mode.enter_context(seq.sequence(ctx))  # starts without a prediction
+                    started = True
+                mid = ctx.interpolate_bgr(prev, nxt, times, levels, warps, window, iters, alpha,
+                                          median=median, out_dtype=np.uint8, prefilter=prefilter,
+                                          smoothness=smoothness)
+                for k in range(len(times)):
+                    yield mid[k]
+            yield nxt
+            prev = nxt
 
 
 def _bgr_frame(src, i: int) -> np.ndarray:

@@ -112,6 +112,12 @@ class Smoothness(collections.namedtuple("Smoothness", "mode lam")):
         return self._C(*self)
 
 
+class _CFlowInit(ctypes.Structure):
+    """hsflow_flow_init: the planes a warped solve starts from (temporal.py)."""
+    _fields_ = [("uf", ctypes.c_void_p), ("vf", ctypes.c_void_p), ("ub", ctypes.c_void_p),
+                ("vb", ctypes.c_void_p)]
+
+
 def _option(kind, value):
     """(keep-alive struct, pointer or None) of an option of `kind` (Prefilter
     or Smoothness): an instance, a plain tuple of its fields, or None."""
@@ -144,6 +150,7 @@ def _prototypes():
                        ctypes.c_size_t)
     ip, fp, vpp, text = ctypes.POINTER(i), ctypes.POINTER(f), ctypes.POINTER(vp), ctypes.c_char_p
     pf, sm = [ctypes.POINTER(_CPrefilter)], [ctypes.POINTER(_CSmoothness)]
+    init = [ctypes.POINTER(_CFlowInit)]
     shape = [i, i, i]                              # rows, cols, batch
     dev_pair = [vp, vp, i] + shape                 # I0, I1, dtype, rows, cols, batch
     dev_bgr_pair = [vp, vp] + shape                # bgr0, bgr1, rows, cols, batch
@@ -248,6 +255,19 @@ def _prototypes():
                                              + sm + tail),
         "hsflow_ctx_set_smoothness": (i, [vp] + sm),
         "hsflow_ctx_smoothness": (i, [vp] + sm),
+        # the temporal warm start (temporal.py is its public face)
+        "hsflow_downflow_device": (i, uv + [i, i] + uv + [i, i, i, vp]),
+        "hsflow_flow_predict_device": (i, uv + shape + flows + [vp]),
+        "hsflow_flow_warped_init_device": (i, dev_pair + solve + uv + pf + sm + init + tail),
+        "hsflow_flow_bidir_init_device": (i, dev_pair + solve + thresholds + bidir_out + pf + sm
+                                          + init + tail),
+        "hsflow_flow_interp_init_device": (i, dev_pair + solve + thresholds + times_out + pf + sm
+                                           + init + tail),
+        "hsflow_flow_interp_bgr_init_device": (i, dev_bgr_pair + solve + thresholds + times_out
+                                               + pf + sm + init + tail),
+        "hsflow_ctx_set_temporal": (i, [vp, i]),
+        "hsflow_ctx_temporal": (i, [vp]),
+        "hsflow_ctx_temporal_reset": (i, [vp]),
         "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
         "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
         "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),
@@ -960,6 +980,22 @@ def _interp_outputs(frames, channels, nt, out, out_dtype, flags, trusted):
     return out, flags, trusted
 
 
+def _init_entry(stem, init, dims):
+    """(entry point, its init argument) of a warped-family solve `stem`: the
+    *_sm_device call and nothing for init None, else the *_init_device call and
+    the hsflow_flow_init of `init` = (uf, vf, ub, vb), float32 CUDA planes like
+    the frames or None each; the library checks that pairs are whole."""
+    if init is None:
+        return stem + "_sm_device", ()
+    planes = tuple(init)
+    if len(planes) != 4:
+        raise HsflowError(HSFLOW_ERR_ARG, "init: need (uf, vf, ub, vb), None for a plane not given")
+    for t, name in zip(planes, ("uf", "vf", "ub", "vb")):
+        if t is not None:
+            _check_plane(t, dims[:2], dims[2], "init." + name)
+    return stem + "_init_device", (ctypes.byref(_CFlowInit(*[_ptr(t) for t in planes])),)
+
+
 def flow_device(I0, I1, window: int, iters: int, alpha: float, u=None, v=None,
                 workspace=None, stream=None):
     """Stream-ordered solve on torch CUDA tensors [B, H, W] (or [H, W]).
@@ -1001,15 +1037,23 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
     Smoothness; SMOOTH_FLOW_DRIVEN runs the g-weighted iterations
     (hsflow_flow_warped_sm_device; window 3 or 5, no more workspace).
     Stream-ordered."""
+    return _flow_warped_device(I0, I1, levels, warps, window, iters, alpha, u, v, workspace,
+                               stream, median, prefilter, smoothness)
+
+
+def _flow_warped_device(I0, I1, levels, warps, window, iters, alpha, u, v, workspace, stream,
+                        median, prefilter, smoothness, init=None):
+    """flow_warped_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     u, v = _plane(u, I0, dims, "u"), _plane(v, I0, dims, "v")
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, I0.device, pyramid_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    _device_call("hsflow_flow_warped_sm_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+    name, start = _init_entry("hsflow_flow_warped", init, dims)
+    _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
                  *_solve_args(levels, warps, median, window, iters, alpha), u.data_ptr(),
-                 v.data_ptr(), pf, sm, *_ws_args(workspace))
+                 v.data_ptr(), pf, sm, *start, *_ws_args(workspace))
     return u, v
 
 
@@ -1068,6 +1112,15 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
     median and prefilter (hsflow_flow_bidir_pf_device; prefilter_planes_bytes
     more workspace) as in flow_warped_device, for both directions.
     Stream-ordered."""
+    return _flow_bidir_device(I0, I1, levels, warps, window, iters, alpha, rel, abs, uf, vf, ub,
+                              vb, err_f, mask_f, counts_f, err_b, mask_b, counts_b, workspace,
+                              stream, median, prefilter, smoothness)
+
+
+def _flow_bidir_device(I0, I1, levels, warps, window, iters, alpha, rel, abs, uf, vf, ub, vb,
+                       err_f, mask_f, counts_f, err_b, mask_b, counts_b, workspace, stream,
+                       median, prefilter, smoothness, init=None):
+    """flow_bidir_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     flows = [_plane(t, I0, dims, name)
              for t, name in ((uf, "uf"), (vf, "vf"), (ub, "ub"), (vb, "vb"))]
@@ -1083,10 +1136,11 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, I0.device, bidir_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    _device_call("hsflow_flow_bidir_sm_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+    name, start = _init_entry("hsflow_flow_bidir", init, dims)
+    _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
                  *_solve_args(levels, warps, median, window, iters, alpha), float(rel), float(abs),
-                 *[t.data_ptr() for t in flows], *[_ptr(t) for t in outs], pf, sm,
+                 *[t.data_ptr() for t in flows], *[_ptr(t) for t in outs], pf, sm, *start,
                  *_ws_args(workspace))
     return BidirDevice(*flows, *outs)
 
@@ -1156,17 +1210,27 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
     frames themselves are sampled (hsflow_flow_interp_pf_device;
     prefilter_planes_bytes more workspace).  Returns (out, flags, trusted) as
     frame_interp_device.  Stream-ordered."""
+    return _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel,
+                               abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
+                               smoothness)
+
+
+def _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel, abs, out,
+                        out_dtype, flags, trusted, workspace, stream, prefilter, smoothness,
+                        init=None):
+    """flow_interp_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     tm = _times_array(times)
     out, flags, trusted = _interp_outputs(I0, (), len(tm), out, out_dtype, flags, trusted)
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, I0.device, flow_interp_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    _device_call("hsflow_flow_interp_sm_device", I0.device, stream, I0.data_ptr(), I1.data_ptr(),
+    name, start = _init_entry("hsflow_flow_interp", init, dims)
+    _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
                  *_solve_args(levels, warps, median, window, iters, alpha), float(rel), float(abs),
                  tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags), _ptr(trusted), pf, sm,
-                 *_ws_args(workspace))
+                 *start, *_ws_args(workspace))
     return out, flags, trusted
 
 
@@ -1243,16 +1307,26 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
     solve (hsflow_flow_interp_bgr_pf_device; prefilter_planes_bytes more
     workspace).  Returns (out, flags, trusted) as frame_interp_bgr_device.
     Stream-ordered."""
+    return _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median,
+                                   rel, abs, out, out_dtype, flags, trusted, workspace, stream,
+                                   prefilter, smoothness)
+
+
+def _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median, rel,
+                            abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
+                            smoothness, init=None):
+    """flow_interp_bgr_device, from `init` (_init_entry) where given."""
     dims = _bgr_pair(bgr0, bgr1)
     tm = _times_array(times)
     out, flags, trusted = _interp_outputs(bgr0, (3,), len(tm), out, out_dtype, flags, trusted)
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, bgr0.device, flow_interp_bgr_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    _device_call("hsflow_flow_interp_bgr_sm_device", bgr0.device, stream, bgr0.data_ptr(),
+    name, start = _init_entry("hsflow_flow_interp_bgr", init, dims)
+    _device_call(name, bgr0.device, stream, bgr0.data_ptr(),
                  bgr1.data_ptr(), *dims, *_solve_args(levels, warps, median, window, iters, alpha),
                  float(rel), float(abs), tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags),
-                 _ptr(trusted), pf, sm, *_ws_args(workspace))
+                 _ptr(trusted), pf, sm, *start, *_ws_args(workspace))
     return out, flags, trusted
 
 

@@ -66,8 +66,27 @@ class hornSchunck {
         }
     }
 
+    // Sequence mode of the context behind this object (hsflow.h,
+    // hsflow_ctx_set_temporal): the bidirectional and interpolating solves
+    // made through it start from the flow predicted from the previous call.
+    void setTemporal(bool on) { guarded([&] { impl_.setTemporal(on); }); }
+    bool temporal() {
+        bool on = false;
+        guarded([&] { on = impl_.temporal(); });
+        return on;
+    }
+    void resetTemporal() { guarded([&] { impl_.resetTemporal(); }); }
+
   private:
     hsflow::HornSchunck impl_;
+
+    template <typename F> static void guarded(F f) {
+        try {
+            f();
+        } catch (const hsflow::Error &e) {
+            CV_Error(cv::Error::StsError, e.what());
+        }
+    }
 
     void sync_params() {  // the public fields may be edited between calls
         impl_.windowSize = windowSize;

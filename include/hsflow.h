@@ -832,6 +832,124 @@ int hsflow_flow_interp_bgr_sm_device(const uint8_t *bgr0, const uint8_t *bgr1, i
 int hsflow_ctx_set_smoothness(hsflow_ctx *ctx, const hsflow_smoothness *sm);
 int hsflow_ctx_smoothness(const hsflow_ctx *ctx, hsflow_smoothness *sm);
 
+/* ---- temporal warm start: an initial flow, and sequence mode ----------------
+ * In video the motion of pair k+1 is almost the motion of pair k.  The backward
+ * flow of pair k, (ub, vb) for I1 -> I0, lives on I1's grid, and I1 is the
+ * first frame of pair k+1: under constant velocity the forward flow of pair
+ * k+1 is -(ub, vb) with no splatting, and its backward flow is (ub, vb) read
+ * where that motion lands.  The warped solves take such a flow as their start
+ * instead of zero.
+ *
+ * What it buys ("Temporal warm start"): for steady motion one level
+ * and one warp from the predicted flow match the cold 3-level, 4-warp solve;
+ * with the pyramid kept, a warm solve beats the cold solve of the same
+ * schedule.  A warm start WITHOUT the pyramid (levels = 1) cannot repair a
+ * prediction that is off by more than about a pixel.  So: keep `levels` and
+ * halve `warps` when motion may change; use levels = 1 only for steady motion;
+ * reset the prediction at a scene cut. */
+#define HSFLOW_HAS_TEMPORAL 1
+
+/* The start of a solve: dense f32 planes [batch][rows][cols], solver units,
+ * full resolution.  (uf, vf) starts the forward solve, (ub, vb) the backward
+ * solve of the bidirectional calls.  A pair that is NULL starts cold; one
+ * plane of a pair without the other is HSFLOW_ERR_ARG. */
+typedef struct hsflow_flow_init {
+    const float *uf, *vf, *ub, *vb;
+} hsflow_flow_init;
+
+/* hsflow_upflow_device's counterpart: (u, v) of a level, dense f32
+ * [batch][rows][cols], one level down into (uc, vc), [batch][rc][cc] with rc,
+ * cc the next level's size (hsflow_pyramid_level_size: ceil(n / 2); anything
+ * else is HSFLOW_ERR_ARG).  Per component, in f32, in this order:
+ *   a = u[2y][2x];               b = u[2y][min(2x+1, cols-1)]
+ *   c = u[min(2y+1, rows-1)][2x]; d = u[min(2y+1, rows-1)][min(2x+1, cols-1)]
+ *   uc[y][x] = ((a + b) + (c + d)) * 0.125f
+ * the mean of the four, halved (px of the coarser level).  NaN and inf pass
+ * through arithmetically.  The outputs must not overlap the inputs or each
+ * other.  One launch, no workspace, stream-ordered, capturable. */
+int hsflow_downflow_device(const float *u, const float *v, int rows, int cols, float *uc,
+                           float *vc, int rc, int cc, int batch, void *stream);
+
+/* Pair k's backward flow (ub, vb) into the start of pair k+1:
+ *   uf_next = -ub;  vf_next = -vb                        (the sign bit flipped)
+ *   ub_next = ub sampled at (y + 8 vb, x + 8 ub);  vb_next = vb at that point
+ * with hsflow_warp_image_device's sampler, so ub_next equals
+ * hsflow_warp_image_device(ub as an F32 frame, u = ub, v = vb) bit for bit,
+ * vb_next likewise.  Each output pair may be NULL (both planes), not both
+ * pairs.  The outputs must not overlap the inputs or each other.  One launch,
+ * no workspace, never allocates or synchronises, capturable. */
+int hsflow_flow_predict_device(const float *ub, const float *vb, int rows, int cols, int batch,
+                               float *uf_next, float *vf_next, float *ub_next, float *vb_next,
+                               void *stream);
+
+/* The four *_sm_device solves with `const hsflow_flow_init *init` after `sm`.
+ * init == NULL, or all four planes NULL, launches exactly what the *_sm_device
+ * call launches and returns its bits (those calls are the init = NULL case of
+ * these).  The forward solve starts from (uf, vf), the backward solve from
+ * (ub, vb); the warped call reads only uf and vf.  With levels = 1 the flow
+ * starts as a copy of the init.  With levels > 1 the init is reduced level by
+ * level (hsflow_downflow_device) into the workspace's per-level flow planes,
+ * which the projection up overwrites later, and the coarsest level starts from
+ * the last reduction: the workspace sizes are the *_sm_device calls'.
+ * Everything after the start is the solve unchanged; with a smoothness mode on
+ * the first warp's weights come from the init.  The init planes must not
+ * overlap the outputs or the workspace.  All arguments are checked before any
+ * device work.  The result is bit for bit what the public pieces give one
+ * after the other (pyramid, downflow, upflow, warp gradients, diffusivity,
+ * iterations, median). */
+int hsflow_flow_warped_init_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                   int cols, int batch, int levels, int warps, int median,
+                                   int window, int iters, float alpha, float *u, float *v,
+                                   const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                   const hsflow_flow_init *init, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int hsflow_flow_bidir_init_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                  int batch, int levels, int warps, int median, int window,
+                                  int iters, float alpha, float rel, float abs_thr, float *uf,
+                                  float *vf, float *ub, float *vb, float *err_f, uint8_t *mask_f,
+                                  uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                  uint32_t *counts_b, const hsflow_prefilter *pf,
+                                  const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_init_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                   int cols, int batch, int levels, int warps, int median,
+                                   int window, int iters, float alpha, float rel, float abs_thr,
+                                   const float *times, int nt, void *out, int dtype_out,
+                                   uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                   const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_bgr_init_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                                       int cols, int batch, int levels, int warps, int median,
+                                       int window, int iters, float alpha, float rel,
+                                       float abs_thr, const float *times, int nt, void *out,
+                                       int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                       const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                       const hsflow_flow_init *init, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+
+/* Sequence mode of a context: off by default, and off leaves every call
+ * exactly as it is.  On, the bidirectional host-buffer calls (hsflow_flow_bidir,
+ * hsflow_flow_bidir_median, hsflow_flow_interp, hsflow_flow_interp_bgr)
+ *   1. start from the context's stored prediction, if there is one and its
+ *      rows x cols are the call's, and
+ *   2. after the solve run hsflow_flow_predict_device on their (ub, vb) into
+ *      four planes the context owns (grow-only), on the context's stream ahead
+ *      of the download, with no extra synchronisation.
+ * The result then equals the *_init_device call started from
+ * hsflow_flow_predict_device's output for the previous call, bit for bit; the
+ * first call, and a call without a stored prediction, is the cold call.  The
+ * stored prediction is dropped by a failed call, a call of another size,
+ * hsflow_ctx_temporal_reset and hsflow_ctx_set_temporal.  Feed the calls the
+ * consecutive pairs of one clip, in order.  Keep `levels` and halve `warps`
+ * when motion may change; use levels = 1 only for steady motion; call
+ * hsflow_ctx_temporal_reset at a scene cut.  hsflow_flow_warped* has no
+ * backward flow and ignores the mode, as do hsflow_flow, hsflow_flow_bgr,
+ * hsflow_flow_pyramid and hsflow_flow_multi.  hsflow_ctx_temporal returns the
+ * mode (0 or 1; HSFLOW_ERR_ARG for a null context). */
+int hsflow_ctx_set_temporal(hsflow_ctx *ctx, int on);
+int hsflow_ctx_temporal(const hsflow_ctx *ctx);
+int hsflow_ctx_temporal_reset(hsflow_ctx *ctx);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

@@ -95,6 +95,19 @@ class Context {
         check(hsflow_ctx_smoothness(ctx_, &sm));
         return sm;
     }
+    // Sequence mode (hsflow.h, hsflow_ctx_set_temporal): the bidirectional and
+    // interpolating solves start from the flow predicted from the previous such
+    // call and leave a prediction for the next; feed them the consecutive
+    // pairs of one clip.  Keep `levels` and halve `warps` when motion may
+    // change, levels = 1 only for steady motion, resetTemporal() at a scene
+    // cut.  Off by default.
+    void setTemporal(bool on) { check(hsflow_ctx_set_temporal(ctx_, on ? 1 : 0)); }
+    bool temporal() const {
+        const int rc = hsflow_ctx_temporal(ctx_);
+        if (rc < 0) check(rc);
+        return rc != 0;
+    }
+    void resetTemporal() { check(hsflow_ctx_temporal_reset(ctx_)); }
 
   private:
     hsflow_ctx *ctx_ = nullptr;
@@ -169,6 +182,11 @@ class HornSchunck {
     void setPrefilter(const hsflow_prefilter *pf) { ctx().setPrefilter(pf); }
     // the flow-driven smoothness term for the same methods (Context::setSmoothness)
     void setSmoothness(const hsflow_smoothness *sm) { ctx().setSmoothness(sm); }
+    // sequence mode for getFlowBidir, getFrameInterp and getFrameInterpBgr
+    // (Context::setTemporal); getFlowWarped has no backward flow and ignores it
+    void setTemporal(bool on) { ctx().setTemporal(on); }
+    bool temporal() { return ctx().temporal(); }
+    void resetTemporal() { ctx().resetTemporal(); }
     void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                        int warps, std::vector<double> &u, std::vector<double> &v,
                        int median = 0, const hsflow_prefilter *prefilter = nullptr) {
