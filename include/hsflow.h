@@ -127,7 +127,29 @@ int hsflow_gradients(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
  * (NULL = the default stream of the CURRENT device: then the caller must
  * make the buffers' device current); a non-null stream's own device runs the
  * call, whatever device is current.  `workspace` is device memory of at least
- * hsflow_workspace_bytes(rows, cols, batch) bytes, 256-byte aligned. */
+ * hsflow_workspace_bytes(rows, cols, batch) bytes, 256-byte aligned.
+ *
+ * Memory contract of the device calls (tests/test_footprint.py holds every
+ * entry point below to it):
+ * - Alignment.  A plane needs the alignment of its element and no more: 4
+ *   bytes for every f32 plane (u, v, flows, init planes, err, gx / gy / gt, F32
+ *   frames) and for counts / trusted, 2 for F16 frames, 8 for F64 frames, none
+ *   for U8 and BGR frames, masks, flags and 8-bit outputs.  Only a workspace
+ *   must be 256-byte aligned.  The kernels that move 8 or 16 bytes per lane --
+ *   K2's and K4's column pairs, K4's interleaved state, which lives in the
+ *   caller's u and v between two passes -- issue dword-aligned buffer accesses,
+ *   which gfx950 takes at any 4-byte address: the same bits at every alignment.
+ * - Footprint.  A call writes its outputs and the first <its size function>
+ *   bytes of its workspace (hsflow_prefilter_planes_bytes more where a
+ *   prefilter is on) and nothing else; it never writes an input.
+ * - Prior contents.  What a workspace holds before a call never matters: any
+ *   bytes, another call's leftovers included, give the same outputs.  The one
+ *   hand-over is the documented one: the gradients hsflow_gradients_device /
+ *   hsflow_warp_gradients_device leave for the hsflow_jacobi_device /
+ *   hsflow_jacobi_weighted_device that follows in the same workspace.
+ * - u, v of a cold solve (hsflow_flow_device, hsflow_jacobi_device without
+ *   warm_start, hsflow_flow_pyramid_device, a warped solve without an init) are
+ *   write-only: never read, every element written. */
 size_t hsflow_workspace_bytes(int rows, int cols, int batch);
 
 /* Full solve: gradients + `iters` Jacobi iterations from u = v = 0.
