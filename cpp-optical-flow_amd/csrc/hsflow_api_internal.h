@@ -32,6 +32,9 @@ struct hsflow_ctx {
     // hsflow_ctx_set_smoothness: the smoothness term of the same calls' solves
     // (mode 0: the quadratic one)
     hsflow_smoothness sm{0, 0.0f};
+    // hsflow_ctx_set_finest_level: the last pyramid level the same calls solve
+    // (0: the full frame, the default)
+    int finest = 0;
     // hsflow_ctx_set_temporal: sequence mode of the bidirectional host-buffer
     // calls.  d_pred (grow-only) holds KP's four planes uf, vf, ub, vb of the
     // last such call, each align_up(pred_rows * pred_cols * 4) bytes;

@@ -21,7 +21,9 @@ namespace {
 
 // ---- what a call of the family is asked for ----------------------------------
 struct SolveSpec {
-    int rows, cols, batch, levels, warps, median, window, iters;
+    int rows, cols, batch, levels;
+    int finest;  // the last level solved; its flow goes up to level 0 bilinearly
+    int warps, median, window, iters;
     float alpha;
     const hsflow_prefilter *pf;   // null or mode 0: the frames as they are
     const hsflow_smoothness *sm;  // null or mode 0: the quadratic term
@@ -246,10 +248,18 @@ int check_iteration_args(hsflow_ctx *ctx, const SolveSpec &S) {
     return HSFLOW_OK;
 }
 
+// the finest level solved, against levels (checked before it)
+int check_finest(hsflow_ctx *ctx, const SolveSpec &S) {
+    if (S.finest < 0 || S.finest >= S.levels)
+        return fail(ctx, HSFLOW_ERR_ARG, "finest level %d outside [0, levels - 1 = %d]", S.finest,
+                    S.levels - 1);
+    return HSFLOW_OK;
+}
+
 // Everything a spec says, in the one order every call of the family reports
 // it: the prefilter (planned into *P when on), warps / window / iterations,
-// the median, the smoothness and the window it needs, levels, sizes, and the
-// frames' type.  Null pointers, thresholds and the workspace's size follow in
+// the median, the smoothness and the window it needs, levels, the finest
+// level, sizes, and the frames' type.  Null pointers, thresholds and the workspace's size follow in
 // the caller, each through its one routine.
 int check_solve(hsflow_ctx *ctx, const SolveSpec &S, int dtype_in, PfPlan *P) {
     int rc = pf_on(S.pf) ? plan_prefilter(ctx, S.pf, P) : HSFLOW_OK;
@@ -260,7 +270,8 @@ int check_solve(hsflow_ctx *ctx, const SolveSpec &S, int dtype_in, PfPlan *P) {
             return fail(ctx, HSFLOW_ERR_ARG,
                         "flow-driven smoothness needs windowSize 3 or 5, not %d", S.window);
     }
-    if ((rc = check_levels(ctx, S.levels)) || (rc = check_sizes(ctx, S.rows, S.cols, S.batch)))
+    if ((rc = check_levels(ctx, S.levels)) || (rc = check_finest(ctx, S)) ||
+        (rc = check_sizes(ctx, S.rows, S.cols, S.batch)))
         return rc;
     return check_device_dtype(ctx, dtype_in);
 }
@@ -327,6 +338,25 @@ int downflow_impl(hsflow_ctx *ctx, const float *u, const float *v, int rows, int
         return fail(ctx, HSFLOW_ERR_ARG, "downflow outputs overlap the inputs or each other");
     hipError_t e = hsflow::launch_downflow(u, v, rows, cols, uc, vc, rc, cc, batch, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "downflow launch");
+    return HSFLOW_OK;
+}
+
+// KB alone
+int upflow_bilinear_impl(hsflow_ctx *ctx, const float *uc, const float *vc, int rc, int cc,
+                         float *u, float *v, int rows, int cols, int batch, hipStream_t s) {
+    int bad = check_sizes(ctx, rows, cols, batch);
+    if (bad) return bad;
+    if (!uc || !vc || !u || !v) return null_pointer(ctx);
+    if (rc != (rows + 1) / 2 || cc != (cols + 1) / 2)
+        return fail(ctx, HSFLOW_ERR_ARG, "level size %dx%d is not %dx%d, the next level of %dx%d",
+                    rc, cc, (rows + 1) / 2, (cols + 1) / 2, rows, cols);
+    const size_t pb = (size_t)rows * cols * batch * 4, cb = (size_t)rc * cc * batch * 4;
+    const ByteRange in[2] = {{uc, cb}, {vc, cb}}, outs[2] = {{u, pb}, {v, pb}};
+    if (!outputs_disjoint(in, 2, outs, 2))
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "bilinear upflow outputs overlap the inputs or each other");
+    hipError_t e = hsflow::launch_upflow_bilinear(uc, vc, rc, cc, u, v, rows, cols, batch, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "bilinear upflow launch");
     return HSFLOW_OK;
 }
 
@@ -478,6 +508,11 @@ int warp_gradients_impl(hsflow_ctx *ctx, const Frames &fr, int rows, int cols, i
 // the workspace's per-level (u, v) planes -- upflow overwrites all but the
 // coarsest later -- and the coarsest level starts from the last of them
 // instead of zero (levels = 1: from a copy); null launches what it always has.
+// S.finest > 0: the levels below it are not solved; KB takes the flow of level
+// S.finest up through their sizes, one launch per level, into their per-level
+// planes -- which nothing else uses once the init is reduced -- and at last
+// into (u, v), which that launch alone writes.  S.finest = 0 launches what the
+// solve always has.
 int warped_run(hsflow_ctx *ctx, const SolveSpec &S, const Frames &F, float *u, float *v,
                const float *iu, const float *iv, void *ws, hipStream_t s) {
     const int batch = S.batch, levels = S.levels;
@@ -497,7 +532,7 @@ int warped_run(hsflow_ctx *ctx, const SolveSpec &S, const Frames &F, float *u, f
         if (e != hipSuccess) return hip_fail(ctx, e, "downflow launch");
         iu = ul, iv = vl;
     }
-    for (int l = levels - 1; l >= 0; --l) {
+    for (int l = levels - 1; l >= S.finest; --l) {
         float *ul = l ? (float *)(base + L.off[l][2]) : u;
         float *vl = l ? (float *)(base + L.off[l][3]) : v;
         const size_t n = (size_t)L.R[l] * L.C[l] * batch;
@@ -530,6 +565,13 @@ int warped_run(hsflow_ctx *ctx, const SolveSpec &S, const Frames &F, float *u, f
                 if (rc) return rc;
             }
         }
+    }
+    for (int l = S.finest - 1; l >= 0; --l) {
+        hipError_t e = hsflow::launch_upflow_bilinear(
+            (const float *)(base + L.off[l + 1][2]), (const float *)(base + L.off[l + 1][3]),
+            L.R[l + 1], L.C[l + 1], l ? (float *)(base + L.off[l][2]) : u,
+            l ? (float *)(base + L.off[l][3]) : v, L.R[l], L.C[l], batch, s);
+        if (e != hipSuccess) return hip_fail(ctx, e, "bilinear upflow launch");
     }
     return HSFLOW_OK;
 }
@@ -824,8 +866,8 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
             return fail(ctx, HSFLOW_ERR_ARG, "null output plane %d", k);
     if (O.flags && O.flags_step < (size_t)cols)
         return fail(ctx, HSFLOW_ERR_ARG, "flags step %zu < row bytes %d", O.flags_step, cols);
-    if ((rc = check_levels(ctx, S.levels)) || (rc = check_iteration_args(ctx, S)) ||
-        (rc = check_thresholds(ctx, rel, abs_thr)))
+    if ((rc = check_levels(ctx, S.levels)) || (rc = check_finest(ctx, S)) ||
+        (rc = check_iteration_args(ctx, S)) || (rc = check_thresholds(ctx, rel, abs_thr)))
         return rc;
     if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
     const size_t n = (size_t)rows * cols, row = (size_t)cols * channels;
@@ -873,12 +915,13 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
                                                 O.dtype_out, O.out_step));
 }
 
-// a host form's spec: one pair, the context's prefilter and smoothness
+// a host form's spec: one pair, the context's finest level, prefilter and
+// smoothness
 SolveSpec host_spec(const hsflow_ctx *ctx, int rows, int cols, int levels, int warps, int median,
                     int window, int iters, double alpha) {
-    return SolveSpec{rows,  cols,         1,                        levels,
-                     warps, median,       window,                   iters,
-                     (float)alpha,        ctx ? &ctx->pf : nullptr, ctx ? &ctx->sm : nullptr,
+    return SolveSpec{rows,   cols,   1,     levels,       ctx ? ctx->finest : 0,
+                     warps,  median, window, iters,       (float)alpha,
+                     ctx ? &ctx->pf : nullptr,            ctx ? &ctx->sm : nullptr,
                      nullptr};
 }
 
@@ -896,19 +939,31 @@ int hsflow_warp_gradients_device(const void *I0, const void *I1, int dtype_in, i
                                workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int hsflow_flow_warped_lv_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float *u, float *v,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 const hsflow_flow_init *init, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
+                      window, iters, alpha, pf,     sm,     init};
+    return warped_impl(nullptr, S, Frames{I0, I1, dtype_in}, u, v, workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+
+// the earlier entry points: the same solve with the later options off
 int hsflow_flow_warped_init_device(const void *I0, const void *I1, int dtype_in, int rows,
                                    int cols, int batch, int levels, int warps, int median,
                                    int window, int iters, float alpha, float *u, float *v,
                                    const hsflow_prefilter *pf, const hsflow_smoothness *sm,
                                    const hsflow_flow_init *init, void *workspace,
                                    size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
-    return warped_impl(nullptr, S, Frames{I0, I1, dtype_in}, u, v, workspace, workspace_bytes,
-                       (hipStream_t)stream);
+    return hsflow_flow_warped_lv_device(I0, I1, dtype_in, rows, cols, batch, levels, 0, warps,
+                                        median, window, iters, alpha, u, v, pf, sm, init,
+                                        workspace, workspace_bytes, stream);
 }
 
-// the earlier entry points: the same solve with the later options off
 int hsflow_flow_warped_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                  int batch, int levels, int warps, int median, int window,
                                  int iters, float alpha, float *u, float *v,
@@ -962,7 +1017,7 @@ int hsflow_flow_warped_median(hsflow_ctx *ctx, const void *I0, const void *I1, i
                          out_step);
     if (rc) return rc;
     if (!u || !v) return fail(ctx, HSFLOW_ERR_ARG, "null output");
-    if ((rc = check_levels(ctx, levels))) return rc;
+    if ((rc = check_levels(ctx, levels)) || (rc = check_finest(ctx, S))) return rc;
     const size_t pb = align_up((size_t)rows * cols * 4);
     const size_t wsb = hsflow_pyramid_workspace_bytes(rows, cols, 1, levels) +
                        (pf_on(S.pf) ? pf_planes_bytes(rows, cols, 1) : 0);
@@ -1009,6 +1064,23 @@ int hsflow_flow_consistency_device(const float *uf, const float *vf, const float
                             CheckOut{err, mask, counts}, (hipStream_t)stream);
 }
 
+int hsflow_flow_bidir_lv_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                int batch, int levels, int finest, int warps, int median,
+                                int window, int iters, float alpha, float rel, float abs_thr,
+                                float *uf, float *vf, float *ub, float *vb, float *err_f,
+                                uint8_t *mask_f, uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                uint32_t *counts_b, const hsflow_prefilter *pf,
+                                const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
+                      window, iters, alpha, pf,     sm,     init};
+    const BidirOut B{uf,  vf, ub, vb, {err_f, mask_f, counts_f}, {err_b, mask_b, counts_b},
+                     rel, abs_thr};
+    return bidir_impl(nullptr, S, Frames{I0, I1, dtype_in}, B, workspace, workspace_bytes,
+                      (hipStream_t)stream);
+}
+
 int hsflow_flow_bidir_init_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                   int batch, int levels, int warps, int median, int window,
                                   int iters, float alpha, float rel, float abs_thr, float *uf,
@@ -1017,12 +1089,10 @@ int hsflow_flow_bidir_init_device(const void *I0, const void *I1, int dtype_in, 
                                   uint32_t *counts_b, const hsflow_prefilter *pf,
                                   const hsflow_smoothness *sm, const hsflow_flow_init *init,
                                   void *workspace, size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
-    const BidirOut B{uf,  vf, ub, vb, {err_f, mask_f, counts_f}, {err_b, mask_b, counts_b},
-                     rel, abs_thr};
-    return bidir_impl(nullptr, S, Frames{I0, I1, dtype_in}, B, workspace, workspace_bytes,
-                      (hipStream_t)stream);
+    return hsflow_flow_bidir_lv_device(I0, I1, dtype_in, rows, cols, batch, levels, 0, warps,
+                                       median, window, iters, alpha, rel, abs_thr, uf, vf, ub, vb,
+                                       err_f, mask_f, counts_f, err_b, mask_b, counts_b, pf, sm,
+                                       init, workspace, workspace_bytes, stream);
 }
 
 int hsflow_flow_bidir_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
@@ -1095,8 +1165,8 @@ int hsflow_flow_bidir_median(hsflow_ctx *ctx, const void *I0, const void *I1, in
                              dtype_out, out_step);
     if (rc) return rc;
     if (!u || !v) return fail(ctx, HSFLOW_ERR_ARG, "null output");
-    if ((rc = check_levels(ctx, levels)) || (rc = check_iteration_args(ctx, S)) ||
-        (rc = check_thresholds(ctx, rel, abs_thr)))
+    if ((rc = check_levels(ctx, levels)) || (rc = check_finest(ctx, S)) ||
+        (rc = check_iteration_args(ctx, S)) || (rc = check_thresholds(ctx, rel, abs_thr)))
         return rc;
     if ((mask_f || mask_b) && mask_step < (size_t)cols)
         return fail(ctx, HSFLOW_ERR_ARG, "mask step %zu < row bytes %d", mask_step, cols);
@@ -1173,6 +1243,21 @@ size_t hsflow_flow_interp_workspace_bytes(int rows, int cols, int batch, int lev
     return interp_layout(rows, cols, batch, levels, 1).bytes;
 }
 
+int hsflow_flow_interp_lv_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, void *out, int dtype_out,
+                                 uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                 const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
+                      window, iters, alpha, pf,     sm,     init};
+    return flow_interp_impl(nullptr, S, 1, Frames{I0, I1, dtype_in}, rel, abs_thr,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            workspace_bytes, (hipStream_t)stream);
+}
+
 int hsflow_flow_interp_init_device(const void *I0, const void *I1, int dtype_in, int rows,
                                    int cols, int batch, int levels, int warps, int median,
                                    int window, int iters, float alpha, float rel, float abs_thr,
@@ -1180,11 +1265,10 @@ int hsflow_flow_interp_init_device(const void *I0, const void *I1, int dtype_in,
                                    uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
                                    const hsflow_smoothness *sm, const hsflow_flow_init *init,
                                    void *workspace, size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
-    return flow_interp_impl(nullptr, S, 1, Frames{I0, I1, dtype_in}, rel, abs_thr,
-                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
-                            workspace_bytes, (hipStream_t)stream);
+    return hsflow_flow_interp_lv_device(I0, I1, dtype_in, rows, cols, batch, levels, 0, warps,
+                                        median, window, iters, alpha, rel, abs_thr, times, nt, out,
+                                        dtype_out, flags, trusted, pf, sm, init, workspace,
+                                        workspace_bytes, stream);
 }
 
 int hsflow_flow_interp_sm_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
@@ -1261,6 +1345,22 @@ size_t hsflow_flow_interp_bgr_workspace_bytes(int rows, int cols, int batch, int
     return interp_layout(rows, cols, batch, levels, 3).bytes;
 }
 
+int hsflow_flow_interp_bgr_lv_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int finest, int warps, int median,
+                                     int window, int iters, float alpha, float rel,
+                                     float abs_thr, const float *times, int nt, void *out,
+                                     int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                     const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                     const hsflow_flow_init *init, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
+                      window, iters, alpha, pf,     sm,     init};
+    return flow_interp_impl(nullptr, S, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rel, abs_thr,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            workspace_bytes, (hipStream_t)stream);
+}
+
 int hsflow_flow_interp_bgr_init_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows,
                                        int cols, int batch, int levels, int warps, int median,
                                        int window, int iters, float alpha, float rel,
@@ -1269,11 +1369,10 @@ int hsflow_flow_interp_bgr_init_device(const uint8_t *bgr0, const uint8_t *bgr1,
                                        const hsflow_prefilter *pf, const hsflow_smoothness *sm,
                                        const hsflow_flow_init *init, void *workspace,
                                        size_t workspace_bytes, void *stream) {
-    DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows, cols, batch, levels, warps, median, window, iters, alpha, pf, sm, init};
-    return flow_interp_impl(nullptr, S, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rel, abs_thr,
-                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
-                            workspace_bytes, (hipStream_t)stream);
+    return hsflow_flow_interp_bgr_lv_device(bgr0, bgr1, rows, cols, batch, levels, 0, warps,
+                                            median, window, iters, alpha, rel, abs_thr, times, nt,
+                                            out, dtype_out, flags, trusted, pf, sm, init,
+                                            workspace, workspace_bytes, stream);
 }
 
 int hsflow_flow_interp_bgr_sm_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
@@ -1392,6 +1491,27 @@ int hsflow_downflow_device(const float *u, const float *v, int rows, int cols, f
                            float *vc, int rc, int cc, int batch, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     return downflow_impl(nullptr, u, v, rows, cols, uc, vc, rc, cc, batch, (hipStream_t)stream);
+}
+
+int hsflow_upflow_bilinear_device(const float *uc, const float *vc, int rc, int cc, float *u,
+                                  float *v, int rows, int cols, int batch, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return upflow_bilinear_impl(nullptr, uc, vc, rc, cc, u, v, rows, cols, batch,
+                                (hipStream_t)stream);
+}
+
+int hsflow_ctx_set_finest_level(hsflow_ctx *ctx, int finest) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    if (finest < 0 || finest >= HSFLOW_MAX_LEVELS)
+        return fail(ctx, HSFLOW_ERR_ARG, "finest level %d outside [0, %d]", finest,
+                    HSFLOW_MAX_LEVELS - 1);
+    ctx->finest = finest;
+    return HSFLOW_OK;
+}
+
+int hsflow_ctx_finest_level(const hsflow_ctx *ctx) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    return ctx->finest;
 }
 
 int hsflow_flow_predict_device(const float *ub, const float *vb, int rows, int cols, int batch,

@@ -142,6 +142,12 @@ hipError_t launch_downflow(const float *u, const float *v, int rows, int cols, f
 hipError_t launch_flow_predict(const float *ub, const float *vb, int rows, int cols, int batch,
                                float *uf_next, float *vf_next, float *ub_next, float *vb_next,
                                hipStream_t s);
+// KB (hsflow_upsample.hip): a flow plane pair one level up, bilinearly (pixel
+// centres aligned, border replicated, values doubled): the way a coarse
+// solve's flow reaches the full frame; rc, cc must be ceil(rows / 2),
+// ceil(cols / 2)
+hipError_t launch_upflow_bilinear(const float *uc, const float *vc, int rc, int cc, float *u,
+                                  float *v, int rows, int cols, int batch, hipStream_t s);
 // K4 (hsflow_strips.hip): the streaming pass for the (window, KB) pairs it
 // is built for; `slots` = waves the chip holds at its occupancy
 bool strip_supported(int W, int KB);

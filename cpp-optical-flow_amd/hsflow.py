@@ -160,6 +160,7 @@ def _prototypes():
     pyramid, pyramid_d = [i] + plain, [i] + plain_d            # levels, ...
     warped, warped_d = [i, i] + plain, [i, i] + plain_d        # levels, warps, ...
     solve, solve_d = [i, i, i] + plain, [i, i, i] + plain_d    # levels, warps, median, ...
+    solve_lv = [i] + solve                         # levels, finest, warps, median, ...
     thresholds = [f, f]                            # rel, abs
     uv, host_uv = [vp, vp], [vp, vp, i, sz]        # u, v (host: + out dtype, step)
     flows = [vp] * 4                               # uf, vf, ub, vb
@@ -268,6 +269,17 @@ def _prototypes():
         "hsflow_ctx_set_temporal": (i, [vp, i]),
         "hsflow_ctx_temporal": (i, [vp]),
         "hsflow_ctx_temporal_reset": (i, [vp]),
+        # the coarse solve: finest > 0 stops at that level, KB brings the flow up
+        "hsflow_upflow_bilinear_device": (i, [vp, vp, i, i, vp, vp] + shape + [vp]),
+        "hsflow_flow_warped_lv_device": (i, dev_pair + solve_lv + uv + pf + sm + init + tail),
+        "hsflow_flow_bidir_lv_device": (i, dev_pair + solve_lv + thresholds + bidir_out + pf + sm
+                                        + init + tail),
+        "hsflow_flow_interp_lv_device": (i, dev_pair + solve_lv + thresholds + times_out + pf + sm
+                                         + init + tail),
+        "hsflow_flow_interp_bgr_lv_device": (i, dev_bgr_pair + solve_lv + thresholds + times_out
+                                             + pf + sm + init + tail),
+        "hsflow_ctx_set_finest_level": (i, [vp, i]),
+        "hsflow_ctx_finest_level": (i, [vp]),
         "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
         "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
         "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),
@@ -405,8 +417,11 @@ def _host_uv(rows, cols, out_dtype, out=None):
     return u, v, (u.ctypes.data, v.ctypes.data, _float_code(u.dtype), u.strides[0])
 
 
-def _solve_args(levels, warps, median, window, iters, alpha):
-    return int(levels), int(warps), int(median), int(window), int(iters), float(alpha)
+def _solve_args(levels, warps, median, window, iters, alpha, *finest):
+    """levels[, finest], warps, median, window, iters, alpha as the entry points
+    take them; `finest`: nothing, or the one value of a *_lv_device call."""
+    return (int(levels), *map(int, finest), int(warps), int(median), int(window), int(iters),
+            float(alpha))
 
 
 def _times_array(times):
@@ -494,11 +509,37 @@ class Context:
         finally:
             self._set(kind, was)
 
-    def _call_with(self, prefilter, smoothness, name, *args):
-        """_call with `prefilter` and `smoothness` as the context's settings."""
-        with self._setting_as(Prefilter, prefilter), self._setting_as(Smoothness, smoothness):
+    @contextlib.contextmanager
+    def _finest_as(self, finest):
+        """`finest` as the context's finest level for one call, the setting
+        before it restored afterwards; None leaves the context's own."""
+        if finest is None:
+            yield
+            return
+        was = self._finest_level()
+        self._set_finest_level(finest)
+        try:
+            yield
+        finally:
+            self._set_finest_level(was)
+
+    def _call_with(self, prefilter, smoothness, name, *args, finest=None):
+        """_call with `prefilter`, `smoothness` and `finest` as the context's
+        settings."""
+        with self._setting_as(Prefilter, prefilter), self._setting_as(Smoothness, smoothness), \
+                self._finest_as(finest):
             rc = getattr(lib(), name)(self._p, *args)
         _check(rc, self._p)
+
+    def _set_finest_level(self, finest):
+        """hsflow_ctx_set_finest_level (coarse.set_finest_level is its public face)."""
+        self._call("hsflow_ctx_set_finest_level", int(finest))
+
+    def _finest_level(self) -> int:
+        rc = lib().hsflow_ctx_finest_level(self._p)
+        if rc < 0:
+            _check(rc, self._p)
+        return int(rc)
 
     def set_prefilter(self, prefilter=None):
         """The context's prefilter (hsflow_ctx_set_prefilter): flow_warped,
@@ -545,7 +586,7 @@ class Context:
 
     def flow_warped(self, I0, I1, levels: int, warps: int, window: int, iters: int,
                     alpha: float, out_dtype=np.float64, median: int = 0, prefilter=None,
-                    smoothness=None):
+                    smoothness=None, finest=None):
         """Warped coarse-to-fine solve for large displacements (`warps`
         re-linearisations per level, `iters` iterations each), see
         hsflow_flow_warped in include/hsflow.h.  (u, v) * SOBEL_GAIN is the
@@ -553,18 +594,21 @@ class Context:
         that size after every warp's iterations (hsflow_flow_warped_median);
         0 = none.  prefilter: a Prefilter set on the context for this call
         (None: the context's own setting, off by default).  smoothness: a
-        Smoothness, likewise (window 3 or 5 then)."""
+        Smoothness, likewise (window 3 or 5 then).  finest: the last level
+        solved, likewise (coarse.set_finest_level; None: the context's own, 0
+        by default); (u, v) are full resolution whatever it is."""
         a, b, rows, cols = _host_pair(I0, I1)
         u, v, uv = _host_uv(rows, cols, out_dtype)
         self._call_with(prefilter, smoothness, "hsflow_flow_warped_median", *_pair_args(a, b),
-                        *_solve_args(levels, warps, median, window, iters, alpha), *uv)
+                        *_solve_args(levels, warps, median, window, iters, alpha), *uv,
+                        finest=finest)
         return u, v
 
     def flow_bidir(self, I0, I1, levels: int, warps: int, window: int, iters: int,
                    alpha: float, rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                    out_dtype=np.float64, backward: bool = True, masks: bool = True,
                    counts: bool = True, out=None, mask_out=None, median: int = 0,
-                   prefilter=None, smoothness=None):
+                   prefilter=None, smoothness=None, finest=None):
         """Warped solve in both directions with the forward-backward check
         (hsflow_flow_bidir in include/hsflow.h).  Returns a BidirHost: u, v
         (I0 -> I1), ub, vb (I1 -> I0, None unless `backward`), mask_f, mask_b
@@ -573,7 +617,8 @@ class Context:
         `counts`).  `out`: an array [4, rows, >= cols] of out_dtype whose
         planes' first `cols` columns receive u, v, ub, vb (a padded row step);
         `mask_out`: likewise uint8 [2, rows, >= cols] for the masks.  median,
-        prefilter and smoothness as in flow_warped, for both directions."""
+        prefilter, smoothness and finest as in flow_warped, for both directions;
+        the check runs on the full-resolution flows."""
         a, b, rows, cols = _host_pair(I0, I1)
         if out is None:
             out = np.empty((4, rows, cols), out_dtype)
@@ -595,13 +640,14 @@ class Context:
         self._call_with(prefilter, smoothness, "hsflow_flow_bidir_median", *_pair_args(a, b),
                         *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
                         float(abs), ptr(u), ptr(v), ptr(ub), ptr(vb), _float_code(out.dtype),
-                        out.strides[1], ptr(mf), ptr(mb), mask_out.strides[1], ptr(cnt))
+                        out.strides[1], ptr(mf), ptr(mb), mask_out.strides[1], ptr(cnt),
+                        finest=finest)
         return BidirHost(u, v, ub, vb, mf, mb, cnt)
 
     def interpolate(self, I0, I1, times, levels: int, warps: int, window: int, iters: int,
                     alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                     abs: float = CONSISTENCY_ABS, out_dtype=np.float32,
-                    with_flags: bool = False, prefilter=None, smoothness=None):
+                    with_flags: bool = False, prefilter=None, smoothness=None, finest=None):
         """The frames at `times` (each in [0, 1]; at most MAX_TIMES) between I0
         and I1: the bidirectional warped solve, then the motion-compensated
         blend (hsflow_flow_interp in include/hsflow.h).  Returns an array
@@ -610,20 +656,22 @@ class Context:
         bits; 0 = both sources pass the forward-backward check), trusted uint32
         [len(times)], the pixels per frame with flags == 0.  prefilter as in
         flow_warped: the flows come from the prefiltered frames, the frames
-        themselves are sampled.  smoothness as in flow_warped."""
+        themselves are sampled.  smoothness as in flow_warped.  finest as in
+        flow_warped: the flows are solved down to that level only, the frames
+        are sampled at full resolution."""
         a, b, rows, cols = _host_pair(I0, I1)
         out, flags, trusted, outs = _host_interp_out(times, (rows, cols), out_dtype,
                                                      (np.uint8, np.float32, np.float64), with_flags)
         self._call_with(prefilter, smoothness, "hsflow_flow_interp", *_pair_args(a, b),
                         *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                        float(abs), *outs)
+                        float(abs), *outs, finest=finest)
         return (out, flags, trusted) if with_flags else out
 
     def interpolate_bgr(self, bgr0, bgr1, times, levels: int, warps: int, window: int,
                         iters: int, alpha: float, median: int = 0,
                         rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                         out_dtype=np.uint8, with_flags: bool = False, prefilter=None,
-                        smoothness=None):
+                        smoothness=None, finest=None):
         """The colour frames at `times` between two decoded 8-bit BGR frames
         (H x W x 3, strided rows accepted): uploaded as BGR, converted to grey
         and solved both ways on the GPU, then the motion-compensated blend of
@@ -631,13 +679,14 @@ class Context:
         array [len(times), rows, cols, 3] of out_dtype (uint8 or float32), or
         with_flags: (frames, flags, trusted) -- flags uint8 [len(times), rows,
         cols] and trusted uint32 [len(times)] as in interpolate.  prefilter as
-        in flow_warped, run on the grey planes; smoothness as in flow_warped."""
+        in flow_warped, run on the grey planes; smoothness and finest as in
+        flow_warped."""
         a, b, rows, cols = _host_bgr_pair(bgr0, bgr1, " (grey frames: Context.interpolate)")
         out, flags, trusted, outs = _host_interp_out(times, (rows, cols, 3), out_dtype,
                                                      (np.uint8, np.float32), with_flags)
         self._call_with(prefilter, smoothness, "hsflow_flow_interp_bgr", *_pair_args(a, b),
                         *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                        float(abs), *outs)
+                        float(abs), *outs, finest=finest)
         return (out, flags, trusted) if with_flags else out
 
     def flow_bgr(self, bgr0, bgr1, window: int, iters: int, alpha: float,
@@ -740,7 +789,7 @@ class hornSchunck:  # noqa: N801  (reference class name, hornSchunck.cpp:8)
 
 
 def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int = 1,
-            warps: int = 0, median: int = 0, prefilter=None, smoothness=None):
+            warps: int = 0, median: int = 0, prefilter=None, smoothness=None, finest: int = 0):
     """compute(I0, I1, alpha, nIter) -> (u, v): the north-star convenience
     wrapper over hornSchunck(windowSize, nIter, alpha).getFlow; levels > 1
     runs the config-5 coarse-to-fine warm start (nIter per level).  warps >= 1
@@ -749,19 +798,23 @@ def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int =
     keeps the behaviour above.  median = 3 or 5 (MEDIAN_SIZES) filters the
     flow after every warp's iterations and needs warps >= 1; so does
     prefilter (a Prefilter: the frames are locally normalised first) and so
-    does smoothness (a Smoothness: the flow-driven, edge-preserving term)."""
+    does smoothness (a Smoothness: the flow-driven, edge-preserving term) and so
+    does finest > 0 (the last level solved; its flow goes up to the full frame
+    bilinearly)."""
     if median and not warps:
         raise HsflowError(HSFLOW_ERR_ARG, f"median {median} needs the warped solve (warps >= 1)")
     if prefilter is not None and not warps:
         raise HsflowError(HSFLOW_ERR_ARG, "prefilter needs the warped solve (warps >= 1)")
     if smoothness is not None and not warps:
         raise HsflowError(HSFLOW_ERR_ARG, "smoothness needs the warped solve (warps >= 1)")
+    if finest and not warps:
+        raise HsflowError(HSFLOW_ERR_ARG, f"finest {finest} needs the warped solve (warps >= 1)")
     if warps:
         if not 1 <= int(warps) <= MAX_WARPS:
             raise HsflowError(HSFLOW_ERR_ARG, f"warps {warps} outside [1, {MAX_WARPS}]")
         return default_context().flow_warped(I0, I1, levels, warps, windowSize, nIter, alpha,
                                              median=median, prefilter=prefilter,
-                                             smoothness=smoothness)
+                                             smoothness=smoothness, finest=finest or None)
     if levels > 1:
         return default_context().flow_pyramid(I0, I1, levels, windowSize, nIter, alpha)
     return hornSchunck(windowSize, nIter, alpha).getFlow(I0, I1)
@@ -980,11 +1033,20 @@ def _interp_outputs(frames, channels, nt, out, out_dtype, flags, trusted):
     return out, flags, trusted
 
 
-def _init_entry(stem, init, dims):
-    """(entry point, its init argument) of a warped-family solve `stem`: the
-    *_sm_device call and nothing for init None, else the *_init_device call and
-    the hsflow_flow_init of `init` = (uf, vf, ub, vb), float32 CUDA planes like
-    the frames or None each; the library checks that pairs are whole."""
+def _init_entry(stem, init, dims, finest=0):
+    """(entry point, its finest argument, its init argument) of a
+    warped-family solve `stem`: the *_sm_device call and nothing for init None,
+    else the *_init_device call and the hsflow_flow_init of `init` = (uf, vf, ub,
+    vb), float32 CUDA planes like the frames or None each; the library checks
+    that pairs are whole.  finest != 0: the *_lv_device call, `finest` for
+    _solve_args and the init, NULL for None."""
+    name, start = _init_entry_0(stem, init, dims)
+    if not finest:
+        return name, (), start
+    return stem + "_lv_device", (int(finest),), start or (None,)
+
+
+def _init_entry_0(stem, init, dims):
     if init is None:
         return stem + "_sm_device", ()
     planes = tuple(init)
@@ -1024,7 +1086,7 @@ def flow_pyramid_device(I0, I1, levels: int, window: int, iters: int, alpha: flo
 
 def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
                        alpha: float, u=None, v=None, workspace=None, stream=None,
-                       median: int = 0, prefilter=None, smoothness=None):
+                       median: int = 0, prefilter=None, smoothness=None, finest: int = 0):
     """Warped coarse-to-fine solve on torch CUDA tensors [B, H, W] (uint8 /
     float16 / float32 / float64): per level `warps` times the gradients
     linearised around the current flow and `iters` Jacobi iterations.
@@ -1036,23 +1098,26 @@ def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int,
     needs prefilter_planes_bytes(rows, cols, batch) more.  smoothness: a
     Smoothness; SMOOTH_FLOW_DRIVEN runs the g-weighted iterations
     (hsflow_flow_warped_sm_device; window 3 or 5, no more workspace).
-    Stream-ordered."""
+    finest > 0: only the levels down to `finest` are solved and that flow goes
+    up to the full frame through coarse.upflow_bilinear_device
+    (hsflow_flow_warped_lv_device; the same workspace); (u, v) are full
+    resolution.  Stream-ordered."""
     return _flow_warped_device(I0, I1, levels, warps, window, iters, alpha, u, v, workspace,
-                               stream, median, prefilter, smoothness)
+                               stream, median, prefilter, smoothness, finest=finest)
 
 
 def _flow_warped_device(I0, I1, levels, warps, window, iters, alpha, u, v, workspace, stream,
-                        median, prefilter, smoothness, init=None):
+                        median, prefilter, smoothness, init=None, finest=0):
     """flow_warped_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     u, v = _plane(u, I0, dims, "u"), _plane(v, I0, dims, "v")
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, I0.device, pyramid_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    name, start = _init_entry("hsflow_flow_warped", init, dims)
+    name, lv, start = _init_entry("hsflow_flow_warped", init, dims, finest)
     _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
-                 *_solve_args(levels, warps, median, window, iters, alpha), u.data_ptr(),
+                 *_solve_args(levels, warps, median, window, iters, alpha, *lv), u.data_ptr(),
                  v.data_ptr(), pf, sm, *start, *_ws_args(workspace))
     return u, v
 
@@ -1101,7 +1166,8 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
                       rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                       uf=None, vf=None, ub=None, vb=None, err_f=None, mask_f=True,
                       counts_f=None, err_b=None, mask_b=None, counts_b=None, workspace=None,
-                      stream=None, median: int = 0, prefilter=None, smoothness=None):
+                      stream=None, median: int = 0, prefilter=None, smoothness=None,
+                      finest: int = 0):
     """Warped solve of I0 -> I1 (uf, vf) and I1 -> I0 (ub, vb) on torch CUDA
     tensors [B, H, W], then the forward-backward check each way
     (hsflow_flow_bidir_device in include/hsflow.h).  The flows equal
@@ -1110,16 +1176,17 @@ def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, 
     check.  Returns a BidirDevice, None for outputs not asked for.
     `workspace`: bidir_workspace_bytes(rows, cols, batch, levels) bytes.
     median and prefilter (hsflow_flow_bidir_pf_device; prefilter_planes_bytes
-    more workspace) as in flow_warped_device, for both directions.
-    Stream-ordered."""
+    more workspace) as in flow_warped_device, for both directions; so is
+    finest (hsflow_flow_bidir_lv_device), and the check runs on the
+    full-resolution flows.  Stream-ordered."""
     return _flow_bidir_device(I0, I1, levels, warps, window, iters, alpha, rel, abs, uf, vf, ub,
                               vb, err_f, mask_f, counts_f, err_b, mask_b, counts_b, workspace,
-                              stream, median, prefilter, smoothness)
+                              stream, median, prefilter, smoothness, finest=finest)
 
 
 def _flow_bidir_device(I0, I1, levels, warps, window, iters, alpha, rel, abs, uf, vf, ub, vb,
                        err_f, mask_f, counts_f, err_b, mask_b, counts_b, workspace, stream,
-                       median, prefilter, smoothness, init=None):
+                       median, prefilter, smoothness, init=None, finest=0):
     """flow_bidir_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     flows = [_plane(t, I0, dims, name)
@@ -1136,10 +1203,11 @@ def _flow_bidir_device(I0, I1, levels, warps, window, iters, alpha, rel, abs, uf
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, I0.device, bidir_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    name, start = _init_entry("hsflow_flow_bidir", init, dims)
+    name, lv, start = _init_entry("hsflow_flow_bidir", init, dims, finest)
     _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
-                 *_solve_args(levels, warps, median, window, iters, alpha), float(rel), float(abs),
+                 *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel),
+                 float(abs),
                  *[t.data_ptr() for t in flows], *[_ptr(t) for t in outs], pf, sm, *start,
                  *_ws_args(workspace))
     return BidirDevice(*flows, *outs)
@@ -1201,23 +1269,25 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
                        alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                        abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                        trusted=None, workspace=None, stream=None, prefilter=None,
-                       smoothness=None):
+                       smoothness=None, finest: int = 0):
     """flow_bidir_device(median=...) into planes of the workspace, then
     frame_interp_device with both masks: one call, the same bits
     (hsflow_flow_interp_device in include/hsflow.h).  `workspace`:
     flow_interp_workspace_bytes(rows, cols, batch, levels) bytes.  prefilter: a
     Prefilter; the flows then come from the prefiltered frames while the
     frames themselves are sampled (hsflow_flow_interp_pf_device;
-    prefilter_planes_bytes more workspace).  Returns (out, flags, trusted) as
+    prefilter_planes_bytes more workspace).  finest as in flow_bidir_device
+    (hsflow_flow_interp_lv_device): the flows of a coarse solve, the frames
+    sampled at full resolution.  Returns (out, flags, trusted) as
     frame_interp_device.  Stream-ordered."""
     return _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel,
                                abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
-                               smoothness)
+                               smoothness, finest=finest)
 
 
 def _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel, abs, out,
                         out_dtype, flags, trusted, workspace, stream, prefilter, smoothness,
-                        init=None):
+                        init=None, finest=0):
     """flow_interp_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     tm = _times_array(times)
@@ -1225,11 +1295,11 @@ def _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, medi
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, I0.device, flow_interp_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    name, start = _init_entry("hsflow_flow_interp", init, dims)
+    name, lv, start = _init_entry("hsflow_flow_interp", init, dims, finest)
     _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
-                 *_solve_args(levels, warps, median, window, iters, alpha), float(rel), float(abs),
-                 tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags), _ptr(trusted), pf, sm,
+                 *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel),
+                 float(abs), tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags), _ptr(trusted), pf, sm,
                  *start, *_ws_args(workspace))
     return out, flags, trusted
 
@@ -1298,23 +1368,24 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
                            alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                            abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                            trusted=None, workspace=None, stream=None, prefilter=None,
-                           smoothness=None):
+                           smoothness=None, finest: int = 0):
     """bgr_to_gray_device of both frames, flow_bidir_device(median=...) on the
     grey planes, then frame_interp_bgr_device with both masks: one call, the
     same bits (hsflow_flow_interp_bgr_device in include/hsflow.h).
     `workspace`: flow_interp_bgr_workspace_bytes(rows, cols, batch, levels)
     bytes.  prefilter: a Prefilter run on the grey planes in front of the
     solve (hsflow_flow_interp_bgr_pf_device; prefilter_planes_bytes more
-    workspace).  Returns (out, flags, trusted) as frame_interp_bgr_device.
-    Stream-ordered."""
+    workspace).  finest as in flow_interp_device
+    (hsflow_flow_interp_bgr_lv_device).  Returns (out, flags, trusted) as
+    frame_interp_bgr_device.  Stream-ordered."""
     return _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median,
                                    rel, abs, out, out_dtype, flags, trusted, workspace, stream,
-                                   prefilter, smoothness)
+                                   prefilter, smoothness, finest=finest)
 
 
 def _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median, rel,
                             abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
-                            smoothness, init=None):
+                            smoothness, init=None, finest=0):
     """flow_interp_bgr_device, from `init` (_init_entry) where given."""
     dims = _bgr_pair(bgr0, bgr1)
     tm = _times_array(times)
@@ -1322,10 +1393,9 @@ def _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alp
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     workspace = _workspace(workspace, bgr0.device, flow_interp_bgr_workspace_bytes, *dims, levels,
                            prefilter=prefilter)
-    name, start = _init_entry("hsflow_flow_interp_bgr", init, dims)
-    _device_call(name, bgr0.device, stream, bgr0.data_ptr(),
-                 bgr1.data_ptr(), *dims, *_solve_args(levels, warps, median, window, iters, alpha),
-                 float(rel), float(abs), tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags),
+    name, lv, start = _init_entry("hsflow_flow_interp_bgr", init, dims, finest)
+    _device_call(name, bgr0.device, stream, bgr0.data_ptr(), bgr1.data_ptr(), *dims,
+                 *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel), float(abs), tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags),
                  _ptr(trusted), pf, sm, *start, *_ws_args(workspace))
     return out, flags, trusted
 

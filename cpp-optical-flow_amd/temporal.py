@@ -73,49 +73,54 @@ def predict_device(ub, vb, forward=True, backward=True, out=None, stream=None):
 
 def flow_warped_device(I0, I1, levels: int, warps: int, window: int, iters: int, alpha: float,
                        u=None, v=None, workspace=None, stream=None, median: int = 0,
-                       prefilter=None, smoothness=None, init=None):
+                       prefilter=None, smoothness=None, finest: int = 0, init=None):
     """hsflow.flow_warped_device started from `init` (a FlowInit or a 4-tuple;
     only uf, vf are read): hsflow_flow_warped_init_device.  init=None is that
-    call itself."""
+    call itself.  finest as there: the init stays full resolution."""
     return hsflow._flow_warped_device(I0, I1, levels, warps, window, iters, alpha, u, v, workspace,
-                                      stream, median, prefilter, smoothness, init=init)
+                                      stream, median, prefilter, smoothness, init=init,
+                                      finest=finest)
 
 
 def flow_bidir_device(I0, I1, levels: int, warps: int, window: int, iters: int, alpha: float,
                       rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                       uf=None, vf=None, ub=None, vb=None, err_f=None, mask_f=True,
                       counts_f=None, err_b=None, mask_b=None, counts_b=None, workspace=None,
-                      stream=None, median: int = 0, prefilter=None, smoothness=None, init=None):
+                      stream=None, median: int = 0, prefilter=None, smoothness=None,
+                      finest: int = 0, init=None):
     """hsflow.flow_bidir_device started from `init`: the forward solve from
     (uf, vf), the backward one from (ub, vb) (hsflow_flow_bidir_init_device).
-    The init planes must not overlap the outputs or the workspace."""
+    The init planes must not overlap the outputs or the workspace.  finest as
+    in hsflow.flow_bidir_device."""
     return hsflow._flow_bidir_device(I0, I1, levels, warps, window, iters, alpha, rel, abs, uf, vf,
                                      ub, vb, err_f, mask_f, counts_f, err_b, mask_b, counts_b,
-                                     workspace, stream, median, prefilter, smoothness, init=init)
+                                     workspace, stream, median, prefilter, smoothness, init=init,
+                                     finest=finest)
 
 
 def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iters: int,
                        alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                        abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                        trusted=None, workspace=None, stream=None, prefilter=None,
-                       smoothness=None, init=None):
+                       smoothness=None, finest: int = 0, init=None):
     """hsflow.flow_interp_device with its solve started from `init`
-    (hsflow_flow_interp_init_device)."""
+    (hsflow_flow_interp_init_device); finest as there."""
     return hsflow._flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median,
                                       rel, abs, out, out_dtype, flags, trusted, workspace, stream,
-                                      prefilter, smoothness, init=init)
+                                      prefilter, smoothness, init=init, finest=finest)
 
 
 def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: int, iters: int,
                            alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                            abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                            trusted=None, workspace=None, stream=None, prefilter=None,
-                           smoothness=None, init=None):
+                           smoothness=None, finest: int = 0, init=None):
     """hsflow.flow_interp_bgr_device with its solve started from `init`
-    (hsflow_flow_interp_bgr_init_device)."""
+    (hsflow_flow_interp_bgr_init_device); finest as there."""
     return hsflow._flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha,
                                           median, rel, abs, out, out_dtype, flags, trusted,
-                                          workspace, stream, prefilter, smoothness, init=init)
+                                          workspace, stream, prefilter, smoothness, init=init,
+                                          finest=finest)
 
 
 # ------------------------------------------------------- sequence mode (host)
@@ -142,12 +147,15 @@ def reset(ctx):
 
 
 @contextlib.contextmanager
-def sequence(ctx):
+def sequence(ctx, finest=None):
     """Sequence mode on `ctx` inside the block, starting without a prediction;
-    the previous setting is restored afterwards."""
+    the previous setting is restored afterwards.  finest: the context's finest
+    level (coarse.set_finest_level) inside the block, restored likewise; the
+    prediction comes from the upsampled backward flow.  None leaves it."""
     was = get_temporal(ctx)
-    set_temporal(ctx, True)
-    try:
-        yield ctx
-    finally:
-        set_temporal(ctx, was)
+    with ctx._finest_as(finest):
+        set_temporal(ctx, True)
+        try:
+            yield ctx
+        finally:
+            set_temporal(ctx, was)

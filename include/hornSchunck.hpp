@@ -77,6 +77,16 @@ class hornSchunck {
     }
     void resetTemporal() { guarded([&] { impl_.resetTemporal(); }); }
 
+    // The last pyramid level the warped, bidirectional and interpolating solves
+    // made through this object solve (hsflow.h, hsflow_ctx_set_finest_level);
+    // 0, the default: the full frame.
+    void setFinestLevel(int finest) { guarded([&] { impl_.setFinestLevel(finest); }); }
+    int finestLevel() {
+        int finest = 0;
+        guarded([&] { finest = impl_.finestLevel(); });
+        return finest;
+    }
+
   private:
     hsflow::HornSchunck impl_;
 

@@ -139,6 +139,9 @@ int hsflow_gradients(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
  *   K2's and K4's column pairs, K4's interleaved state, which lives in the
  *   caller's u and v between two passes -- issue dword-aligned buffer accesses,
  *   which gfx950 takes at any 4-byte address: the same bits at every alignment.
+ *   hsflow_upflow_bilinear_device uses its 8-byte loads and 16-byte stores only
+ *   where the planes it is given are aligned for them, 4-byte accesses
+ *   elsewhere: the same bits again.
  * - Footprint.  A call writes its outputs and the first <its size function>
  *   bytes of its workspace (hsflow_prefilter_planes_bytes more where a
  *   prefilter is on) and nothing else; it never writes an input.
@@ -148,8 +151,9 @@ int hsflow_gradients(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
  *   hsflow_warp_gradients_device leave for the hsflow_jacobi_device /
  *   hsflow_jacobi_weighted_device that follows in the same workspace.
  * - u, v of a cold solve (hsflow_flow_device, hsflow_jacobi_device without
- *   warm_start, hsflow_flow_pyramid_device, a warped solve without an init) are
- *   write-only: never read, every element written. */
+ *   warm_start, hsflow_flow_pyramid_device, a warped solve without an init, a
+ *   warped solve with finest > 0 with or without one) are write-only: never
+ *   read, every element written. */
 size_t hsflow_workspace_bytes(int rows, int cols, int batch);
 
 /* Full solve: gradients + `iters` Jacobi iterations from u = v = 0.
@@ -971,6 +975,101 @@ int hsflow_flow_interp_bgr_init_device(const uint8_t *bgr0, const uint8_t *bgr1,
 int hsflow_ctx_set_temporal(hsflow_ctx *ctx, int on);
 int hsflow_ctx_temporal(const hsflow_ctx *ctx);
 int hsflow_ctx_temporal_reset(hsflow_ctx *ctx);
+
+/* ---- coarse solve: the flow at a reduced resolution, the frames at full ------
+ * Level 0 holds 1 / (1 + 1/4 + 1/16) = 76 % of a 3-level solve's pixel x
+ * iterations, and interpolation needs a flow good enough to fetch the right
+ * source pixel, not a level-0 solve.  `finest` in 0 .. levels - 1 is the last
+ * pyramid level the warped family solves:
+ *   - `levels` still counts from the full frame: the pyramid, its rounding and
+ *     the per-level schedule (init or zero start, downflow of an init, `warps`
+ *     x { warp gradients; diffusivity if asked; iterations; median }) are those
+ *     of the call without `finest`; a prefilter runs on the full frames;
+ *   - levels levels-1 .. finest are solved, levels finest-1 .. 0 are not;
+ *   - the flow of level `finest` reaches the full frame by `finest`
+ *     applications of hsflow_upflow_bilinear_device, one per level, through the
+ *     pyramid's own level sizes;
+ *   - the flows returned are full-resolution planes in solver units, as ever;
+ *     the forward-backward check runs on them at full resolution
+ *     (hsflow_flow_consistency_device), interpolation samples the
+ *     full-resolution frames, sequence mode predicts from the upsampled
+ *     (ub, vb), and an init is full resolution and is reduced level by level
+ *     all the same;
+ *   - finest = 0 launches exactly what the call without it launches and
+ *     returns its bits; finest < 0 or finest >= levels is HSFLOW_ERR_ARG before
+ *     any device work.
+ * What it buys and costs ("Coarse solve"): finest = 1 solves a
+ * quarter of the pixels; pure shifts lose nothing visible, a motion boundary
+ * becomes one coarse pixel wide. */
+#define HSFLOW_HAS_FINEST 1
+
+/* hsflow_upflow_device's bilinear counterpart, for a final flow rather than a
+ * warm start: (uc, vc), dense f32 [batch][rc][cc], one level up into (u, v),
+ * [batch][rows][cols]; rc, cc must be ceil(rows / 2), ceil(cols / 2) (anything
+ * else is HSFLOW_ERR_ARG).  Pixel centres aligned, border replicated; per
+ * component, in f32, in this order:
+ *   sy = min(max(0.5f*y - 0.25f, 0), rc-1);  y0 = floor(sy);  fy = sy - y0;
+ *   y1 = min(y0+1, rc-1);   sx, x0, fx, x1 likewise with cc
+ *   top = a[y0][x0] + fx*(a[y0][x1] - a[y0][x0])
+ *   bot = a[y1][x0] + fx*(a[y1][x1] - a[y1][x0])
+ *   out = 2 * (top + fy*(bot - top))
+ * with no multiply fused into an add.  The weights are 0, 0.25 or 0.75, exact
+ * in f32.  NaN and inf pass through arithmetically (a tap of weight 0 counts);
+ * no index leaves a pair's plane.  Planes need element alignment only.  The
+ * outputs must not overlap the inputs or each other.  u and v go in one
+ * launch; no workspace, never allocates or synchronises, capturable. */
+int hsflow_upflow_bilinear_device(const float *uc, const float *vc, int rc, int cc, float *u,
+                                  float *v, int rows, int cols, int batch, void *stream);
+
+/* The four *_init_device solves with `int finest` after `levels` (those calls
+ * are the finest = 0 case of these).  The workspaces are the *_init_device
+ * calls': the flow of level `finest` and the upsampling steps live in the
+ * per-level flow planes the workspace already has, and the outputs are
+ * written by the last step alone.  The result is bit for bit what the public
+ * pieces give one after the other (pyramid, downflow, upflow, warp gradients,
+ * diffusivity, iterations, median, bilinear upflow; then the check and the
+ * interpolation at full resolution). */
+int hsflow_flow_warped_lv_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float *u, float *v,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 const hsflow_flow_init *init, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int hsflow_flow_bidir_lv_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                int batch, int levels, int finest, int warps, int median,
+                                int window, int iters, float alpha, float rel, float abs_thr,
+                                float *uf, float *vf, float *ub, float *vb, float *err_f,
+                                uint8_t *mask_f, uint32_t *counts_f, float *err_b, uint8_t *mask_b,
+                                uint32_t *counts_b, const hsflow_prefilter *pf,
+                                const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_lv_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, void *out, int dtype_out,
+                                 uint8_t *flags, uint32_t *trusted, const hsflow_prefilter *pf,
+                                 const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_bgr_lv_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int finest, int warps, int median,
+                                     int window, int iters, float alpha, float rel,
+                                     float abs_thr, const float *times, int nt, void *out,
+                                     int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                     const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                     const hsflow_flow_init *init, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
+/* The context's finest level: the host-buffer, blocking calls
+ * hsflow_flow_warped*, hsflow_flow_bidir*, hsflow_flow_interp and
+ * hsflow_flow_interp_bgr honour it and then equal their *_lv_device form bit
+ * for bit (sequence mode included).  0, the default: the full frame.  A value
+ * outside [0, HSFLOW_MAX_LEVELS - 1] is HSFLOW_ERR_ARG and leaves the old one
+ * in place; the call that solves rejects finest >= its levels.  hsflow_flow,
+ * hsflow_flow_bgr, hsflow_flow_pyramid, hsflow_flow_multi and hsflow_gradients
+ * ignore the setting.  hsflow_ctx_finest_level reads it back (HSFLOW_ERR_ARG
+ * for a null context). */
+int hsflow_ctx_set_finest_level(hsflow_ctx *ctx, int finest);
+int hsflow_ctx_finest_level(const hsflow_ctx *ctx);
 
 /* ---- host utilities on the path to the hot loop ------------------------ */
 

@@ -108,6 +108,17 @@ class Context {
         return rc != 0;
     }
     void resetTemporal() { check(hsflow_ctx_temporal_reset(ctx_)); }
+    // The last pyramid level the same solves solve (hsflow.h,
+    // hsflow_ctx_set_finest_level): finest > 0 stops the solve at that level
+    // and brings its flow to the full frame bilinearly; frames are still
+    // interpolated at full resolution.  Must be < the call's levels.  0, the
+    // default: the full frame.
+    void setFinestLevel(int finest) { check(hsflow_ctx_set_finest_level(ctx_, finest)); }
+    int finestLevel() const {
+        const int rc = hsflow_ctx_finest_level(ctx_);
+        if (rc < 0) check(rc);
+        return rc;
+    }
 
   private:
     hsflow_ctx *ctx_ = nullptr;
@@ -187,6 +198,9 @@ class HornSchunck {
     void setTemporal(bool on) { ctx().setTemporal(on); }
     bool temporal() { return ctx().temporal(); }
     void resetTemporal() { ctx().resetTemporal(); }
+    // the last pyramid level the same methods solve (Context::setFinestLevel)
+    void setFinestLevel(int finest) { ctx().setFinestLevel(finest); }
+    int finestLevel() { return ctx().finestLevel(); }
     void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                        int warps, std::vector<double> &u, std::vector<double> &v,
                        int median = 0, const hsflow_prefilter *prefilter = nullptr) {
