@@ -249,3 +249,152 @@ def test_config5_8k_fp16_pyramid(hs):
     uo, vo = oracle.flow_pyramid(I0, I1, 3, 5, 12, 1.0, nthreads=16)
     assert norm_rel_err(u16.cpu().numpy(), uo) <= TOL
     assert norm_rel_err(v16.cpu().numpy(), vo) <= TOL
+
+
+# ---------------------------- the level planes and the projection, directly
+# hs_pyrdown_kernel through pyramid_build_device and hs_upflow_kernel through
+# upflow_device against a chain of oracle.pyrdown and the numpy projection.
+# The levels of an integer pair are bit-exact with the oracle (the header of
+# csrc/hsflow_pyramid.hip); the others within 2e-6 * l at level l: an output
+# is a sum of 25 products, at most 31 fp32 roundings including the division,
+# each at most 2^-24 of the largest partial sum, and the kernel's gain is 1,
+# so the errors of l levels add up (a float32 restatement of the kernel
+# measures 1e-7 at levels 1 and 2).  Workspaces are prefilled with 0xA5
+# bytes, outputs with NaN.
+LEVELS = 4
+LEVEL_TOL = 2e-6
+PYR_SHAPES = [(1, 1), (1, 6), (2, 3), (5, 7), (17, 33), (48, 64), (97, 161)]
+PYR_DTYPES = {"u8": np.uint8, "f16": np.float16, "f32": np.float32, "f64": np.float64}
+
+
+def _int_pair(rows, cols, batch=None, seed=31):
+    rng = np.random.default_rng(seed + 1000 * rows + cols)
+    shape = (batch, rows, cols) if batch else (rows, cols)
+    return (rng.integers(0, 256, shape).astype(np.float64),
+            rng.integers(0, 256, shape).astype(np.float64))
+
+
+def _build_levels(hs, I0, I1, levels=LEVELS):
+    """pyramid_build_device's call on NaN planes and a 0xA5 workspace:
+    ([level 1.., numpy] of I0, the same of I1)."""
+    import ctypes
+    import torch
+    t0 = torch.from_numpy(np.ascontiguousarray(I0)).cuda()
+    t1 = torch.from_numpy(np.ascontiguousarray(I1)).cuda()
+    rows, cols = I0.shape[-2:]
+    lead = tuple(I0.shape[:-2])
+    batch = int(np.prod(lead, dtype=np.int64))
+    sizes = [hs.pyramid_level_size(rows, cols, l) for l in range(1, levels)]
+    P = [[torch.full(lead + s, float("nan"), device="cuda") for s in sizes] for _ in range(2)]
+    ws = torch.full((hs.workspace_bytes(rows, cols, batch),), 0xA5, dtype=torch.uint8,
+                    device="cuda")
+    arrays = [(ctypes.c_void_p * max(1, levels - 1))(*[t.data_ptr() for t in p]) for p in P]
+    codes = {"uint8": hs.U8, "float16": hs.F16, "float32": hs.F32, "float64": hs.F64}
+    assert I1.dtype == I0.dtype
+    rc = hs.lib().hsflow_pyramid_build_device(
+        t0.data_ptr(), t1.data_ptr(), codes[I0.dtype.name], rows, cols, batch, levels,
+        arrays[0], arrays[1], ws.data_ptr(), ws.numel(),
+        torch.cuda.current_stream().cuda_stream)
+    assert rc == hs.HSFLOW_OK
+    torch.cuda.synchronize()
+    return [[t.cpu().numpy() for t in p] for p in P]
+
+
+def _chain(img, rnd, levels=LEVELS):
+    """Levels 1.. of one frame by oracle.pyrdown."""
+    out, a = [], np.asarray(img, np.float64)
+    for _ in range(1, levels):
+        a = oracle.pyrdown(a, rnd)
+        out.append(a)
+    return out
+
+
+def _levels_exact(got, frame):
+    for l, (g, r) in enumerate(zip(got, _chain(frame, True)), 1):
+        assert g.dtype == np.float32 and g.shape == r.shape, l
+        assert np.array_equal(g, r), l
+        assert g.min() >= 0 and g.max() <= 255, l
+
+
+def _levels_close(got, frame, what):
+    for l, (g, r) in enumerate(zip(got, _chain(frame, False)), 1):
+        assert g.shape == r.shape, l
+        err = norm_rel_err(g, r)
+        print(f"{what} level {l}: norm_rel_err {err:.3e} (bound {LEVEL_TOL * l:.0e})")
+        assert err <= LEVEL_TOL * l, l
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", list(PYR_DTYPES))
+@pytest.mark.parametrize("shape", PYR_SHAPES)
+def test_levels_of_integer_pairs_are_bit_exact(hs, shape, kind):
+    """Down to 1x1 and through 2- and 3-wide levels (reflect-101 bouncing
+    twice); 97x161: several blocks, odd sizes at every level."""
+    I0, I1 = _int_pair(*shape)
+    P0, P1 = _build_levels(hs, I0.astype(PYR_DTYPES[kind]), I1.astype(PYR_DTYPES[kind]))
+    _levels_exact(P0, I0)
+    _levels_exact(P1, I1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", list(PYR_DTYPES))
+@pytest.mark.parametrize("value", [0, 255])
+def test_constant_frames_stay_constant(hs, value, kind):
+    """Unit gain with the rounding: 255 must not become 254 or 256."""
+    for shape in ((5, 7), (17, 33)):
+        I = np.full(shape, value, PYR_DTYPES[kind])
+        for P in _build_levels(hs, I, I):
+            for l, g in enumerate(P, 1):
+                assert g.shape == hs.pyramid_level_size(*shape, l)
+                assert np.array_equal(g, np.full(g.shape, value, np.float32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", PYR_SHAPES)
+def test_levels_of_non_integral_pairs(hs, shape):
+    I0, I1 = _int_pair(*shape)
+    a, b = (I0 * 0.73 + 0.21).astype(np.float32), (I1 * 0.61 + 3.3).astype(np.float32)
+    P0, P1 = _build_levels(hs, a, b)
+    _levels_close(P0, a, f"{shape} I0")
+    _levels_close(P1, b, f"{shape} I1")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(5, 7), (97, 161)])
+def test_one_bad_pixel_decides_the_whole_pair(hs, shape):
+    """100.5 at the last pixel of I1: no level of either frame is rounded."""
+    I0, I1 = (x.astype(np.float32) for x in _int_pair(*shape))
+    I1[-1, -1] = 100.5
+    P0, P1 = _build_levels(hs, I0, I1)
+    _levels_close(P0, I0, f"{shape} I0 beside a bad I1")
+    _levels_close(P1, I1, f"{shape} bad I1")
+    assert not np.array_equal(P0[0], np.rint(P0[0]))
+
+
+@pytest.mark.gpu
+def test_levels_of_a_mixed_batch(hs):
+    """[integral, non-integral, integral]: each pair by its own flag."""
+    I0, I1 = (x.astype(np.float32) for x in _int_pair(17, 33, batch=3))
+    I0[1], I1[1] = I0[1] * np.float32(0.73) + np.float32(0.21), I1[1] + np.float32(0.5)
+    P0, P1 = _build_levels(hs, I0, I1)
+    for P, I, name in ((P0, I0, "I0"), (P1, I1, "I1")):
+        for k in (0, 2):
+            _levels_exact([g[k] for g in P], I[k])
+        _levels_close([g[1] for g in P], I[1], f"mixed batch {name} pair 1")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fine,coarse", [((1, 1), (1, 1)), ((2, 3), (1, 2)), ((5, 7), (3, 4)),
+                                         ((96, 160), (48, 80)), ((97, 161), (49, 81))])
+def test_upflow_is_the_doubled_nearest_projection(hs, fine, coarse):
+    import torch
+    rng = np.random.default_rng(41)
+    uc = rng.uniform(-3, 3, coarse).astype(np.float32)
+    vc = rng.uniform(-3, 3, coarse).astype(np.float32)
+    u = torch.full(fine, float("nan"), device="cuda")
+    v = torch.full(fine, float("nan"), device="cuda")
+    hs.upflow_device(torch.from_numpy(uc).cuda(), torch.from_numpy(vc).cuda(), u, v)
+    torch.cuda.synchronize()
+    for got, src in ((u, uc), (v, vc)):
+        want = 2 * np.repeat(np.repeat(src, 2, 0), 2, 1)[:fine[0], :fine[1]]
+        assert np.array_equal(got.cpu().numpy(), want)
