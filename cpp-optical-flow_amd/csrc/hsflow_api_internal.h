@@ -35,6 +35,9 @@ struct hsflow_ctx {
     // hsflow_ctx_set_finest_level: the last pyramid level the same calls solve
     // (0: the full frame, the default)
     int finest = 0;
+    // hsflow_ctx_set_projection: 1: the interpolating host calls carry the
+    // flows to each time first (KS, KIP); 0, the default: KI as it is
+    int projection = 0;
     // hsflow_ctx_set_temporal: sequence mode of the bidirectional host-buffer
     // calls.  d_pred (grow-only) holds KP's four planes uf, vf, ub, vb of the
     // last such call, each align_up(pred_rows * pred_cols * 4) bytes;

@@ -28,6 +28,9 @@ struct SolveSpec {
     const hsflow_prefilter *pf;   // null or mode 0: the frames as they are
     const hsflow_smoothness *sm;  // null or mode 0: the quadratic term
     const hsflow_flow_init *init;  // null or no plane: every solve starts cold
+    // the interpolating calls: 0, KI on the flows at the output pixel; 1, KS
+    // carries the flows to each time first and KIP reads them there
+    int projection;
 };
 
 // the outputs of one direction's consistency check (KC); each may be null
@@ -44,10 +47,12 @@ struct BidirOut {
     float rel, abs_thr;
 };
 
-// the flows and masks an interpolation (KI, KIC) reads; the masks may be null
+// the flows and masks an interpolation (KI, KIC) reads; the masks may be null.
+// cells: KS's plane, for the projected interpolation (KIP); null: KI, KIC
 struct FlowsIn {
     const float *uf, *vf, *ub, *vb;
     const uint8_t *mask_f, *mask_b;
+    const uint64_t *cells;
 };
 
 // ... and what it writes: nt frames at `times` (host), flags and trusted
@@ -702,13 +707,19 @@ int warp_image_bgr_impl(hsflow_ctx *ctx, const uint8_t *bgr, int rows, int cols,
 
 // times (host), nt and the output type of an interpolation; f64: the grey host
 // form, which widens on the way down
-int check_interp_args(hsflow_ctx *ctx, const float *times, int nt, int dtype_out, bool f64) {
+int check_times(hsflow_ctx *ctx, const float *times, int nt) {
     if (nt < 1 || nt > HSFLOW_MAX_TIMES)
         return fail(ctx, HSFLOW_ERR_ARG, "nt %d outside [1, %d]", nt, HSFLOW_MAX_TIMES);
     if (!times) return fail(ctx, HSFLOW_ERR_ARG, "null times");
     for (int k = 0; k < nt; ++k)
         if (!(times[k] >= 0.0f && times[k] <= 1.0f))  // negated: NaN fails
             return fail(ctx, HSFLOW_ERR_ARG, "time %d (%g) outside [0, 1]", k, (double)times[k]);
+    return HSFLOW_OK;
+}
+
+int check_interp_args(hsflow_ctx *ctx, const float *times, int nt, int dtype_out, bool f64) {
+    const int rc = check_times(ctx, times, nt);
+    if (rc) return rc;
     if (dtype_out != HSFLOW_F32 && dtype_out != HSFLOW_U8 && !(f64 && dtype_out == HSFLOW_F64))
         return fail(ctx, HSFLOW_ERR_ARG, f64 ? "output dtype must be U8, F32 or F64"
                                              : "device output dtype must be U8 or F32");
@@ -723,52 +734,108 @@ void interp_out_ranges(const InterpOut &O, size_t n, int batch, int channels, By
 }
 
 // KI (channels 1: frames of fr.dtype) or KIC (channels 3: 8-bit interleaved
-// BGR) on checked arguments: trusted zeroed stream-ordered, then one launch
+// BGR), or with W.cells KIP on either, on checked arguments: trusted zeroed
+// stream-ordered, then one launch
 int frame_interp_run(hsflow_ctx *ctx, int channels, const Frames &fr, int rows, int cols, int batch,
                      const FlowsIn &W, const InterpOut &O, hipStream_t s) {
     if (O.trusted) HIP_TRY(ctx, hipMemsetAsync(O.trusted, 0, (size_t)batch * O.nt * 4, s));
     const bool u8 = O.dtype_out == HSFLOW_U8;
+    hipError_t e;
     if (channels == 3) {
-        hipError_t e = hsflow::launch_frame_interp_bgr(
-            (const uint8_t *)fr.I0, (const uint8_t *)fr.I1, rows, cols, batch, W.uf, W.vf, W.ub,
-            W.vb, W.mask_f, W.mask_b, O.times, O.nt, O.out, u8, O.flags, O.trusted, s);
+        const uint8_t *b0 = (const uint8_t *)fr.I0, *b1 = (const uint8_t *)fr.I1;
+        e = W.cells ? hsflow::launch_frame_interp_bgr_proj(b0, b1, rows, cols, batch, W.uf, W.vf,
+                                                           W.ub, W.vb, W.mask_f, W.mask_b, W.cells,
+                                                           O.times, O.nt, O.out, u8, O.flags,
+                                                           O.trusted, s)
+                    : hsflow::launch_frame_interp_bgr(b0, b1, rows, cols, batch, W.uf, W.vf, W.ub,
+                                                      W.vb, W.mask_f, W.mask_b, O.times, O.nt,
+                                                      O.out, u8, O.flags, O.trusted, s);
         if (e != hipSuccess) return hip_fail(ctx, e, "BGR frame interpolation launch");
         return HSFLOW_OK;
     }
-    hipError_t e = hsflow::launch_frame_interp(fr.I0, fr.I1, fr.dtype, rows, cols, batch, W.uf, W.vf,
-                                               W.ub, W.vb, W.mask_f, W.mask_b, O.times, O.nt,
-                                               O.out, u8, O.flags, O.trusted, s);
+    e = W.cells ? hsflow::launch_frame_interp_proj(fr.I0, fr.I1, fr.dtype, rows, cols, batch, W.uf,
+                                                   W.vf, W.ub, W.vb, W.mask_f, W.mask_b, W.cells,
+                                                   O.times, O.nt, O.out, u8, O.flags, O.trusted, s)
+                : hsflow::launch_frame_interp(fr.I0, fr.I1, fr.dtype, rows, cols, batch, W.uf, W.vf,
+                                              W.ub, W.vb, W.mask_f, W.mask_b, O.times, O.nt, O.out,
+                                              u8, O.flags, O.trusted, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "frame interpolation launch");
     return HSFLOW_OK;
 }
 
-// hsflow_frame_interp_device, hsflow_frame_interp_bgr_device (fr.dtype: U8)
+// ---- flow projection (KS) -----------------------------------------------------
+int check_cells(hsflow_ctx *ctx, const void *cells) {
+    if (!cells) return null_pointer(ctx);
+    if ((uintptr_t)cells & 7) return fail(ctx, HSFLOW_ERR_ARG, "cells must be 8-byte aligned");
+    return HSFLOW_OK;
+}
+
+int check_projection(hsflow_ctx *ctx, int projection) {
+    if (projection != 0 && projection != 1)
+        return fail(ctx, HSFLOW_ERR_ARG, "projection %d is not 0 or 1", projection);
+    return HSFLOW_OK;
+}
+
+// KS on checked arguments: the cells set to all ones stream-ordered, then one
+// launch
+int project_run(hsflow_ctx *ctx, const Frames &G, int rows, int cols, int batch, const FlowsIn &W,
+                const float *times, int nt, uint64_t *cells, hipStream_t s) {
+    HIP_TRY(ctx, hipMemsetAsync(cells, 0xFF, (size_t)rows * cols * batch * nt * 8, s));
+    hipError_t e = hsflow::launch_flow_project(G.I0, G.I1, G.dtype, rows, cols, batch, W.uf, W.vf,
+                                               W.ub, W.vb, times, nt, cells, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "flow projection launch");
+    return HSFLOW_OK;
+}
+
+// hsflow_flow_project_device
+int project_impl(hsflow_ctx *ctx, const Frames &G, int rows, int cols, int batch, const FlowsIn &W,
+                 const float *times, int nt, uint64_t *cells, hipStream_t s) {
+    int rc = check_sizes(ctx, rows, cols, batch);
+    if (rc || (rc = check_device_dtype(ctx, G.dtype))) return rc;
+    if (!G.I0 || !G.I1 || !W.uf || !W.vf || !W.ub || !W.vb) return null_pointer(ctx);
+    if ((rc = check_times(ctx, times, nt)) || (rc = check_cells(ctx, cells))) return rc;
+    const size_t n = (size_t)rows * cols * batch, fb = n * elem_size(G.dtype);
+    const ByteRange in[6] = {{G.I0, fb},    {G.I1, fb},    {W.uf, n * 4},
+                             {W.vf, n * 4}, {W.ub, n * 4}, {W.vb, n * 4}};
+    const ByteRange out{cells, n * nt * 8};
+    if (!outputs_disjoint(in, 6, &out, 1))
+        return fail(ctx, HSFLOW_ERR_ARG, "cells overlap the frames or the flows");
+    return project_run(ctx, G, rows, cols, batch, W, times, nt, cells, s);
+}
+
+// hsflow_frame_interp_device, hsflow_frame_interp_bgr_device (fr.dtype: U8) and,
+// `proj`, their *_proj_device forms, which read W.cells
 int frame_interp_impl(hsflow_ctx *ctx, int channels, const Frames &fr, int rows, int cols,
-                      int batch, const FlowsIn &W, const InterpOut &O, hipStream_t s) {
+                      int batch, const FlowsIn &W, const InterpOut &O, bool proj, hipStream_t s) {
     int rc = check_sizes(ctx, rows, cols, batch);
     if (rc || (rc = check_device_dtype(ctx, fr.dtype))) return rc;
     if (!fr.I0 || !fr.I1 || !W.uf || !W.vf || !W.ub || !W.vb || !O.out) return null_pointer(ctx);
     if ((rc = check_interp_args(ctx, O.times, O.nt, O.dtype_out, false))) return rc;
+    if (proj && (rc = check_cells(ctx, W.cells))) return rc;
     const size_t n = (size_t)rows * cols * batch;
     const size_t fb = n * (channels == 3 ? 3 : elem_size(fr.dtype));
-    const ByteRange in[8] = {{fr.I0, fb},   {fr.I1, fb},   {W.uf, n * 4},  {W.vf, n * 4},
-                             {W.ub, n * 4}, {W.vb, n * 4}, {W.mask_f, n}, {W.mask_b, n}};
+    const ByteRange in[9] = {{fr.I0, fb},   {fr.I1, fb},   {W.uf, n * 4},
+                             {W.vf, n * 4}, {W.ub, n * 4}, {W.vb, n * 4},
+                             {W.mask_f, n}, {W.mask_b, n},
+                             {proj ? W.cells : nullptr, n * O.nt * 8}};
     ByteRange outs[3];
     interp_out_ranges(O, n, batch, channels, outs);
-    if (!outputs_disjoint(in, 8, outs, 3))
+    if (!outputs_disjoint(in, 9, outs, 3))
         return fail(ctx, HSFLOW_ERR_ARG,
                     "interpolation outputs overlap the inputs or each other");
     return frame_interp_run(ctx, channels, fr, rows, cols, batch, W, O, s);
 }
 
 // Workspace of the fused call: [the bidirectional solve's][uf][vf][ub][vb]
-// (f32 batch planes)[mask_f][mask_b] (u8 batch planes) and, for BGR frames,
-// [grey I0][grey I1] (u8 batch planes), each 256-byte aligned.
+// (f32 batch planes)[mask_f][mask_b] (u8 batch planes), for BGR frames
+// [grey I0][grey I1] (u8 batch planes) and, for a projected call of cell_nt
+// times, KS's [cells] (u64, batch x cell_nt planes), each 256-byte aligned.
 struct InterpLayout {
-    size_t solve_bytes, flow[4], mask[2], gray[2], bytes;
+    size_t solve_bytes, flow[4], mask[2], gray[2], cells, bytes;
 };
 
-InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channels) {
+InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channels,
+                           int cell_nt = 0) {
     InterpLayout L{};
     const size_t n = (size_t)rows * cols * batch;
     L.solve_bytes = align_up(pyr_layout(rows, cols, batch, levels).bytes);
@@ -777,6 +844,7 @@ InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channe
     for (int k = 0; k < 2; ++k) L.mask[k] = off, off += align_up(n);
     if (channels == 3)
         for (int k = 0; k < 2; ++k) L.gray[k] = off, off += align_up(n);
+    if (cell_nt > 0) L.cells = off, off += align_up(n * cell_nt * 8);
     L.bytes = off;
     return L;
 }
@@ -787,7 +855,10 @@ InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channe
 // workspace's planes (the masks only when flags or trusted needs them), then
 // KI or KIC on the frames themselves: public calls one after the other, so the
 // bits are theirs by construction.  With a prefilter the solve runs on the two
-// prefiltered f32 planes behind that layout.
+// prefiltered f32 planes behind that layout.  S.projection = 1: KS
+// (hsflow_flow_project_device) on the frames the solve ran on, into the
+// workspace's cells, stands between the solve and the interpolation, which is
+// then KIP (hsflow_frame_interp*_proj_device).
 int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Frames &in,
                      float rel, float abs_thr, const InterpOut &O, void *ws, size_t ws_bytes,
                      hipStream_t s) {
@@ -797,7 +868,9 @@ int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Fr
     if (!in.I0 || !in.I1 || !O.out || !ws) return null_pointer(ctx);
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
     if ((rc = check_interp_args(ctx, O.times, O.nt, O.dtype_out, false))) return rc;
-    const InterpLayout L = interp_layout(S.rows, S.cols, S.batch, S.levels, channels);
+    if ((rc = check_projection(ctx, S.projection))) return rc;
+    const InterpLayout L = interp_layout(S.rows, S.cols, S.batch, S.levels, channels,
+                                         S.projection ? O.nt : 0);
     const size_t need = L.bytes + (pf_on(S.pf) ? pf_planes_bytes(S.rows, S.cols, S.batch) : 0);
     const size_t n = (size_t)S.rows * S.cols * S.batch;
     const size_t fb = n * (channels == 3 ? 3 : elem_size(in.dtype));
@@ -821,8 +894,11 @@ int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Fr
     const BidirOut B{f[0], f[1], f[2], f[3], {nullptr, mf, nullptr}, {nullptr, mb, nullptr},
                      rel,  abs_thr};
     if ((rc = bidir_run(ctx, S, F, B, ws, s))) return rc;
-    return frame_interp_run(ctx, channels, in, S.rows, S.cols, S.batch,
-                            FlowsIn{f[0], f[1], f[2], f[3], mf, mb}, O, s);
+    uint64_t *cells = S.projection ? (uint64_t *)(base + L.cells) : nullptr;
+    const FlowsIn W{f[0], f[1], f[2], f[3], mf, mb, cells};
+    if (cells && (rc = project_run(ctx, F, S.rows, S.cols, S.batch, W, O.times, O.nt, cells, s)))
+        return rc;
+    return frame_interp_run(ctx, channels, in, S.rows, S.cols, S.batch, W, O, s);
 }
 
 // The host-buffer form of both: the frames go up as they are (BGR: 3 B/px),
@@ -874,7 +950,9 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
     const int dev_out = O.dtype_out == HSFLOW_U8 ? HSFLOW_U8 : HSFLOW_F32;
     // d_out: the nt frames (f32 or u8), the nt flag planes, trusted
     const size_t ob = align_up(n * nt * channels * elem_size(dev_out)), flb = align_up(n * nt);
-    const size_t wsb = interp_layout(rows, cols, 1, S.levels, channels).bytes +
+    if ((rc = check_projection(ctx, S.projection))) return rc;
+    const int cell_nt = S.projection ? nt : 0;
+    const size_t wsb = interp_layout(rows, cols, 1, S.levels, channels, cell_nt).bytes +
                        (pf_on(S.pf) ? pf_planes_bytes(rows, cols, 1) : 0);
     char *in0, *in1;
     rc = stage_pair(ctx, I0, I1, bgr ? 3 : elem_size(dtype_in), rows, cols, step0, step1,
@@ -888,7 +966,7 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
     rc = flow_interp_impl(ctx, S, channels, Frames{in0, in1, dtype_in}, rel, abs_thr, D, ctx->d_ws,
                           ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
-    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, channels);
+    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, channels, cell_nt);
     rc = predict_run(ctx, (const float *)((char *)ctx->d_ws + L.flow[2]),
                      (const float *)((char *)ctx->d_ws + L.flow[3]), rows, cols);
     if (rc) return rc;
@@ -915,14 +993,14 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
                                                 O.dtype_out, O.out_step));
 }
 
-// a host form's spec: one pair, the context's finest level, prefilter and
-// smoothness
+// a host form's spec: one pair, the context's finest level, prefilter,
+// smoothness and projection
 SolveSpec host_spec(const hsflow_ctx *ctx, int rows, int cols, int levels, int warps, int median,
                     int window, int iters, double alpha) {
     return SolveSpec{rows,   cols,   1,     levels,       ctx ? ctx->finest : 0,
                      warps,  median, window, iters,       (float)alpha,
                      ctx ? &ctx->pf : nullptr,            ctx ? &ctx->sm : nullptr,
-                     nullptr};
+                     nullptr,                             ctx ? ctx->projection : 0};
 }
 
 }  // namespace
@@ -947,7 +1025,7 @@ int hsflow_flow_warped_lv_device(const void *I0, const void *I1, int dtype_in, i
                                  size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
-                      window, iters, alpha, pf,     sm,     init};
+                      window, iters, alpha, pf,     sm,     init,  0};
     return warped_impl(nullptr, S, Frames{I0, I1, dtype_in}, u, v, workspace, workspace_bytes,
                        (hipStream_t)stream);
 }
@@ -1074,7 +1152,7 @@ int hsflow_flow_bidir_lv_device(const void *I0, const void *I1, int dtype_in, in
                                 void *workspace, size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
-                      window, iters, alpha, pf,     sm,     init};
+                      window, iters, alpha, pf,     sm,     init,  0};
     const BidirOut B{uf,  vf, ub, vb, {err_f, mask_f, counts_f}, {err_b, mask_b, counts_b},
                      rel, abs_thr};
     return bidir_impl(nullptr, S, Frames{I0, I1, dtype_in}, B, workspace, workspace_bytes,
@@ -1233,9 +1311,55 @@ int hsflow_frame_interp_device(const void *I0, const void *I1, int dtype_in, int
                                uint8_t *flags, uint32_t *trusted, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     return frame_interp_impl(nullptr, 1, Frames{I0, I1, dtype_in}, rows, cols, batch,
-                             FlowsIn{uf, vf, ub, vb, mask_f, mask_b},
-                             InterpOut{times, nt, out, dtype_out, flags, trusted},
+                             FlowsIn{uf, vf, ub, vb, mask_f, mask_b, nullptr},
+                             InterpOut{times, nt, out, dtype_out, flags, trusted}, false,
                              (hipStream_t)stream);
+}
+
+int hsflow_flow_project_device(const void *G0, const void *G1, int dtype_in, int rows, int cols,
+                               int batch, const float *uf, const float *vf, const float *ub,
+                               const float *vb, const float *times, int nt, uint64_t *cells,
+                               void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return project_impl(nullptr, Frames{G0, G1, dtype_in}, rows, cols, batch,
+                        FlowsIn{uf, vf, ub, vb, nullptr, nullptr, nullptr}, times, nt, cells,
+                        (hipStream_t)stream);
+}
+
+int hsflow_frame_interp_proj_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                    int cols, int batch, const float *uf, const float *vf,
+                                    const float *ub, const float *vb, const uint8_t *mask_f,
+                                    const uint8_t *mask_b, const uint64_t *cells,
+                                    const float *times, int nt, void *out, int dtype_out,
+                                    uint8_t *flags, uint32_t *trusted, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return frame_interp_impl(nullptr, 1, Frames{I0, I1, dtype_in}, rows, cols, batch,
+                             FlowsIn{uf, vf, ub, vb, mask_f, mask_b, cells},
+                             InterpOut{times, nt, out, dtype_out, flags, trusted}, true,
+                             (hipStream_t)stream);
+}
+
+size_t hsflow_flow_interp_pj_workspace_bytes(int rows, int cols, int batch, int levels, int nt) {
+    if (!sizes_ok(rows, cols, batch) || levels < 1 || levels > HSFLOW_MAX_LEVELS || nt < 1 ||
+        nt > HSFLOW_MAX_TIMES)
+        return 0;
+    return interp_layout(rows, cols, batch, levels, 1, nt).bytes;
+}
+
+int hsflow_flow_interp_pj_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, int projection, void *out,
+                                 int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 const hsflow_flow_init *init, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
+                      window, iters, alpha, pf,     sm,     init,  projection};
+    return flow_interp_impl(nullptr, S, 1, Frames{I0, I1, dtype_in}, rel, abs_thr,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            workspace_bytes, (hipStream_t)stream);
 }
 
 size_t hsflow_flow_interp_workspace_bytes(int rows, int cols, int batch, int levels) {
@@ -1252,7 +1376,7 @@ int hsflow_flow_interp_lv_device(const void *I0, const void *I1, int dtype_in, i
                                  void *workspace, size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
-                      window, iters, alpha, pf,     sm,     init};
+                      window, iters, alpha, pf,     sm,     init,  0};
     return flow_interp_impl(nullptr, S, 1, Frames{I0, I1, dtype_in}, rel, abs_thr,
                             InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
                             workspace_bytes, (hipStream_t)stream);
@@ -1335,9 +1459,46 @@ int hsflow_frame_interp_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int
                                    uint8_t *flags, uint32_t *trusted, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     return frame_interp_impl(nullptr, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rows, cols, batch,
-                             FlowsIn{uf, vf, ub, vb, mask_f, mask_b},
-                             InterpOut{times, nt, out, dtype_out, flags, trusted},
+                             FlowsIn{uf, vf, ub, vb, mask_f, mask_b, nullptr},
+                             InterpOut{times, nt, out, dtype_out, flags, trusted}, false,
                              (hipStream_t)stream);
+}
+
+int hsflow_frame_interp_bgr_proj_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                                        int cols, int batch, const float *uf, const float *vf,
+                                        const float *ub, const float *vb, const uint8_t *mask_f,
+                                        const uint8_t *mask_b, const uint64_t *cells,
+                                        const float *times, int nt, void *out, int dtype_out,
+                                        uint8_t *flags, uint32_t *trusted, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return frame_interp_impl(nullptr, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rows, cols, batch,
+                             FlowsIn{uf, vf, ub, vb, mask_f, mask_b, cells},
+                             InterpOut{times, nt, out, dtype_out, flags, trusted}, true,
+                             (hipStream_t)stream);
+}
+
+size_t hsflow_flow_interp_bgr_pj_workspace_bytes(int rows, int cols, int batch, int levels,
+                                                 int nt) {
+    if (!sizes_ok(rows, cols, batch) || levels < 1 || levels > HSFLOW_MAX_LEVELS || nt < 1 ||
+        nt > HSFLOW_MAX_TIMES)
+        return 0;
+    return interp_layout(rows, cols, batch, levels, 3, nt).bytes;
+}
+
+int hsflow_flow_interp_bgr_pj_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int finest, int warps, int median,
+                                     int window, int iters, float alpha, float rel,
+                                     float abs_thr, const float *times, int nt, int projection,
+                                     void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                     const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                     const hsflow_flow_init *init, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
+                      window, iters, alpha, pf,     sm,     init,  projection};
+    return flow_interp_impl(nullptr, S, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rel, abs_thr,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            workspace_bytes, (hipStream_t)stream);
 }
 
 size_t hsflow_flow_interp_bgr_workspace_bytes(int rows, int cols, int batch, int levels) {
@@ -1355,7 +1516,7 @@ int hsflow_flow_interp_bgr_lv_device(const uint8_t *bgr0, const uint8_t *bgr1, i
                                      size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
     const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
-                      window, iters, alpha, pf,     sm,     init};
+                      window, iters, alpha, pf,     sm,     init,  0};
     return flow_interp_impl(nullptr, S, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rel, abs_thr,
                             InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
                             workspace_bytes, (hipStream_t)stream);
@@ -1507,6 +1668,19 @@ int hsflow_ctx_set_finest_level(hsflow_ctx *ctx, int finest) {
                     HSFLOW_MAX_LEVELS - 1);
     ctx->finest = finest;
     return HSFLOW_OK;
+}
+
+int hsflow_ctx_set_projection(hsflow_ctx *ctx, int projection) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    const int rc = check_projection(ctx, projection);
+    if (rc) return rc;
+    ctx->projection = projection;
+    return HSFLOW_OK;
+}
+
+int hsflow_ctx_projection(const hsflow_ctx *ctx) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    return ctx->projection;
 }
 
 int hsflow_ctx_finest_level(const hsflow_ctx *ctx) {

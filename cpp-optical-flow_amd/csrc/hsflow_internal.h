@@ -107,6 +107,30 @@ hipError_t launch_frame_interp_bgr(const uint8_t *I0, const uint8_t *I1, int row
                                    const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
                                    const float *times, int nt, void *out, bool out_u8,
                                    uint8_t *flags, uint32_t *trusted, hipStream_t s);
+// KS (hsflow_project.hip): both flows carried to each of `nt` times: every pixel
+// of G0 (by uf, vf over t) and of G1 (by ub, vb over 1 - t) bids for the cell
+// it lands on with cost << 32 | dir << 31 | its index; cells [batch][nt] planes
+// of u64, all ones before the launch (the kernel takes minima).  `times` is
+// read on the host at launch.
+hipError_t launch_flow_project(const void *G0, const void *G1, int dtype_in, int rows, int cols,
+                               int batch, const float *uf, const float *vf, const float *ub,
+                               const float *vb, const float *times, int nt, uint64_t *cells,
+                               hipStream_t s);
+// KIP (hsflow_interp.hip, hsflow_interp_bgr.hip): KI and KIC with each output
+// pixel's time-t flow read at the source pixel its cell names; an empty cell
+// falls back to KI's formula and sets flag bit 16
+hipError_t launch_frame_interp_proj(const void *I0, const void *I1, int dtype_in, int rows,
+                                    int cols, int batch, const float *uf, const float *vf,
+                                    const float *ub, const float *vb, const uint8_t *mask_f,
+                                    const uint8_t *mask_b, const uint64_t *cells,
+                                    const float *times, int nt, void *out, bool out_u8,
+                                    uint8_t *flags, uint32_t *trusted, hipStream_t s);
+hipError_t launch_frame_interp_bgr_proj(const uint8_t *I0, const uint8_t *I1, int rows, int cols,
+                                        int batch, const float *uf, const float *vf,
+                                        const float *ub, const float *vb, const uint8_t *mask_f,
+                                        const uint8_t *mask_b, const uint64_t *cells,
+                                        const float *times, int nt, void *out, bool out_u8,
+                                        uint8_t *flags, uint32_t *trusted, hipStream_t s);
 // how KRC and KIC fetch the two adjacent taps of a row: as six bytes (on == 0,
 // default) or as one unaligned dword and halfword; same bits.  Returns the
 // previous setting.

@@ -122,4 +122,22 @@ hipError_t launch_frame_interp(const void *I0, const void *I1, int dtype_in, int
     return e;
 }
 
+// KIP: KI with each output pixel's time-t flow taken from the source pixel its
+// cell names (hsflow_project.hip)
+hipError_t launch_frame_interp_proj(const void *I0, const void *I1, int dtype_in, int rows,
+                                    int cols, int batch, const float *uf, const float *vf,
+                                    const float *ub, const float *vb, const uint8_t *mask_f,
+                                    const uint8_t *mask_b, const uint64_t *cells,
+                                    const float *times, int nt, void *out, bool out_u8,
+                                    uint8_t *flags, uint32_t *trusted, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;  // stays for an unknown dtype or null cells
+    if (!cells) return e;
+    dispatch_frame_type(dtype_in, [&](auto t) {
+        e = launch_frame_interp_as<GreyFrame<decltype(t)>>(I0, I1, rows, cols, batch, uf, vf, ub,
+                                                           vb, mask_f, mask_b, times, nt, out,
+                                                           out_u8, flags, trusted, s, cells);
+    });
+    return e;
+}
+
 }  // namespace hsflow

@@ -195,7 +195,21 @@ hipError_t launch_frame_interp_bgr(const uint8_t *I0, const uint8_t *I1, int row
     const auto launch = g_wide_loads.load() ? launch_frame_interp_as<BgrFrame<true>>
                                             : launch_frame_interp_as<BgrFrame<false>>;
     return launch(I0, I1, rows, cols, batch, uf, vf, ub, vb, mask_f, mask_b, times, nt, out,
-                  out_u8, flags, trusted, s);
+                  out_u8, flags, trusted, s, nullptr);
+}
+
+// KIP on BGR frames: the cells come from the grey planes (hsflow_project.hip)
+hipError_t launch_frame_interp_bgr_proj(const uint8_t *I0, const uint8_t *I1, int rows, int cols,
+                                        int batch, const float *uf, const float *vf,
+                                        const float *ub, const float *vb, const uint8_t *mask_f,
+                                        const uint8_t *mask_b, const uint64_t *cells,
+                                        const float *times, int nt, void *out, bool out_u8,
+                                        uint8_t *flags, uint32_t *trusted, hipStream_t s) {
+    if (!cells) return hipErrorInvalidValue;
+    const auto launch = g_wide_loads.load() ? launch_frame_interp_as<BgrFrame<true>>
+                                            : launch_frame_interp_as<BgrFrame<false>>;
+    return launch(I0, I1, rows, cols, batch, uf, vf, ub, vb, mask_f, mask_b, times, nt, out,
+                  out_u8, flags, trusted, s, cells);
 }
 
 }  // namespace hsflow

@@ -149,15 +149,23 @@ constexpr int kInterpThreads = 256, kInterpPix = 2, kInterpTile = kInterpThreads
 //       that starts at pixel obase of the whole output; a quad store as
 //       store_quad_u8, every lane calls
 //   kBlocksPerCu        the grid's cap
-// grid (blocks per pair, batch)
-template <typename Frame>
-__global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_kernel(
+// Proj says where the time-t flow of an output pixel comes from: false (KI,
+// KIC) from the four flows at the pixel itself; true (KIP, DESIGN.md "Flow
+// projection") from the source pixel that KS's cell [pair][time][pixel] names
+// (hsflow_project.hip: dir << 31 | source index in its low 32 bits), the
+// flows at the pixel itself only where the cell is empty (all ones), with flag
+// bit 16.  Everything behind (u0, v0), (u1, v1) is one text.  The body of both
+// kernels below; grid (blocks per pair, batch).
+constexpr uint32_t kInterpHole = 16;  // HSFLOW_INTERP_HOLE
+
+template <typename Frame, bool Proj>
+__device__ __forceinline__ void frame_interp_body(
     const typename Frame::Elem *__restrict__ I0, const typename Frame::Elem *__restrict__ I1,
     const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
     const float *__restrict__ vb, const uint8_t *__restrict__ mask_f,
-    const uint8_t *__restrict__ mask_b, int rows, int cols, InterpTimes times, int nt,
-    void *__restrict__ out, int out_u8, uint8_t *__restrict__ flags,
-    uint32_t *__restrict__ trusted) {
+    const uint8_t *__restrict__ mask_b, const uint64_t *__restrict__ cells, int rows, int cols,
+    const InterpTimes &times, int nt, void *__restrict__ out, int out_u8,
+    uint8_t *__restrict__ flags, uint32_t *__restrict__ trusted) {
     constexpr int kThreads = kInterpThreads, kPix = kInterpPix, kTile = kInterpTile;
     constexpr int kCh = Frame::kChannels;
     __shared__ uint32_t block_trusted[kInterpMaxTimes];
@@ -183,8 +191,10 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_kernel(
             const int p = min(pk[k], plane - 1);
             const XY q = pixel_xy(p, cols, inv_cols);
             x[k] = q.x, y[k] = q.y;
-            fu[k] = uf[base + p], fv[k] = vf[base + p];
-            bu[k] = ub[base + p], bv[k] = vb[base + p];
+            if constexpr (!Proj) {
+                fu[k] = uf[base + p], fv[k] = vf[base + p];
+                bu[k] = ub[base + p], bv[k] = vb[base + p];
+            }
         }
         for (int ti = 0; ti < nt; ++ti) {
             const float tt = times.t[ti];
@@ -194,8 +204,32 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_kernel(
 #pragma unroll
             for (int k = 0; k < kPix; ++k) {
                 const bool valid = pk[k] < plane;
-                const float u0 = b * bu[k] - a * fu[k], v0 = b * bv[k] - a * fv[k];
-                const float u1 = c * fu[k] - a * bu[k], v1 = c * fv[k] - a * bv[k];
+                float u0, v0, u1, v1;
+                uint32_t fl = 0;
+                if constexpr (Proj) {
+                    const int p = min(pk[k], plane - 1);
+                    const uint64_t cell = cells[obase + p];
+                    if (cell == ~0ull) {  // nothing landed here: KI's flow
+                        const float hfu = uf[base + p], hfv = vf[base + p];
+                        const float hbu = ub[base + p], hbv = vb[base + p];
+                        u0 = b * hbu - a * hfu, v0 = b * hbv - a * hfv;
+                        u1 = c * hfu - a * hbu, v1 = c * hfv - a * hbv;
+                        fl = kInterpHole;
+                    } else {
+                        // KS wrote an index below `plane`; a foreign cell
+                        // plane cannot lead out of the pair's either
+                        const size_t src = base + min((uint32_t)cell & 0x7fffffffu,
+                                                      (uint32_t)(plane - 1));
+                        const bool back = ((uint32_t)cell >> 31) != 0;
+                        const float ut = back ? -ub[src] : uf[src];
+                        const float vt = back ? -vb[src] : vf[src];
+                        u0 = -tt * ut, v0 = -tt * vt;
+                        u1 = s * ut, v1 = s * vt;
+                    }
+                } else {
+                    u0 = b * bu[k] - a * fu[k], v0 = b * bv[k] - a * fv[k];
+                    u1 = c * fu[k] - a * bu[k], v1 = c * fv[k] - a * bv[k];
+                }
                 bool in0, in1;
                 int n0, n1;
                 const Taps t0 = sample_taps(rows, cols, x[k], y[k], u0, v0, in0, n0);
@@ -214,7 +248,7 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_kernel(
 #pragma unroll
                     for (int ch = 0; ch < kCh; ++ch) o.c[ch] = blend(wt, s0.c[ch], s1.c[ch]);
                 }
-                uint32_t fl = (in0 ? 0u : 1u) | (in1 ? 0u : 2u);
+                fl |= (in0 ? 0u : 1u) | (in1 ? 0u : 2u);
                 if (mf) fl |= mf[n0] != 0 ? 4u : 0u;  // uniform
                 if (mb) fl |= mb[n1] != 0 ? 8u : 0u;  // uniform
                 good += valid && fl == 0u;
@@ -242,15 +276,43 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_kernel(
         atomicAdd(trusted + (size_t)blockIdx.y * nt + t, block_trusted[t]);
 }
 
+// KI / KIC
+template <typename Frame>
+__global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_kernel(
+    const typename Frame::Elem *__restrict__ I0, const typename Frame::Elem *__restrict__ I1,
+    const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
+    const float *__restrict__ vb, const uint8_t *__restrict__ mask_f,
+    const uint8_t *__restrict__ mask_b, int rows, int cols, InterpTimes times, int nt,
+    void *__restrict__ out, int out_u8, uint8_t *__restrict__ flags,
+    uint32_t *__restrict__ trusted) {
+    frame_interp_body<Frame, false>(I0, I1, uf, vf, ub, vb, mask_f, mask_b, nullptr, rows, cols,
+                                    times, nt, out, out_u8, flags, trusted);
+}
+
+// KIP: the same over KS's cells [batch][nt][rows][cols]
+template <typename Frame>
+__global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_proj_kernel(
+    const typename Frame::Elem *__restrict__ I0, const typename Frame::Elem *__restrict__ I1,
+    const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
+    const float *__restrict__ vb, const uint8_t *__restrict__ mask_f,
+    const uint8_t *__restrict__ mask_b, const uint64_t *__restrict__ cells, int rows, int cols,
+    InterpTimes times, int nt, void *__restrict__ out, int out_u8, uint8_t *__restrict__ flags,
+    uint32_t *__restrict__ trusted) {
+    frame_interp_body<Frame, true>(I0, I1, uf, vf, ub, vb, mask_f, mask_b, cells, rows, cols,
+                                   times, nt, out, out_u8, flags, trusted);
+}
+
 // `times` is read here, on the host.  The grid is capped at what a CU holds
 // (Frame::kBlocksPerCu blocks of four waves): more blocks would wait for a
-// slot and only add atomics on the counts, which share a cache line.
+// slot and only add atomics on the counts, which share a cache line.  With
+// `cells` the launch is KIP's.
 template <typename Frame>
 hipError_t launch_frame_interp_as(const void *I0, const void *I1, int rows, int cols, int batch,
                                   const float *uf, const float *vf, const float *ub,
                                   const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
                                   const float *times, int nt, void *out, bool out_u8,
-                                  uint8_t *flags, uint32_t *trusted, hipStream_t s) {
+                                  uint8_t *flags, uint32_t *trusted, hipStream_t s,
+                                  const uint64_t *cells = nullptr) {
     using Elem = typename Frame::Elem;
     if (nt < 1 || nt > kInterpMaxTimes) return hipErrorInvalidValue;
     InterpTimes tm{};
@@ -259,9 +321,14 @@ hipError_t launch_frame_interp_as(const void *I0, const void *I1, int rows, int 
     const int ntiles = (int)((plane + kInterpTile - 1) / kInterpTile);
     const int cap = std::max(1, (Frame::kBlocksPerCu * device_cus() + batch - 1) / batch);
     dim3 blk(kInterpThreads, 1, 1), grd(std::min(ntiles, cap), batch, 1);
-    hipLaunchKernelGGL(hs_frame_interp_kernel<Frame>, grd, blk, 0, s, (const Elem *)I0,
-                       (const Elem *)I1, uf, vf, ub, vb, mask_f, mask_b, rows, cols, tm, nt, out,
-                       out_u8 ? 1 : 0, flags, trusted);
+    if (cells)
+        hipLaunchKernelGGL(hs_frame_interp_proj_kernel<Frame>, grd, blk, 0, s, (const Elem *)I0,
+                           (const Elem *)I1, uf, vf, ub, vb, mask_f, mask_b, cells, rows, cols, tm,
+                           nt, out, out_u8 ? 1 : 0, flags, trusted);
+    else
+        hipLaunchKernelGGL(hs_frame_interp_kernel<Frame>, grd, blk, 0, s, (const Elem *)I0,
+                           (const Elem *)I1, uf, vf, ub, vb, mask_f, mask_b, rows, cols, tm, nt,
+                           out, out_u8 ? 1 : 0, flags, trusted);
     return hipGetLastError();
 }
 

@@ -167,6 +167,7 @@ def _prototypes():
     bidir_out = flows + [vp] * 6                   # + err, mask, counts each way
     host_bidir_out = flows + [i, sz, vp, vp, sz, vp]   # + dtype, step, masks, step, counts
     times_out = [fp, i, vp, i, vp, vp]             # times, n, out, out dtype, flags, trusted
+    times_pj_out = [fp, i, i, vp, i, vp, vp]       # times, n, projection, out, ...
     host_times_out = [fp, i, vpp, i, sz, vpp, sz, vp]  # planes and their steps
     tail = [vp, sz, vp]                            # workspace, bytes, stream
     sized = (sz, shape + [i])                      # a workspace size of a shape and levels
@@ -280,6 +281,20 @@ def _prototypes():
                                              + pf + sm + init + tail),
         "hsflow_ctx_set_finest_level": (i, [vp, i]),
         "hsflow_ctx_finest_level": (i, [vp]),
+        # flow projection (projection.py is its public face): KS, KIP on grey and
+        # BGR frames, the fused calls with `projection` after nt
+        "hsflow_flow_project_device": (i, dev_pair + flows + [fp, i, vp, vp]),
+        "hsflow_frame_interp_proj_device": (i, dev_pair + flows + [vp, vp, vp] + times_out + [vp]),
+        "hsflow_frame_interp_bgr_proj_device": (i, dev_bgr_pair + flows + [vp, vp, vp] + times_out
+                                                + [vp]),
+        "hsflow_flow_interp_pj_workspace_bytes": (sz, shape + [i, i]),
+        "hsflow_flow_interp_bgr_pj_workspace_bytes": (sz, shape + [i, i]),
+        "hsflow_flow_interp_pj_device": (i, dev_pair + solve_lv + thresholds + times_pj_out + pf
+                                         + sm + init + tail),
+        "hsflow_flow_interp_bgr_pj_device": (i, dev_bgr_pair + solve_lv + thresholds + times_pj_out
+                                             + pf + sm + init + tail),
+        "hsflow_ctx_set_projection": (i, [vp, i]),
+        "hsflow_ctx_projection": (i, [vp]),
         "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
         "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
         "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),
@@ -523,13 +538,37 @@ class Context:
         finally:
             self._set_finest_level(was)
 
-    def _call_with(self, prefilter, smoothness, name, *args, finest=None):
-        """_call with `prefilter`, `smoothness` and `finest` as the context's
-        settings."""
+    @contextlib.contextmanager
+    def _projection_as(self, projection):
+        """`projection` as the context's for one call, the setting before it
+        restored afterwards; None leaves the context's own."""
+        if projection is None:
+            yield
+            return
+        was = self._projection()
+        self._set_projection(projection)
+        try:
+            yield
+        finally:
+            self._set_projection(was)
+
+    def _call_with(self, prefilter, smoothness, name, *args, finest=None, projection=None):
+        """_call with `prefilter`, `smoothness`, `finest` and `projection` as the
+        context's settings."""
         with self._setting_as(Prefilter, prefilter), self._setting_as(Smoothness, smoothness), \
-                self._finest_as(finest):
+                self._finest_as(finest), self._projection_as(projection):
             rc = getattr(lib(), name)(self._p, *args)
         _check(rc, self._p)
+
+    def _set_projection(self, projection):
+        """hsflow_ctx_set_projection (projection.set_projection is its public face)."""
+        self._call("hsflow_ctx_set_projection", int(projection))
+
+    def _projection(self) -> int:
+        rc = lib().hsflow_ctx_projection(self._p)
+        if rc < 0:
+            _check(rc, self._p)
+        return int(rc)
 
     def _set_finest_level(self, finest):
         """hsflow_ctx_set_finest_level (coarse.set_finest_level is its public face)."""
@@ -647,7 +686,8 @@ class Context:
     def interpolate(self, I0, I1, times, levels: int, warps: int, window: int, iters: int,
                     alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                     abs: float = CONSISTENCY_ABS, out_dtype=np.float32,
-                    with_flags: bool = False, prefilter=None, smoothness=None, finest=None):
+                    with_flags: bool = False, prefilter=None, smoothness=None, finest=None,
+                    projection=None):
         """The frames at `times` (each in [0, 1]; at most MAX_TIMES) between I0
         and I1: the bidirectional warped solve, then the motion-compensated
         blend (hsflow_flow_interp in include/hsflow.h).  Returns an array
@@ -658,20 +698,22 @@ class Context:
         flow_warped: the flows come from the prefiltered frames, the frames
         themselves are sampled.  smoothness as in flow_warped.  finest as in
         flow_warped: the flows are solved down to that level only, the frames
-        are sampled at full resolution."""
+        are sampled at full resolution.  projection: 1 carries the flows to each
+        time before the blend (projection.set_projection; None: the context's
+        own, 0 by default); flags then has FLAG bit 16 where nothing landed."""
         a, b, rows, cols = _host_pair(I0, I1)
         out, flags, trusted, outs = _host_interp_out(times, (rows, cols), out_dtype,
                                                      (np.uint8, np.float32, np.float64), with_flags)
         self._call_with(prefilter, smoothness, "hsflow_flow_interp", *_pair_args(a, b),
                         *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                        float(abs), *outs, finest=finest)
+                        float(abs), *outs, finest=finest, projection=projection)
         return (out, flags, trusted) if with_flags else out
 
     def interpolate_bgr(self, bgr0, bgr1, times, levels: int, warps: int, window: int,
                         iters: int, alpha: float, median: int = 0,
                         rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                         out_dtype=np.uint8, with_flags: bool = False, prefilter=None,
-                        smoothness=None, finest=None):
+                        smoothness=None, finest=None, projection=None):
         """The colour frames at `times` between two decoded 8-bit BGR frames
         (H x W x 3, strided rows accepted): uploaded as BGR, converted to grey
         and solved both ways on the GPU, then the motion-compensated blend of
@@ -680,13 +722,14 @@ class Context:
         with_flags: (frames, flags, trusted) -- flags uint8 [len(times), rows,
         cols] and trusted uint32 [len(times)] as in interpolate.  prefilter as
         in flow_warped, run on the grey planes; smoothness and finest as in
-        flow_warped."""
+        flow_warped; projection as in interpolate (the cells come from the grey
+        planes)."""
         a, b, rows, cols = _host_bgr_pair(bgr0, bgr1, " (grey frames: Context.interpolate)")
         out, flags, trusted, outs = _host_interp_out(times, (rows, cols, 3), out_dtype,
                                                      (np.uint8, np.float32), with_flags)
         self._call_with(prefilter, smoothness, "hsflow_flow_interp_bgr", *_pair_args(a, b),
                         *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                        float(abs), *outs, finest=finest)
+                        float(abs), *outs, finest=finest, projection=projection)
         return (out, flags, trusted) if with_flags else out
 
     def flow_bgr(self, bgr0, bgr1, window: int, iters: int, alpha: float,
@@ -789,7 +832,8 @@ class hornSchunck:  # noqa: N801  (reference class name, hornSchunck.cpp:8)
 
 
 def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int = 1,
-            warps: int = 0, median: int = 0, prefilter=None, smoothness=None, finest: int = 0):
+            warps: int = 0, median: int = 0, prefilter=None, smoothness=None, finest: int = 0,
+            projection: int = 0):
     """compute(I0, I1, alpha, nIter) -> (u, v): the north-star convenience
     wrapper over hornSchunck(windowSize, nIter, alpha).getFlow; levels > 1
     runs the config-5 coarse-to-fine warm start (nIter per level).  warps >= 1
@@ -800,7 +844,12 @@ def compute(I0, I1, alpha: float, nIter: int, windowSize: int = 5, levels: int =
     prefilter (a Prefilter: the frames are locally normalised first) and so
     does smoothness (a Smoothness: the flow-driven, edge-preserving term) and so
     does finest > 0 (the last level solved; its flow goes up to the full frame
-    bilinearly)."""
+    bilinearly).  projection is a step of frame interpolation (Context.interpolate,
+    flow_interp_device), not of the solve: compute returns the flows, which it
+    does not change, so anything but 0 is an error here rather than ignored."""
+    if projection:
+        raise HsflowError(HSFLOW_ERR_ARG, f"projection {projection} belongs to frame "
+                          "interpolation (Context.interpolate), not to a flow")
     if median and not warps:
         raise HsflowError(HSFLOW_ERR_ARG, f"median {median} needs the warped solve (warps >= 1)")
     if prefilter is not None and not warps:
@@ -1046,6 +1095,26 @@ def _init_entry(stem, init, dims, finest=0):
     return stem + "_lv_device", (int(finest),), start or (None,)
 
 
+def _pj_entry(stem, init, dims, finest, projection):
+    """_init_entry for the two interpolating solves, plus the projection
+    argument: nothing for projection 0, which is _init_entry as it stands; else
+    the *_pj_device call, which takes finest, `projection` after nt and an
+    init or NULL."""
+    name, lv, start = _init_entry(stem, init, dims, finest)
+    if not projection:
+        return name, lv, start, ()
+    return stem + "_pj_device", (int(finest),), start or (None,), (int(projection),)
+
+
+def _pj_size(size_fn, stem, projection, levels, nt):
+    """(workspace size function, its arguments past the shape) of an
+    interpolating solve: `size_fn` of the levels, or with projection the
+    *_pj_workspace_bytes of `stem`, which counts the cell planes of nt times."""
+    if not projection:
+        return size_fn, (levels,)
+    return getattr(lib(), stem + "_pj_workspace_bytes"), (levels, nt)
+
+
 def _init_entry_0(stem, init, dims):
     if init is None:
         return stem + "_sm_device", ()
@@ -1269,7 +1338,7 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
                        alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                        abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                        trusted=None, workspace=None, stream=None, prefilter=None,
-                       smoothness=None, finest: int = 0):
+                       smoothness=None, finest: int = 0, projection: int = 0):
     """flow_bidir_device(median=...) into planes of the workspace, then
     frame_interp_device with both masks: one call, the same bits
     (hsflow_flow_interp_device in include/hsflow.h).  `workspace`:
@@ -1278,29 +1347,33 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
     frames themselves are sampled (hsflow_flow_interp_pf_device;
     prefilter_planes_bytes more workspace).  finest as in flow_bidir_device
     (hsflow_flow_interp_lv_device): the flows of a coarse solve, the frames
-    sampled at full resolution.  Returns (out, flags, trusted) as
-    frame_interp_device.  Stream-ordered."""
+    sampled at full resolution.  projection = 1: projection.project_device on
+    the frames the solve ran on stands between the two and the interpolation
+    is projection.frame_interp_device (hsflow_flow_interp_pj_device; the
+    workspace grows by the cells, projection.flow_interp_workspace_bytes).
+    Returns (out, flags, trusted) as frame_interp_device.  Stream-ordered."""
     return _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel,
                                abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
-                               smoothness, finest=finest)
+                               smoothness, finest=finest, projection=projection)
 
 
 def _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel, abs, out,
                         out_dtype, flags, trusted, workspace, stream, prefilter, smoothness,
-                        init=None, finest=0):
+                        init=None, finest=0, projection=0):
     """flow_interp_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     tm = _times_array(times)
     out, flags, trusted = _interp_outputs(I0, (), len(tm), out, out_dtype, flags, trusted)
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
-    workspace = _workspace(workspace, I0.device, flow_interp_workspace_bytes, *dims, levels,
-                           prefilter=prefilter)
-    name, lv, start = _init_entry("hsflow_flow_interp", init, dims, finest)
+    size_fn, size_args = _pj_size(flow_interp_workspace_bytes, "hsflow_flow_interp", projection,
+                                  levels, len(tm))
+    workspace = _workspace(workspace, I0.device, size_fn, *dims, *size_args, prefilter=prefilter)
+    name, lv, start, pj = _pj_entry("hsflow_flow_interp", init, dims, finest, projection)
     _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
                  *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel),
-                 float(abs), tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags), _ptr(trusted), pf, sm,
-                 *start, *_ws_args(workspace))
+                 float(abs), tm, len(tm), *pj, out.data_ptr(), _out_code(out), _ptr(flags),
+                 _ptr(trusted), pf, sm, *start, *_ws_args(workspace))
     return out, flags, trusted
 
 
@@ -1368,7 +1441,7 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
                            alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                            abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                            trusted=None, workspace=None, stream=None, prefilter=None,
-                           smoothness=None, finest: int = 0):
+                           smoothness=None, finest: int = 0, projection: int = 0):
     """bgr_to_gray_device of both frames, flow_bidir_device(median=...) on the
     grey planes, then frame_interp_bgr_device with both masks: one call, the
     same bits (hsflow_flow_interp_bgr_device in include/hsflow.h).
@@ -1376,26 +1449,30 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
     bytes.  prefilter: a Prefilter run on the grey planes in front of the
     solve (hsflow_flow_interp_bgr_pf_device; prefilter_planes_bytes more
     workspace).  finest as in flow_interp_device
-    (hsflow_flow_interp_bgr_lv_device).  Returns (out, flags, trusted) as
-    frame_interp_bgr_device.  Stream-ordered."""
+    (hsflow_flow_interp_bgr_lv_device); projection likewise, the cells made
+    from the grey planes (hsflow_flow_interp_bgr_pj_device;
+    projection.flow_interp_bgr_workspace_bytes).  Returns (out, flags, trusted)
+    as frame_interp_bgr_device.  Stream-ordered."""
     return _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median,
                                    rel, abs, out, out_dtype, flags, trusted, workspace, stream,
-                                   prefilter, smoothness, finest=finest)
+                                   prefilter, smoothness, finest=finest, projection=projection)
 
 
 def _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median, rel,
                             abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
-                            smoothness, init=None, finest=0):
+                            smoothness, init=None, finest=0, projection=0):
     """flow_interp_bgr_device, from `init` (_init_entry) where given."""
     dims = _bgr_pair(bgr0, bgr1)
     tm = _times_array(times)
     out, flags, trusted = _interp_outputs(bgr0, (3,), len(tm), out, out_dtype, flags, trusted)
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
-    workspace = _workspace(workspace, bgr0.device, flow_interp_bgr_workspace_bytes, *dims, levels,
-                           prefilter=prefilter)
-    name, lv, start = _init_entry("hsflow_flow_interp_bgr", init, dims, finest)
+    size_fn, size_args = _pj_size(flow_interp_bgr_workspace_bytes, "hsflow_flow_interp_bgr",
+                                  projection, levels, len(tm))
+    workspace = _workspace(workspace, bgr0.device, size_fn, *dims, *size_args, prefilter=prefilter)
+    name, lv, start, pj = _pj_entry("hsflow_flow_interp_bgr", init, dims, finest, projection)
     _device_call(name, bgr0.device, stream, bgr0.data_ptr(), bgr1.data_ptr(), *dims,
-                 *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel), float(abs), tm, len(tm), out.data_ptr(), _out_code(out), _ptr(flags),
+                 *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel),
+                 float(abs), tm, len(tm), *pj, out.data_ptr(), _out_code(out), _ptr(flags),
                  _ptr(trusted), pf, sm, *start, *_ws_args(workspace))
     return out, flags, trusted
 

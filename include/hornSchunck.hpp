@@ -87,6 +87,15 @@ class hornSchunck {
         return finest;
     }
 
+    // Flow projection for the interpolating calls made through this object
+    // (hsflow.h, hsflow_ctx_set_projection); 0, the default: none.
+    void setProjection(int projection) { guarded([&] { impl_.setProjection(projection); }); }
+    int projection() {
+        int projection = 0;
+        guarded([&] { projection = impl_.projection(); });
+        return projection;
+    }
+
   private:
     hsflow::HornSchunck impl_;
 

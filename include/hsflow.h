@@ -1071,6 +1071,118 @@ int hsflow_flow_interp_bgr_lv_device(const uint8_t *bgr0, const uint8_t *bgr1, i
 int hsflow_ctx_set_finest_level(hsflow_ctx *ctx, int finest);
 int hsflow_ctx_finest_level(const hsflow_ctx *ctx);
 
+/* ---- flow projection: the flows carried to time t before a frame is made -----
+ * hsflow_frame_interp_device forms the time-t flow of an output pixel from the
+ * four flows at that pixel.  Near a motion boundary the output pixel belongs
+ * to whichever surface lands on it at time t, not to the one that sits there
+ * in frame 0 or frame 1.  Projection (Baker et al., IJCV 2011, section 3.3.2)
+ * carries every source pixel's flow to where that pixel is at time t, keeps
+ * per target the candidate whose brightness matches best, and samples both
+ * frames with the winner's flow.  Per pair and per time t, f32, s = 1 - t:
+ *   candidates   every pixel p = (y, x) of both frames:
+ *                  direction 0: frame A = G0, other = G1, (u, v) = (uf, vf), tau = t
+ *                  direction 1: frame A = G1, other = G0, (u, v) = (ub, vb), tau = s
+ *   displacement dx = 8 u, dy = 8 v, clamped as floats to [-cols, cols] and
+ *                [-rows, rows] (NaN -> lower bound), hsflow_warp_image_device's
+ *   cost         |w - A(p)|, w = the other frame sampled at (y + dy, x + dx) as
+ *                hsflow_warp_image_device samples (f64 frames: in double,
+ *                rounded to f32 once);  code = cost * 8 as a float;
+ *                !(code < 2^30) -> 2^30 (NaN lands there); truncated to uint32
+ *   target       qx = floorf(x + tau dx + 0.5f), qy likewise (left to right, no
+ *                multiply fused into an add); a candidate whose qx is outside
+ *                [0, cols) or qy outside [0, rows), tested as floats, has none
+ *   key          code << 32 | dir << 31 | (y cols + x)
+ *   cells[pair][time][qy][qx] = the minimum key over the candidates that land
+ *                there: an integer minimum, so the plane is the same bytes
+ *                whatever the order of arrival; ties go to direction 0, then
+ *                to the lower source index.  A cell nothing lands on stays
+ *                all ones: a hole.
+ * Resolve and blend at output pixel q (hsflow_frame_interp_proj_device): a hole
+ * is hsflow_frame_interp_device's pixel unchanged, with HSFLOW_INTERP_HOLE in
+ * its flags; else with (dir, p) decoded from the cell's low word,
+ *   (ut, vt) = (uf, vf)[p] for direction 0, (-ub, -vb)[p] for direction 1
+ *   u0 = -t ut;  v0 = -t vt;  u1 = s ut;  v1 = s vt
+ * and from there hsflow_frame_interp_device's text: the two samples, in0, in1,
+ * wt, the blend, the u8 rounding, n0, n1, the four flag bits from mask_f and
+ * mask_b, trusted as the count of flags == 0.  t = 0 and t = 1 return I0 and
+ * I1 exactly (finite flows).  The masks stay a confidence output.
+ * What it buys ("Flow projection"): about a third of the error in
+ * the band around a moving object and of the whole frame's; pure shifts are
+ * unchanged; the narrow ring of real occlusion stays. */
+#define HSFLOW_HAS_PROJECTION 1
+#define HSFLOW_INTERP_HOLE 16 /* no candidate landed on the pixel at this time */
+
+/* KS: the cells of `nt` times (host array, read at call time, each in [0, 1],
+ * nt in 1 .. HSFLOW_MAX_TIMES) from the grey frames G0, G1 the flows were
+ * solved on (dense [batch][rows][cols] of dtype_in: U8, F16, F32 or F64) and
+ * the four flows (dense f32).  cells: [batch][nt][rows][cols] of uint64_t,
+ * 8-byte aligned (else HSFLOW_ERR_ARG), disjoint from the inputs; the call
+ * sets it to all ones stream-ordered, then one launch takes the minima.  NaN,
+ * inf and huge flows are safe: no index leaves a pair's plane, and every
+ * non-empty cell's low 31 bits are below rows * cols.  rows * cols beyond the
+ * library's plane limit (any product above 2^31 included) is HSFLOW_ERR_ARG.
+ * No workspace, never allocates or synchronises, capturable. */
+int hsflow_flow_project_device(const void *G0, const void *G1, int dtype_in, int rows, int cols,
+                               int batch, const float *uf, const float *vf, const float *ub,
+                               const float *vb, const float *times, int nt, uint64_t *cells,
+                               void *stream);
+
+/* hsflow_frame_interp_device and hsflow_frame_interp_bgr_device reading the
+ * time-t flow through `cells` (of the same times, 8-byte aligned, not
+ * overlapping an output).  For colour frames the cells come from the grey
+ * conversions (hsflow_bgr_to_gray_device) of both frames; each channel of the
+ * result has the bits the grey call gives that channel's plane. */
+int hsflow_frame_interp_proj_device(const void *I0, const void *I1, int dtype_in, int rows,
+                                    int cols, int batch, const float *uf, const float *vf,
+                                    const float *ub, const float *vb, const uint8_t *mask_f,
+                                    const uint8_t *mask_b, const uint64_t *cells,
+                                    const float *times, int nt, void *out, int dtype_out,
+                                    uint8_t *flags, uint32_t *trusted, void *stream);
+int hsflow_frame_interp_bgr_proj_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows,
+                                        int cols, int batch, const float *uf, const float *vf,
+                                        const float *ub, const float *vb, const uint8_t *mask_f,
+                                        const uint8_t *mask_b, const uint64_t *cells,
+                                        const float *times, int nt, void *out, int dtype_out,
+                                        uint8_t *flags, uint32_t *trusted, void *stream);
+
+/* The fused calls: the *_lv_device forms with `int projection` after `nt`.
+ * 0 makes exactly the launches of the *_lv_device call (and needs its
+ * workspace only); 1 is the public pieces one after the other -- the
+ * bidirectional solve, hsflow_flow_project_device on the grey frames the solve
+ * ran on (after the conversion and the prefilter, where there is one), the
+ * projected interpolation of the frames themselves -- and bit for bit what
+ * they give; anything else is HSFLOW_ERR_ARG.  The workspace of projection = 1
+ * is the *_lv_device call's plus the 256-byte-aligned cell plane of nt times
+ * (and a prefilter's planes behind it, as ever).  All arguments are checked
+ * before any device work. */
+size_t hsflow_flow_interp_pj_workspace_bytes(int rows, int cols, int batch, int levels, int nt);
+size_t hsflow_flow_interp_bgr_pj_workspace_bytes(int rows, int cols, int batch, int levels,
+                                                 int nt);
+int hsflow_flow_interp_pj_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, int projection, void *out,
+                                 int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 const hsflow_flow_init *init, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_bgr_pj_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int finest, int warps, int median,
+                                     int window, int iters, float alpha, float rel,
+                                     float abs_thr, const float *times, int nt, int projection,
+                                     void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                     const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                     const hsflow_flow_init *init, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
+/* The context's projection: hsflow_flow_interp and hsflow_flow_interp_bgr
+ * honour it and then equal their *_pj_device form bit for bit.  0, the
+ * default: as before.  A value other than 0 or 1 is HSFLOW_ERR_ARG and leaves
+ * the old one in place.  hsflow_ctx_projection reads it back (HSFLOW_ERR_ARG
+ * for a null context). */
+int hsflow_ctx_set_projection(hsflow_ctx *ctx, int projection);
+int hsflow_ctx_projection(const hsflow_ctx *ctx);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

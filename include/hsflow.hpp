@@ -119,6 +119,16 @@ class Context {
         if (rc < 0) check(rc);
         return rc;
     }
+    // Flow projection for the interpolating calls (hsflow.h,
+    // hsflow_ctx_set_projection): 1 carries both flows to each time before
+    // the blend, so a pixel near a motion boundary takes the flow of the
+    // surface that lands on it; 0, the default: the flows at the pixel itself.
+    void setProjection(int projection) { check(hsflow_ctx_set_projection(ctx_, projection)); }
+    int projection() const {
+        const int rc = hsflow_ctx_projection(ctx_);
+        if (rc < 0) check(rc);
+        return rc;
+    }
 
   private:
     hsflow_ctx *ctx_ = nullptr;
@@ -201,6 +211,10 @@ class HornSchunck {
     // the last pyramid level the same methods solve (Context::setFinestLevel)
     void setFinestLevel(int finest) { ctx().setFinestLevel(finest); }
     int finestLevel() { return ctx().finestLevel(); }
+    // flow projection for getFrameInterp and getFrameInterpBgr
+    // (Context::setProjection)
+    void setProjection(int projection) { ctx().setProjection(projection); }
+    int projection() { return ctx().projection(); }
     void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                        int warps, std::vector<double> &u, std::vector<double> &v,
                        int median = 0, const hsflow_prefilter *prefilter = nullptr) {
