@@ -1088,9 +1088,10 @@ int hsflow_ctx_finest_level(const hsflow_ctx *ctx);
  *                hsflow_warp_image_device samples (f64 frames: in double,
  *                rounded to f32 once);  code = cost * 8 as a float;
  *                !(code < 2^30) -> 2^30 (NaN lands there); truncated to uint32
- *   target       qx = floorf(x + tau dx + 0.5f), qy likewise (left to right, no
- *                multiply fused into an add); a candidate whose qx is outside
- *                [0, cols) or qy outside [0, rows), tested as floats, has none
+ *   target       qx = x + (int)floorf(tau dx + 0.5f), qy likewise (no multiply
+ *                fused into an add; the displacement is rounded on its own, so
+ *                the target is exact at any x, y); a candidate whose qx is
+ *                outside [0, cols) or qy outside [0, rows) has none
  *   key          code << 32 | dir << 31 | (y cols + x)
  *   cells[pair][time][qy][qx] = the minimum key over the candidates that land
  *                there: an integer minimum, so the plane is the same bytes

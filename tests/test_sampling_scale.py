@@ -31,6 +31,7 @@ cannot hold.  Here
 The bounds are the other modules': err within 16 eps32 8 M and the mask equal
 outside that band (test_consistency), |out - ref| <= 1e-4 max|ref| outside the
 rim band and the flags equal outside the rim and half bands (test_interp).
+test_projection_scale.py does the same for KS, KIP and the kernels added since.
 """
 import functools
 
