@@ -64,8 +64,15 @@ int hip_fail(hsflow_ctx *ctx, hipError_t e, const char *what);
 constexpr size_t kAlign = 256;
 inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
-// Largest frame: plane bytes must fit the 31-bit buffer offsets of K2.
-constexpr long long kMaxPlanePixels = (1ll << 29) - 1;
+// Largest frame: 2^29 - 4 pixels.  The Jacobi kernels (K2, K2w, K4, KJ) give a
+// lane outside the image the byte offset kOOB = 0x7FFFFFF0 into raw buffers of
+// rows * cols * 4 bytes and rely on the range check there to read 0 and drop
+// the store (the zero border).  A plane of more bytes than kOOB holds that
+// offset: every such load would return its element 2^29 - 4 and every such
+// store overwrite it.  So the cap is the sentinel over the element size; the
+// two change together (tests/test_plane_cap.py).
+constexpr long long kJacobiOobOffset = 0x7FFFFFF0;
+constexpr long long kMaxPlanePixels = kJacobiOobOffset / 4;
 
 // Largest batch: pairs index gridDim.y / gridDim.z of the kernels (65535);
 // tallest plane: the 64 x 4 per-pixel kernels put rows / 4 in gridDim.y.

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kThreads) void hs_flow_consistency_kernel(
     float *__restrict__ err, uint8_t *__restrict__ mask, uint32_t *__restrict__ counts,
     int pack_mask) {
     __shared__ uint32_t wave_counts[kThreads / 64][3];
-    const int plane = rows * cols;  // <= 2^29 - 1
+    const int plane = rows * cols;  // <= 2^29 - 4
     const size_t base = (size_t)blockIdx.y * plane;
     const int shift = (int)(base & 3);  // base + tile start is a multiple of 4
     const int ntiles = (plane + shift + kTile - 1) / kTile;

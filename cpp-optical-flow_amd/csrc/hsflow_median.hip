@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kCols *kWaves) void hs_flow_median_kernel(
     const int x = blockIdx.x * kCols + threadIdx.x;
     const int y0 = (blockIdx.y * kWaves + threadIdx.y) * kRun;  // uniform per wave
     if (x >= cols || y0 >= rows) return;
-    const size_t base = (size_t)blockIdx.z * rows * cols;  // rows * cols <= 2^29 - 1
+    const size_t base = (size_t)blockIdx.z * rows * cols;  // rows * cols <= 2^29 - 4
     int xs[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) xs[i] = clampi(x + i - H, cols);

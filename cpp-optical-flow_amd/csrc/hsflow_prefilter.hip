@@ -125,7 +125,7 @@ __global__ __launch_bounds__(TW + 64) void hs_prefilter_kernel(const T *__restri
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * TW;
     const int ys = blockIdx.y * seg_rows, ye = min(rows, ys + seg_rows);
-    const size_t base = (size_t)blockIdx.z * rows * cols;  // rows * cols <= 2^29 - 1
+    const size_t base = (size_t)blockIdx.z * rows * cols;  // rows * cols <= 2^29 - 4
     const T *in = I + base;
     float *o = out + base;
     // This thread's column of a row buffer (cI), of a ringA / ringB row (cH) and

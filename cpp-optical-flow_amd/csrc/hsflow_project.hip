@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void hs_flow_project_kernel(
     const T *__restrict__ G0, const T *__restrict__ G1, const float *__restrict__ uf,
     const float *__restrict__ vf, const float *__restrict__ ub, const float *__restrict__ vb,
     int rows, int cols, InterpTimes times, int nt, unsigned long long *__restrict__ cells) {
-    const int plane = rows * cols;  // <= 2^29 - 1
+    const int plane = rows * cols;  // <= 2^29 - 4
     const size_t base = (size_t)blockIdx.y * plane;
     const int ntiles = (plane + kTile - 1) / kTile;
     const float inv_cols = 1.0f / (float)cols;

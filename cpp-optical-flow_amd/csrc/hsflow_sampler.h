@@ -169,7 +169,7 @@ __device__ __forceinline__ void frame_interp_body(
     constexpr int kThreads = kInterpThreads, kPix = kInterpPix, kTile = kInterpTile;
     constexpr int kCh = Frame::kChannels;
     __shared__ uint32_t block_trusted[kInterpMaxTimes];
-    const int plane = rows * cols;  // <= 2^29 - 1
+    const int plane = rows * cols;  // <= 2^29 - 4
     const size_t base = (size_t)blockIdx.y * plane;
     const int ntiles = (plane + kTile - 1) / kTile;
     const float inv_cols = 1.0f / (float)cols;

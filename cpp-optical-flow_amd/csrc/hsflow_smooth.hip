@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void hs_diffusivity_kernel(const float *__rest
     const int x = blockIdx.x * 64 + threadIdx.x;
     const int y = blockIdx.y * 4 + threadIdx.y;
     if (x >= cols || y >= rows) return;
-    const size_t base = (size_t)blockIdx.z * rows * cols;  // rows * cols <= 2^29 - 1
+    const size_t base = (size_t)blockIdx.z * rows * cols;  // rows * cols <= 2^29 - 4
     const float *ur = u + base + (size_t)y * cols, *vr = v + base + (size_t)y * cols;
     const int xl = clampi(x - 1, cols), xr = clampi(x + 1, cols);
     const size_t up = base + (size_t)clampi(y - 1, rows) * cols + x;

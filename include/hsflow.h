@@ -129,6 +129,12 @@ int hsflow_gradients(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_
  * call, whatever device is current.  `workspace` is device memory of at least
  * hsflow_workspace_bytes(rows, cols, batch) bytes, 256-byte aligned.
  *
+ * Sizes.  rows in 1..262140, cols >= 1 and rows * cols <= 2^29 - 4 pixels
+ * (536870908: the byte offset 0x7FFFFFF0 that the Jacobi kernels give a lane
+ * outside the image must lie past the end of a plane).  Anything else is
+ * HSFLOW_ERR_ARG, "bad size", before any device work, and
+ * hsflow_workspace_bytes returns 0 for it.
+ *
  * Memory contract of the device calls (tests/test_footprint.py holds every
  * entry point below to it):
  * - Alignment.  A plane needs the alignment of its element and no more: 4
@@ -1121,7 +1127,8 @@ int hsflow_ctx_finest_level(const hsflow_ctx *ctx);
  * sets it to all ones stream-ordered, then one launch takes the minima.  NaN,
  * inf and huge flows are safe: no index leaves a pair's plane, and every
  * non-empty cell's low 31 bits are below rows * cols.  rows * cols beyond the
- * library's plane limit (any product above 2^31 included) is HSFLOW_ERR_ARG.
+ * library's plane limit of 2^29 - 4 pixels (any product above 2^31 included)
+ * is HSFLOW_ERR_ARG.
  * No workspace, never allocates or synchronises, capturable. */
 int hsflow_flow_project_device(const void *G0, const void *G1, int dtype_in, int rows, int cols,
                                int batch, const float *uf, const float *vf, const float *ub,

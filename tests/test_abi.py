@@ -243,6 +243,13 @@ def test_batch_and_plane_limits_are_rejected_on_the_host():
     assert hsflow.workspace_bytes(10, 10, 65536) == 0          # gridDim limit
     assert hsflow.workspace_bytes(1 << 14, (1 << 15) - 1, 1) > 0   # < 2^29 px: accepted
     assert hsflow.workspace_bytes(1 << 14, 1 << 15, 1) == 0        # 2^29 px: offsets overflow
+    # the cap is 2^29 - 4 px, the Jacobi kernels' out-of-image byte offset
+    # 0x7FFFFFF0 over 4: a larger plane holds that offset (test_plane_cap.py)
+    for rows, cols in ((1022, 525314), (2044, 262657)):            # 2^29 - 4 px
+        assert rows * cols == 0x7FFFFFF0 // 4 and hsflow.workspace_bytes(rows, cols, 1) > 0
+    for rows, cols in ((256999, 2089), (2089, 256999), (18705, 28702), (1, 536870909)):
+        assert 0x7FFFFFF0 // 4 < rows * cols < 1 << 29             # 2^29 - 1, - 2, - 3 px
+        assert hsflow.workspace_bytes(rows, cols, 1) == 0
     assert hsflow.workspace_bytes(4 * 65535, 8, 1) > 0             # tallest plane
     assert hsflow.workspace_bytes(4 * 65535 + 1, 8, 1) == 0        # gridDim.y of K1
 
