@@ -38,6 +38,13 @@ struct hsflow_ctx {
     // hsflow_ctx_set_projection: 1: the interpolating host calls carry the
     // flows to each time first (KS, KIP); 0, the default: KI as it is
     int projection = 0;
+    // hsflow_ctx_set_fallback: what the interpolating host calls do with a pair
+    // whose flows fail the check (mode 0, the default: nothing).  last_cut: the
+    // verdict of the last such call, -1 where there is none; cut_byte: where
+    // that call's verdict lands ahead of the drain
+    hsflow_fallback fb{HSFLOW_FALLBACK_OFF, 0.0f};
+    int last_cut = -1;
+    uint8_t cut_byte = 0;
     // hsflow_ctx_set_temporal: sequence mode of the bidirectional host-buffer
     // calls.  d_pred (grow-only) holds KP's four planes uf, vf, ub, vb of the
     // last such call, each align_up(pred_rows * pred_cols * 4) bytes;

@@ -2,7 +2,7 @@
 // the warped coarse-to-fine solve, the median and the smoothness weights
 // between its warps, the bidirectional solve with its consistency check, the
 // prefilter in front of them, and the frame warp and frame interpolation
-// (grey and BGR) behind them.
+// (grey and BGR) behind them, with the fallback for a pair whose flows fail.
 //
 // Every solve of the family is described by one SolveSpec, filled once in the
 // extern "C" entry point and passed down by reference; check_solve checks it,
@@ -31,6 +31,9 @@ struct SolveSpec {
     // the interpolating calls: 0, KI on the flows at the output pixel; 1, KS
     // carries the flows to each time first and KIP reads them there
     int projection;
+    // the interpolating calls: null or mode 0, nothing; else KF replaces the
+    // frames of every pair whose flows fail the check
+    const hsflow_fallback *fb;
 };
 
 // the outputs of one direction's consistency check (KC); each may be null
@@ -55,7 +58,8 @@ struct FlowsIn {
     const uint64_t *cells;
 };
 
-// ... and what it writes: nt frames at `times` (host), flags and trusted
+// ... and what it writes: nt frames at `times` (host), flags and trusted; the
+// calls with a fallback also the verdict per pair
 struct InterpOut {
     const float *times;
     int nt;
@@ -63,6 +67,7 @@ struct InterpOut {
     int dtype_out;
     uint8_t *flags;
     uint32_t *trusted;
+    uint8_t *cut;
 };
 
 // the host form's: one host plane per time
@@ -731,6 +736,7 @@ void interp_out_ranges(const InterpOut &O, size_t n, int batch, int channels, By
     r[0] = {O.out, n * O.nt * channels * elem_size(O.dtype_out)};
     r[1] = {O.flags, n * O.nt};
     r[2] = {O.trusted, (size_t)batch * O.nt * 4};
+    r[3] = {O.cut, (size_t)batch};
 }
 
 // KI (channels 1: frames of fr.dtype) or KIC (channels 3: 8-bit interleaved
@@ -818,24 +824,86 @@ int frame_interp_impl(hsflow_ctx *ctx, int channels, const Frames &fr, int rows,
                              {W.vf, n * 4}, {W.ub, n * 4}, {W.vb, n * 4},
                              {W.mask_f, n}, {W.mask_b, n},
                              {proj ? W.cells : nullptr, n * O.nt * 8}};
-    ByteRange outs[3];
+    ByteRange outs[4];
     interp_out_ranges(O, n, batch, channels, outs);
-    if (!outputs_disjoint(in, 9, outs, 3))
+    if (!outputs_disjoint(in, 9, outs, 4))
         return fail(ctx, HSFLOW_ERR_ARG,
                     "interpolation outputs overlap the inputs or each other");
     return frame_interp_run(ctx, channels, fr, rows, cols, batch, W, O, s);
 }
 
+// ---- fallback for a failed pair (KF) --------------------------------------------
+bool fb_on(const hsflow_fallback *fb) { return fb && fb->mode != HSFLOW_FALLBACK_OFF; }
+
+// a setting that is on: the mode and the share (negated comparison: NaN fails)
+int check_fallback(hsflow_ctx *ctx, const hsflow_fallback *fb) {
+    if (fb->mode != HSFLOW_FALLBACK_NEAREST && fb->mode != HSFLOW_FALLBACK_BLEND)
+        return fail(ctx, HSFLOW_ERR_ARG, "fallback mode %d is not 0, 1 or 2", fb->mode);
+    if (!(fb->min_share >= 0.0f && fb->min_share <= 1.0f))
+        return fail(ctx, HSFLOW_ERR_ARG, "fallback min_share %g outside [0, 1]",
+                    (double)fb->min_share);
+    return HSFLOW_OK;
+}
+
+// the smallest integer >= min_share * 2 * rows * cols: exact in double (24 bits
+// of the share, at most 30 of the pixels of both directions)
+uint64_t min_consistent(int rows, int cols, float min_share) {
+    return (uint64_t)std::ceil((double)min_share * 2.0 * (double)rows * (double)cols);
+}
+
+size_t fb_counts_bytes(int batch) { return 2 * align_up((size_t)batch * 3 * 4); }
+
+// KF on checked arguments: one launch
+int fallback_run(hsflow_ctx *ctx, int channels, const Frames &fr, int rows, int cols, int batch,
+                 const uint32_t *counts_f, const uint32_t *counts_b, const hsflow_fallback &fb,
+                 const InterpOut &O, hipStream_t s) {
+    const uint64_t m = min_consistent(rows, cols, fb.min_share);
+    const bool u8 = O.dtype_out == HSFLOW_U8;
+    hipError_t e =
+        channels == 3
+            ? hsflow::launch_frame_fallback_bgr((const uint8_t *)fr.I0, (const uint8_t *)fr.I1,
+                                                rows, cols, batch, counts_f, counts_b, m, fb.mode,
+                                                O.times, O.nt, O.out, u8, O.flags, O.trusted,
+                                                O.cut, s)
+            : hsflow::launch_frame_fallback(fr.I0, fr.I1, fr.dtype, rows, cols, batch, counts_f,
+                                            counts_b, m, fb.mode, O.times, O.nt, O.out, u8,
+                                            O.flags, O.trusted, O.cut, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "frame fallback launch");
+    return HSFLOW_OK;
+}
+
+// hsflow_frame_fallback_device, hsflow_frame_fallback_bgr_device (fr.dtype: U8)
+int fallback_impl(hsflow_ctx *ctx, int channels, const Frames &fr, int rows, int cols, int batch,
+                  const uint32_t *counts_f, const uint32_t *counts_b, const hsflow_fallback *fb,
+                  const InterpOut &O, hipStream_t s) {
+    int rc = check_sizes(ctx, rows, cols, batch);
+    if (rc || (rc = check_device_dtype(ctx, fr.dtype))) return rc;
+    if (!fr.I0 || !fr.I1 || !counts_f || !counts_b || !O.out) return null_pointer(ctx);
+    if (!fb_on(fb))
+        return fail(ctx, HSFLOW_ERR_ARG, "no fallback: a null setting or mode 0");
+    if ((rc = check_fallback(ctx, fb))) return rc;
+    if ((rc = check_interp_args(ctx, O.times, O.nt, O.dtype_out, false))) return rc;
+    const size_t n = (size_t)rows * cols * batch, cb = (size_t)batch * 3 * 4;
+    const size_t fbytes = n * (channels == 3 ? 3 : elem_size(fr.dtype));
+    const ByteRange in[4] = {{fr.I0, fbytes}, {fr.I1, fbytes}, {counts_f, cb}, {counts_b, cb}};
+    ByteRange outs[4];
+    interp_out_ranges(O, n, batch, channels, outs);
+    if (!outputs_disjoint(in, 4, outs, 4))
+        return fail(ctx, HSFLOW_ERR_ARG, "fallback outputs overlap the inputs or each other");
+    return fallback_run(ctx, channels, fr, rows, cols, batch, counts_f, counts_b, *fb, O, s);
+}
+
 // Workspace of the fused call: [the bidirectional solve's][uf][vf][ub][vb]
 // (f32 batch planes)[mask_f][mask_b] (u8 batch planes), for BGR frames
-// [grey I0][grey I1] (u8 batch planes) and, for a projected call of cell_nt
-// times, KS's [cells] (u64, batch x cell_nt planes), each 256-byte aligned.
+// [grey I0][grey I1] (u8 batch planes), for a projected call of cell_nt
+// times KS's [cells] (u64, batch x cell_nt planes) and, for a call with a
+// fallback, KC's [counts_f][counts_b] (u32, batch x 3), each 256-byte aligned.
 struct InterpLayout {
-    size_t solve_bytes, flow[4], mask[2], gray[2], cells, bytes;
+    size_t solve_bytes, flow[4], mask[2], gray[2], cells, counts[2], bytes;
 };
 
 InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channels,
-                           int cell_nt = 0) {
+                           int cell_nt = 0, bool fb_counts = false) {
     InterpLayout L{};
     const size_t n = (size_t)rows * cols * batch;
     L.solve_bytes = align_up(pyr_layout(rows, cols, batch, levels).bytes);
@@ -845,6 +913,8 @@ InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channe
     if (channels == 3)
         for (int k = 0; k < 2; ++k) L.gray[k] = off, off += align_up(n);
     if (cell_nt > 0) L.cells = off, off += align_up(n * cell_nt * 8);
+    if (fb_counts)
+        for (int k = 0; k < 2; ++k) L.counts[k] = off, off += fb_counts_bytes(batch) / 2;
     L.bytes = off;
     return L;
 }
@@ -858,7 +928,10 @@ InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channe
 // prefiltered f32 planes behind that layout.  S.projection = 1: KS
 // (hsflow_flow_project_device) on the frames the solve ran on, into the
 // workspace's cells, stands between the solve and the interpolation, which is
-// then KIP (hsflow_frame_interp*_proj_device).
+// then KIP (hsflow_frame_interp*_proj_device).  With a fallback on (S.fb) both
+// checks run whatever is asked for, their counts go into the workspace, and KF
+// (hsflow_frame_fallback*_device) follows the interpolation; off, the launches
+// are unchanged and a given O.cut is zeroed.
 int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Frames &in,
                      float rel, float abs_thr, const InterpOut &O, void *ws, size_t ws_bytes,
                      hipStream_t s) {
@@ -869,18 +942,20 @@ int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Fr
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
     if ((rc = check_interp_args(ctx, O.times, O.nt, O.dtype_out, false))) return rc;
     if ((rc = check_projection(ctx, S.projection))) return rc;
+    const bool fallback = fb_on(S.fb);
+    if (fallback && (rc = check_fallback(ctx, S.fb))) return rc;
     const InterpLayout L = interp_layout(S.rows, S.cols, S.batch, S.levels, channels,
-                                         S.projection ? O.nt : 0);
+                                         S.projection ? O.nt : 0, fallback);
     const size_t need = L.bytes + (pf_on(S.pf) ? pf_planes_bytes(S.rows, S.cols, S.batch) : 0);
     const size_t n = (size_t)S.rows * S.cols * S.batch;
     const size_t fb = n * (channels == 3 ? 3 : elem_size(in.dtype));
     const ByteRange ins[3] = {{in.I0, fb}, {in.I1, fb}, {ws, need}};
-    ByteRange outs[3];
+    ByteRange outs[4];
     interp_out_ranges(O, n, S.batch, channels, outs);
-    if (!outputs_disjoint(ins, 3, outs, 3))
+    if (!outputs_disjoint(ins, 3, outs, 4))
         return fail(ctx, HSFLOW_ERR_ARG,
                     "interpolation outputs overlap the frames, the workspace or each other");
-    if ((rc = check_init(ctx, S, true, outs, 3, ws, ws_bytes, need))) return rc;
+    if ((rc = check_init(ctx, S, true, outs, 4, ws, ws_bytes, need))) return rc;
     char *base = (char *)ws;
     uint8_t *const grey[2] = {(uint8_t *)(base + L.gray[0]), (uint8_t *)(base + L.gray[1])};
     Frames F;
@@ -891,14 +966,18 @@ int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Fr
     uint8_t *mb = masks ? (uint8_t *)(base + L.mask[1]) : nullptr;
     float *f[4];
     for (int k = 0; k < 4; ++k) f[k] = (float *)(base + L.flow[k]);
-    const BidirOut B{f[0], f[1], f[2], f[3], {nullptr, mf, nullptr}, {nullptr, mb, nullptr},
-                     rel,  abs_thr};
+    uint32_t *cf = fallback ? (uint32_t *)(base + L.counts[0]) : nullptr;
+    uint32_t *cb = fallback ? (uint32_t *)(base + L.counts[1]) : nullptr;
+    const BidirOut B{f[0], f[1], f[2], f[3], {nullptr, mf, cf}, {nullptr, mb, cb}, rel, abs_thr};
     if ((rc = bidir_run(ctx, S, F, B, ws, s))) return rc;
     uint64_t *cells = S.projection ? (uint64_t *)(base + L.cells) : nullptr;
     const FlowsIn W{f[0], f[1], f[2], f[3], mf, mb, cells};
     if (cells && (rc = project_run(ctx, F, S.rows, S.cols, S.batch, W, O.times, O.nt, cells, s)))
         return rc;
-    return frame_interp_run(ctx, channels, in, S.rows, S.cols, S.batch, W, O, s);
+    if ((rc = frame_interp_run(ctx, channels, in, S.rows, S.cols, S.batch, W, O, s))) return rc;
+    if (fallback) return fallback_run(ctx, channels, in, S.rows, S.cols, S.batch, cf, cb, *S.fb, O, s);
+    if (O.cut) HIP_TRY(ctx, hipMemsetAsync(O.cut, 0, (size_t)S.batch, s));
+    return HSFLOW_OK;
 }
 
 // The host-buffer form of both: the frames go up as they are (BGR: 3 B/px),
@@ -911,6 +990,8 @@ int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Fr
 // In sequence mode (hsflow_ctx_set_temporal) the solve starts from the
 // context's stored prediction and KP of its (ub, vb), which lie in the
 // workspace, follows it on the stream ahead of the downloads.
+// With the context's fallback on, the verdict comes down behind trusted; a cut
+// leaves no prediction behind, so the next call starts cold.
 int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const void *I0,
                      const void *I1, int dtype_in, size_t step0, size_t step1, float rel,
                      float abs_thr, const HostInterpOut &O) {
@@ -918,6 +999,7 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
     SolveSpec S = spec;
     const int rows = S.rows, cols = S.cols, nt = O.nt;
     if (!bgr && !ctx) return HSFLOW_ERR_ARG;
+    if (ctx) ctx->last_cut = -1;
     hsflow_flow_init init;
     if (ctx && take_prediction(ctx, rows, cols, &init)) S.init = &init;
     int rc = check_interp_args(ctx, O.times, nt, O.dtype_out, !bgr);
@@ -952,7 +1034,8 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
     const size_t ob = align_up(n * nt * channels * elem_size(dev_out)), flb = align_up(n * nt);
     if ((rc = check_projection(ctx, S.projection))) return rc;
     const int cell_nt = S.projection ? nt : 0;
-    const size_t wsb = interp_layout(rows, cols, 1, S.levels, channels, cell_nt).bytes +
+    const bool fb = fb_on(S.fb);
+    const size_t wsb = interp_layout(rows, cols, 1, S.levels, channels, cell_nt, fb).bytes +
                        (pf_on(S.pf) ? pf_planes_bytes(rows, cols, 1) : 0);
     char *in0, *in1;
     rc = stage_pair(ctx, I0, I1, bgr ? 3 : elem_size(dtype_in), rows, cols, step0, step1,
@@ -961,12 +1044,13 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
     char *dout = (char *)ctx->d_out;
     uint8_t *dfl = (uint8_t *)(dout + ob);
     uint32_t *dtr = (uint32_t *)(dout + ob + flb);
+    uint8_t *dcut = (uint8_t *)(dtr + HSFLOW_MAX_TIMES);  // within the kAlign bytes
     const InterpOut D{O.times, nt, dout, dev_out, O.flags ? dfl : nullptr,
-                      O.trusted ? dtr : nullptr};
+                      O.trusted ? dtr : nullptr, fb ? dcut : nullptr};
     rc = flow_interp_impl(ctx, S, channels, Frames{in0, in1, dtype_in}, rel, abs_thr, D, ctx->d_ws,
                           ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
-    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, channels, cell_nt);
+    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, channels, cell_nt, fb);
     rc = predict_run(ctx, (const float *)((char *)ctx->d_ws + L.flow[2]),
                      (const float *)((char *)ctx->d_ws + L.flow[3]), rows, cols);
     if (rc) return rc;
@@ -978,29 +1062,38 @@ int flow_interp_host(hsflow_ctx *ctx, const SolveSpec &spec, int channels, const
     if (O.trusted)
         HIP_TRY(ctx, hipMemcpyAsync(O.trusted, dtr, (size_t)nt * sizeof(uint32_t),
                                     hipMemcpyDeviceToHost, ctx->stream));
+    if (fb)
+        HIP_TRY(ctx, hipMemcpyAsync(&ctx->cut_byte, dcut, 1, hipMemcpyDeviceToHost, ctx->stream));
+    // the stream has drained: the verdict is here, and a cut keeps no prediction
+    const auto finish = [&](int status) {
+        if (status || !fb) return keep_prediction(ctx, status);
+        ctx->last_cut = ctx->cut_byte ? 1 : 0;
+        return ctx->last_cut ? HSFLOW_OK : keep_prediction(ctx, HSFLOW_OK);
+    };
     if (dev_out == HSFLOW_U8) {
         for (int k = 0; k < nt; ++k)
             HIP_TRY(ctx, hipMemcpy2DAsync(O.out[k], O.out_step, dout + k * n * channels, row, row,
                                           rows, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return keep_prediction(ctx, HSFLOW_OK);
+        return finish(HSFLOW_OK);
     }
     // f32 (widened to f64 on the way for the grey call): a plane is rows x
     // channels * cols floats
     const float *srcs[HSFLOW_MAX_TIMES];
     for (int k = 0; k < nt; ++k) srcs[k] = (const float *)dout + k * n * channels;
-    return keep_prediction(ctx, download_planes(ctx, srcs, O.out, nt, rows, cols * channels,
-                                                O.dtype_out, O.out_step));
+    return finish(download_planes(ctx, srcs, O.out, nt, rows, cols * channels, O.dtype_out,
+                                  O.out_step));
 }
 
 // a host form's spec: one pair, the context's finest level, prefilter,
-// smoothness and projection
+// smoothness, projection and fallback
 SolveSpec host_spec(const hsflow_ctx *ctx, int rows, int cols, int levels, int warps, int median,
                     int window, int iters, double alpha) {
     return SolveSpec{rows,   cols,   1,     levels,       ctx ? ctx->finest : 0,
                      warps,  median, window, iters,       (float)alpha,
                      ctx ? &ctx->pf : nullptr,            ctx ? &ctx->sm : nullptr,
-                     nullptr,                             ctx ? ctx->projection : 0};
+                     nullptr,                             ctx ? ctx->projection : 0,
+                     ctx ? &ctx->fb : nullptr};
 }
 
 }  // namespace
@@ -1354,12 +1447,59 @@ int hsflow_flow_interp_pj_device(const void *I0, const void *I1, int dtype_in, i
                                  const hsflow_prefilter *pf, const hsflow_smoothness *sm,
                                  const hsflow_flow_init *init, void *workspace,
                                  size_t workspace_bytes, void *stream) {
+    return hsflow_flow_interp_fb_device(I0, I1, dtype_in, rows, cols, batch, levels, finest, warps,
+                                        median, window, iters, alpha, rel, abs_thr, times, nt,
+                                        projection, out, dtype_out, flags, trusted, nullptr, pf,
+                                        sm, init, nullptr, workspace, workspace_bytes, stream);
+}
+
+int hsflow_flow_interp_fb_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, int projection, void *out,
+                                 int dtype_out, uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 const hsflow_flow_init *init, const hsflow_fallback *fb,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
-                      window, iters, alpha, pf,     sm,     init,  projection};
+    const SolveSpec S{rows,  cols,  batch, levels, finest, warps,      median, window,
+                      iters, alpha, pf,    sm,     init,   projection, fb};
     return flow_interp_impl(nullptr, S, 1, Frames{I0, I1, dtype_in}, rel, abs_thr,
-                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted, cut}, workspace,
                             workspace_bytes, (hipStream_t)stream);
+}
+
+size_t hsflow_fallback_min_consistent(int rows, int cols, float min_share) {
+    if (!sizes_ok(rows, cols, 1) || !(min_share >= 0.0f && min_share <= 1.0f)) return 0;
+    return (size_t)min_consistent(rows, cols, min_share);
+}
+
+size_t hsflow_fallback_counts_bytes(int batch) {
+    if (batch < 1 || batch > kMaxBatch) return 0;
+    return fb_counts_bytes(batch);
+}
+
+int hsflow_frame_fallback_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, const uint32_t *counts_f, const uint32_t *counts_b,
+                                 const hsflow_fallback *fb, const float *times, int nt, void *out,
+                                 int dtype_out, uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                 void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return fallback_impl(nullptr, 1, Frames{I0, I1, dtype_in}, rows, cols, batch, counts_f,
+                         counts_b, fb, InterpOut{times, nt, out, dtype_out, flags, trusted, cut},
+                         (hipStream_t)stream);
+}
+
+int hsflow_frame_fallback_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, const uint32_t *counts_f,
+                                     const uint32_t *counts_b, const hsflow_fallback *fb,
+                                     const float *times, int nt, void *out, int dtype_out,
+                                     uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                     void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return fallback_impl(nullptr, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rows, cols, batch, counts_f,
+                         counts_b, fb, InterpOut{times, nt, out, dtype_out, flags, trusted, cut},
+                         (hipStream_t)stream);
 }
 
 size_t hsflow_flow_interp_workspace_bytes(int rows, int cols, int batch, int levels) {
@@ -1493,11 +1633,27 @@ int hsflow_flow_interp_bgr_pj_device(const uint8_t *bgr0, const uint8_t *bgr1, i
                                      const hsflow_prefilter *pf, const hsflow_smoothness *sm,
                                      const hsflow_flow_init *init, void *workspace,
                                      size_t workspace_bytes, void *stream) {
+    return hsflow_flow_interp_bgr_fb_device(bgr0, bgr1, rows, cols, batch, levels, finest, warps,
+                                            median, window, iters, alpha, rel, abs_thr, times, nt,
+                                            projection, out, dtype_out, flags, trusted, nullptr,
+                                            pf, sm, init, nullptr, workspace, workspace_bytes,
+                                            stream);
+}
+
+int hsflow_flow_interp_bgr_fb_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int finest, int warps, int median,
+                                     int window, int iters, float alpha, float rel,
+                                     float abs_thr, const float *times, int nt, int projection,
+                                     void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                     uint8_t *cut, const hsflow_prefilter *pf,
+                                     const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                     const hsflow_fallback *fb, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
     DeviceGuard g((hipStream_t)stream);
-    const SolveSpec S{rows,   cols,  batch, levels, finest, warps, median,
-                      window, iters, alpha, pf,     sm,     init,  projection};
+    const SolveSpec S{rows,  cols,  batch, levels, finest, warps,      median, window,
+                      iters, alpha, pf,    sm,     init,   projection, fb};
     return flow_interp_impl(nullptr, S, 3, Frames{bgr0, bgr1, HSFLOW_U8}, rel, abs_thr,
-                            InterpOut{times, nt, out, dtype_out, flags, trusted}, workspace,
+                            InterpOut{times, nt, out, dtype_out, flags, trusted, cut}, workspace,
                             workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1682,6 +1838,26 @@ int hsflow_ctx_projection(const hsflow_ctx *ctx) {
     if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
     return ctx->projection;
 }
+
+int hsflow_ctx_set_fallback(hsflow_ctx *ctx, const hsflow_fallback *fb) {
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    if (fb_on(fb)) {
+        int rc = check_fallback(ctx, fb);
+        if (rc) return rc;
+        ctx->fb = *fb;
+    } else {
+        ctx->fb = hsflow_fallback{HSFLOW_FALLBACK_OFF, 0.0f};
+    }
+    return HSFLOW_OK;
+}
+
+int hsflow_ctx_fallback(const hsflow_ctx *ctx, hsflow_fallback *fb) {
+    if (!ctx || !fb) return fail(nullptr, HSFLOW_ERR_ARG, "null %s", ctx ? "fallback" : "context");
+    *fb = ctx->fb;
+    return HSFLOW_OK;
+}
+
+int hsflow_ctx_last_cut(const hsflow_ctx *ctx) { return ctx ? ctx->last_cut : -1; }
 
 int hsflow_ctx_finest_level(const hsflow_ctx *ctx) {
     if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");

@@ -131,6 +131,23 @@ hipError_t launch_frame_interp_bgr_proj(const uint8_t *I0, const uint8_t *I1, in
                                         const uint8_t *mask_b, const uint64_t *cells,
                                         const float *times, int nt, void *out, bool out_u8,
                                         uint8_t *flags, uint32_t *trusted, hipStream_t s);
+// KF (hsflow_fallback.hip): for every pair whose consistent pixels, counts_f[b][0]
+// + counts_b[b][0] of KC's counts as a 64-bit sum, number fewer than
+// min_consistent: out of all nt times = I0 / I1 by `mode` (1: the nearer frame,
+// 2: KI's blend at wt = t), flags = 32, trusted[b][t] = 0; cut[b] = the verdict
+// of every pair.  A pair that passes keeps its out, flags and trusted.  flags,
+// trusted and cut may be null.  `times` is read on the host at launch.
+hipError_t launch_frame_fallback(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, const uint32_t *counts_f, const uint32_t *counts_b,
+                                 uint64_t min_consistent, int mode, const float *times, int nt,
+                                 void *out, bool out_u8, uint8_t *flags, uint32_t *trusted,
+                                 uint8_t *cut, hipStream_t s);
+hipError_t launch_frame_fallback_bgr(const uint8_t *I0, const uint8_t *I1, int rows, int cols,
+                                     int batch, const uint32_t *counts_f,
+                                     const uint32_t *counts_b, uint64_t min_consistent, int mode,
+                                     const float *times, int nt, void *out, bool out_u8,
+                                     uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                     hipStream_t s);
 // how KRC and KIC fetch the two adjacent taps of a row: as six bytes (on == 0,
 // default) or as one unaligned dword and halfword; same bits.  Returns the
 // previous setting.

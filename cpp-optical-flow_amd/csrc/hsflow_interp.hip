@@ -26,8 +26,9 @@
 //     <= 16 times, which travel by value in the kernel arguments: a thread
 //     loads the four flow values of each of its two pixels once and loops over
 //     the times.  trusted[pair][time] counts the pixels with flags == 0.
-//     The kernel is the sampler's, written once over a frame policy: GreyFrame
-//     here, BgrFrame in hsflow_interp_bgr.hip (KIC).
+//     The kernel is the sampler's, written once over a frame policy
+//     (hsflow_frame_policy.h): GreyFrame here, BgrFrame in hsflow_interp_bgr.hip
+//     (KIC).
 //
 // HBM-bound: 16 B/px of flows once and, per time, 8 B/px of f32 frames (the
 // taps of neighbouring pixels overlap) read, 4 + 1 B/px written.  KI's map is
@@ -45,6 +46,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hsflow_frame_policy.h"
 #include "hsflow_internal.h"
 #include "hsflow_sampler.h"
 
@@ -70,28 +72,6 @@ __global__ __launch_bounds__(256) void hs_warp_image_kernel(
     out[o] = (float)sample_plane(I + blockIdx.z * plane, cols, t);
     if (oof) oof[o] = in ? 0 : 1;
 }
-
-// ---- KI: hs_frame_interp_kernel on a grey frame of T
-template <typename T>
-struct GreyFrame {
-    using Elem = T;
-    static constexpr int kChannels = 1;
-    // six blocks of four waves are resident per CU (64 to 68 VGPRs: 7 waves
-    // per SIMD; the cap predates that count)
-    static constexpr int kBlocksPerCu = 6;
-    using Px = float;
-    static __device__ __forceinline__ float sample(const T *__restrict__ img, int cols,
-                                                   const Taps &t) {
-        return (float)sample_plane(img, cols, t);
-    }
-    static __device__ __forceinline__ void store_f32(void *out, size_t px, float o) {
-        ((float *)out)[px] = o;
-    }
-    static __device__ __forceinline__ void store_u8(void *out, size_t obase, int pk, int q0,
-                                                    bool whole, bool valid, float o, int lane) {
-        store_quad_u8((uint8_t *)out + obase, pk, q0, whole, valid, round_u8(o), lane);
-    }
-};
 
 }  // namespace
 

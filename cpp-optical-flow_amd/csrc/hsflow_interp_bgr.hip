@@ -33,11 +33,14 @@
 // quad collect one each over DPP and store it, else (ragged quads at a
 // plane's ends, odd planes, unaligned bases) every valid lane stores its three
 // bytes.  An f32 pixel is one 12-byte store.  Byte offsets are size_t.
+// The loads, the stores and BgrFrame are in hsflow_frame_policy.h, which KF
+// (hsflow_fallback.hip) shares.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <atomic>
 
+#include "hsflow_frame_policy.h"
 #include "hsflow_internal.h"
 #include "hsflow_sampler.h"
 
@@ -47,77 +50,6 @@ namespace {
 using namespace sampler;
 
 std::atomic<int> g_wide_loads{0};
-
-using Bgr = Pixel<3>;
-
-__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-__device__ __forceinline__ uint32_t load_u16_unaligned(const uint8_t *p) {
-    uint16_t v;
-    __builtin_memcpy(&v, p, 2);
-    return v;
-}
-
-// the taps xa and xb of one row of a BGR plane (row: its first byte)
-template <bool Wide>
-__device__ __forceinline__ void row_taps(const uint8_t *__restrict__ row, int xa, int xb, Bgr &a,
-                                         Bgr &b) {
-    const uint8_t *pa = row + (size_t)xa * 3;
-    if (Wide && xb != xa) {  // xb == xa + 1: six bytes of this row
-        const uint32_t lo = load_u32_unaligned(pa), hi = load_u16_unaligned(pa + 4);
-        a.c[0] = (float)(lo & 0xFF), a.c[1] = (float)((lo >> 8) & 0xFF);
-        a.c[2] = (float)((lo >> 16) & 0xFF), b.c[0] = (float)(lo >> 24);
-        b.c[1] = (float)(hi & 0xFF), b.c[2] = (float)(hi >> 8);
-    } else {
-        const uint8_t *pb = row + (size_t)xb * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.c[c] = (float)pa[c], b.c[c] = (float)pb[c];
-    }
-}
-
-// img (one pair's BGR plane) at the taps `t`: KR's sample, per channel
-template <bool Wide>
-__device__ __forceinline__ Bgr sample_bgr(const uint8_t *__restrict__ img, int cols,
-                                          const Taps &t) {
-    Bgr ta, tb, ba, bb, r;
-    row_taps<Wide>(img + (size_t)t.ya * cols * 3, t.xa, t.xb, ta, tb);
-    row_taps<Wide>(img + (size_t)t.yb * cols * 3, t.xa, t.xb, ba, bb);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) r.c[c] = lerp_taps(ta.c[c], tb.c[c], ba.c[c], bb.c[c], t.fx, t.fy);
-    return r;
-}
-
-// Three bytes per lane (bgr: B | G << 8 | R << 16) into a u8 BGR plane: quad:
-// the first byte of the lane's quad of pixels, whole: its four pixels lie in
-// the plane.  Three aligned dwords per quad where the address allows, else
-// three bytes per valid lane.  Every lane of the wave calls.
-__device__ __forceinline__ void store_quad_bgr_u8(uint8_t *quad, bool whole, bool valid,
-                                                  uint32_t bgr, int lane) {
-    const uint32_t p0 = quad_lane<0>(bgr), p1 = quad_lane<1>(bgr), p2 = quad_lane<2>(bgr),
-                   p3 = quad_lane<3>(bgr);
-    const int j = lane & 3;
-    if (whole && ((uintptr_t)quad & 3) == 0) {
-        // bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
-        const uint32_t w = j == 0 ? (p0 | p1 << 24) : j == 1 ? (p1 >> 8 | p2 << 16)
-                                                             : (p2 >> 16 | p3 << 8);
-        if (j < 3) reinterpret_cast<uint32_t *>(quad)[j] = w;
-    } else if (valid) {
-        uint8_t *d = quad + j * 3;
-        d[0] = (uint8_t)bgr, d[1] = (uint8_t)(bgr >> 8), d[2] = (uint8_t)(bgr >> 16);
-    }
-}
-
-__device__ __forceinline__ uint32_t pack_u8(const Bgr &o) {
-    return round_u8(o.c[0]) | round_u8(o.c[1]) << 8 | round_u8(o.c[2]) << 16;
-}
-
-// one f32 pixel: a 12-byte store (the plane is 4-byte aligned)
-struct alignas(4) Float3 {
-    float c[3];
-};
 
 // ---- KRC: block 64 x 4, one pixel per thread (KR's map);
 // grid (ceil(cols/64), ceil(rows/4), batch).  Every lane computes (a lane past
@@ -145,29 +77,6 @@ __global__ __launch_bounds__(256) void hs_warp_image_bgr_kernel(
     }
     if (oof && valid) oof[o] = in ? 0 : 1;
 }
-
-// ---- KIC: hs_frame_interp_kernel on a BGR frame
-template <bool Wide>
-struct BgrFrame {
-    using Elem = uint8_t;
-    static constexpr int kChannels = 3;
-    using Px = Bgr;
-    // 84 VGPRs with wide loads: five waves per SIMD, five blocks per CU (80
-    // with byte loads, which would let a sixth in; one cap for both forms)
-    static constexpr int kBlocksPerCu = 5;
-    static __device__ __forceinline__ Bgr sample(const uint8_t *__restrict__ img, int cols,
-                                                 const Taps &t) {
-        return sample_bgr<Wide>(img, cols, t);
-    }
-    static __device__ __forceinline__ void store_f32(void *out, size_t px, const Bgr &o) {
-        reinterpret_cast<Float3 *>(out)[px] = Float3{{o.c[0], o.c[1], o.c[2]}};
-    }
-    static __device__ __forceinline__ void store_u8(void *out, size_t obase, int, int q0,
-                                                    bool whole, bool valid, const Bgr &o, int lane) {
-        store_quad_bgr_u8((uint8_t *)out + (obase + (size_t)q0) * 3, whole, valid, pack_u8(o),
-                          lane);
-    }
-};
 
 }  // namespace
 

@@ -329,7 +329,7 @@ def solve_stream(src, pairs: Sequence[Tuple[int, int]], window: int, iters: int,
 def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int, iters: int,
                          alpha: float, median: int = 0, context=None, prefilter=None,
                          smoothness=None, temporal: bool = False, finest=None,
-                         projection=None):
+                         projection=None, fallback=None, cuts=None):
     """A colour source at `factor` times its frame rate: a generator of
     (len(src) - 1) * factor + 1 BGR uint8 frames.  Every factor-th one is a
     source frame itself, untouched; between two consecutive source frames come
@@ -344,15 +344,24 @@ def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int,
     `temporal`: run the clip in the context's sequence mode (temporal.sequence):
     every pair but the first starts from the flow predicted from the pair
     before it, so fewer warps do (keep `levels` and halve `warps` when motion
-    may change; levels = 1 only for steady motion; a clip with a scene cut is
-    two calls).  The context's own setting is restored when the generator ends
+    may change; levels = 1 only for steady motion; with `fallback` a pair across
+    a scene cut drops the prediction, so the pair after it starts cold; without
+    it the prediction crosses the cut).  The context's own setting is restored when the generator ends
     or is closed.  False solves every pair cold.  `finest`: the last pyramid
     level every pair's solve goes down to (coarse.set_finest_level): 1 solves
     the flow at half resolution, a quarter of the pixels, and interpolates at
     full resolution; None: the context's own setting, 0 by default.
     `projection`: 1 carries every pair's flows to each time before the blend
     (projection.set_projection), which takes about a third off the error
-    around moving objects; None: the context's own setting, 0 by default."""
+    around moving objects; None: the context's own setting, 0 by default.
+    `fallback`: an hsflow.Fallback (fallback.set_fallback): the in-between
+    frames of a pair whose flows fail the forward-backward check -- a scene
+    cut, a motion beyond the pyramid's reach -- are the nearer source frame
+    (FALLBACK_NEAREST) or a cross-fade (FALLBACK_BLEND), not a morph of two
+    unrelated pictures; None: the context's own setting, off by default.
+    `cuts`: a list; the index i of the second frame of every failed pair is
+    appended to it as the pair is reached.  A pair that is a cut in half the
+    picture is not decided by any threshold."""
     factor = int(factor)
     if factor < 1:
         raise ValueError("factor must be at least 1")
@@ -379,7 +388,9 @@ def interpolate_sequence(src, factor: int, levels: int, warps: int, window: int,
                 mid = ctx.interpolate_bgr(prev, nxt, times, levels, warps, window, iters, alpha,
                                           median=median, out_dtype=np.uint8, prefilter=prefilter,
                                           smoothness=smoothness, finest=finest,
-                                          projection=projection)
+                                          projection=projection, fallback=fallback)
+                if cuts is not None and ctx.last_cut:
+                    cuts.append(i)
                 for k in range(len(times)):
                     yield mid[k]
             yield nxt

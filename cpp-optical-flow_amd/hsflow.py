@@ -112,6 +112,33 @@ class Smoothness(collections.namedtuple("Smoothness", "mode lam")):
         return self._C(*self)
 
 
+# what the interpolating calls do with a pair whose flows fail the
+# forward-backward check (HSFLOW_FALLBACK_*) and the default share of consistent
+# pixels below which a pair fails; fallback.py is their public face
+_FALLBACK_OFF, _FALLBACK_NEAREST, _FALLBACK_BLEND = 0, 1, 2
+_FALLBACK_MIN_SHARE = 0.4
+
+
+class _CFallback(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("min_share", ctypes.c_float)]
+
+
+class _Fallback(collections.namedtuple("Fallback", "mode min_share")):
+    """hsflow_fallback: what becomes of a pair whose share of consistent pixels,
+    both directions together, is below `min_share` -- a scene cut, a motion
+    beyond the pyramid's reach.  FALLBACK_NEAREST: every frame of the pair is
+    the nearer source frame; FALLBACK_BLEND: a cross-fade (include/hsflow.h,
+    "fallback for a failed pair"; fallback.Fallback is its public name)."""
+    __slots__ = ()
+    _C, _GET, _SET = _CFallback, "hsflow_ctx_fallback", "hsflow_ctx_set_fallback"
+
+    def __new__(cls, mode=_FALLBACK_NEAREST, min_share=_FALLBACK_MIN_SHARE):
+        return super().__new__(cls, int(mode), float(min_share))
+
+    def _c(self):
+        return self._C(*self)
+
+
 class _CFlowInit(ctypes.Structure):
     """hsflow_flow_init: the planes a warped solve starts from (temporal.py)."""
     _fields_ = [("uf", ctypes.c_void_p), ("vf", ctypes.c_void_p), ("ub", ctypes.c_void_p),
@@ -119,8 +146,8 @@ class _CFlowInit(ctypes.Structure):
 
 
 def _option(kind, value):
-    """(keep-alive struct, pointer or None) of an option of `kind` (Prefilter
-    or Smoothness): an instance, a plain tuple of its fields, or None."""
+    """(keep-alive struct, pointer or None) of an option of `kind` (Prefilter,
+    Smoothness or fallback.Fallback): an instance, a plain tuple of its fields, or None."""
     if value is None:
         return None, None
     if not isinstance(value, kind):
@@ -151,6 +178,7 @@ def _prototypes():
     ip, fp, vpp, text = ctypes.POINTER(i), ctypes.POINTER(f), ctypes.POINTER(vp), ctypes.c_char_p
     pf, sm = [ctypes.POINTER(_CPrefilter)], [ctypes.POINTER(_CSmoothness)]
     init = [ctypes.POINTER(_CFlowInit)]
+    fb = [ctypes.POINTER(_CFallback)]
     shape = [i, i, i]                              # rows, cols, batch
     dev_pair = [vp, vp, i] + shape                 # I0, I1, dtype, rows, cols, batch
     dev_bgr_pair = [vp, vp] + shape                # bgr0, bgr1, rows, cols, batch
@@ -168,6 +196,7 @@ def _prototypes():
     host_bidir_out = flows + [i, sz, vp, vp, sz, vp]   # + dtype, step, masks, step, counts
     times_out = [fp, i, vp, i, vp, vp]             # times, n, out, out dtype, flags, trusted
     times_pj_out = [fp, i, i, vp, i, vp, vp]       # times, n, projection, out, ...
+    times_fb_out = times_pj_out + [vp]             # ... and cut
     host_times_out = [fp, i, vpp, i, sz, vpp, sz, vp]  # planes and their steps
     tail = [vp, sz, vp]                            # workspace, bytes, stream
     sized = (sz, shape + [i])                      # a workspace size of a shape and levels
@@ -295,6 +324,21 @@ def _prototypes():
                                              + pf + sm + init + tail),
         "hsflow_ctx_set_projection": (i, [vp, i]),
         "hsflow_ctx_projection": (i, [vp]),
+        # the fallback for a failed pair (fallback.py is its public face): KF on
+        # grey and BGR frames, the fused calls with cut after trusted and the
+        # setting after init
+        "hsflow_fallback_min_consistent": (sz, [i, i, f]),
+        "hsflow_frame_fallback_device": (i, dev_pair + [vp, vp] + fb + times_out + [vp, vp]),
+        "hsflow_frame_fallback_bgr_device": (i, dev_bgr_pair + [vp, vp] + fb + times_out
+                                             + [vp, vp]),
+        "hsflow_fallback_counts_bytes": (sz, [i]),
+        "hsflow_flow_interp_fb_device": (i, dev_pair + solve_lv + thresholds + times_fb_out + pf
+                                         + sm + init + fb + tail),
+        "hsflow_flow_interp_bgr_fb_device": (i, dev_bgr_pair + solve_lv + thresholds + times_fb_out
+                                             + pf + sm + init + fb + tail),
+        "hsflow_ctx_set_fallback": (i, [vp] + fb),
+        "hsflow_ctx_fallback": (i, [vp] + fb),
+        "hsflow_ctx_last_cut": (i, [vp]),
         "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
         "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
         "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),
@@ -512,7 +556,7 @@ class Context:
 
     @contextlib.contextmanager
     def _setting_as(self, kind, value):
-        """`value` (a Prefilter or a Smoothness) on the context for one call,
+        """`value` (a Prefilter, a Smoothness or a Fallback) on the context for one call,
         the setting before it restored afterwards; None leaves the context's own."""
         if value is None:
             yield
@@ -552,13 +596,24 @@ class Context:
         finally:
             self._set_projection(was)
 
-    def _call_with(self, prefilter, smoothness, name, *args, finest=None, projection=None):
-        """_call with `prefilter`, `smoothness`, `finest` and `projection` as the
-        context's settings."""
+    def _call_with(self, prefilter, smoothness, name, *args, finest=None, projection=None,
+                   fallback=None):
+        """_call with `prefilter`, `smoothness`, `finest`, `projection` and
+        `fallback` as the context's settings."""
         with self._setting_as(Prefilter, prefilter), self._setting_as(Smoothness, smoothness), \
-                self._finest_as(finest), self._projection_as(projection):
+                self._finest_as(finest), self._projection_as(projection), \
+                self._setting_as(_Fallback, fallback):
             rc = getattr(lib(), name)(self._p, *args)
         _check(rc, self._p)
+
+    @property
+    def last_cut(self):
+        """The verdict of the last interpolate / interpolate_bgr on this context
+        (hsflow_ctx_last_cut): True where the pair failed the check and the
+        fallback made its frames, False where it passed, None where there was
+        no such call or the fallback was off."""
+        rc = int(lib().hsflow_ctx_last_cut(self._p))
+        return None if rc < 0 else bool(rc)
 
     def _set_projection(self, projection):
         """hsflow_ctx_set_projection (projection.set_projection is its public face)."""
@@ -687,7 +742,7 @@ class Context:
                     alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                     abs: float = CONSISTENCY_ABS, out_dtype=np.float32,
                     with_flags: bool = False, prefilter=None, smoothness=None, finest=None,
-                    projection=None):
+                    projection=None, fallback=None):
         """The frames at `times` (each in [0, 1]; at most MAX_TIMES) between I0
         and I1: the bidirectional warped solve, then the motion-compensated
         blend (hsflow_flow_interp in include/hsflow.h).  Returns an array
@@ -700,20 +755,25 @@ class Context:
         flow_warped: the flows are solved down to that level only, the frames
         are sampled at full resolution.  projection: 1 carries the flows to each
         time before the blend (projection.set_projection; None: the context's
-        own, 0 by default); flags then has FLAG bit 16 where nothing landed."""
+        own, 0 by default); flags then has FLAG bit 16 where nothing landed.
+        fallback: a fallback.Fallback (fallback.set_fallback; None: the context's own,
+        off by default): where the pair fails the check every frame is a
+        source frame or a cross-fade, flags is fallback.FLAG_FALLBACK, trusted 0 and
+        Context.last_cut True."""
         a, b, rows, cols = _host_pair(I0, I1)
         out, flags, trusted, outs = _host_interp_out(times, (rows, cols), out_dtype,
                                                      (np.uint8, np.float32, np.float64), with_flags)
         self._call_with(prefilter, smoothness, "hsflow_flow_interp", *_pair_args(a, b),
                         *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                        float(abs), *outs, finest=finest, projection=projection)
+                        float(abs), *outs, finest=finest, projection=projection,
+                        fallback=fallback)
         return (out, flags, trusted) if with_flags else out
 
     def interpolate_bgr(self, bgr0, bgr1, times, levels: int, warps: int, window: int,
                         iters: int, alpha: float, median: int = 0,
                         rel: float = CONSISTENCY_REL, abs: float = CONSISTENCY_ABS,
                         out_dtype=np.uint8, with_flags: bool = False, prefilter=None,
-                        smoothness=None, finest=None, projection=None):
+                        smoothness=None, finest=None, projection=None, fallback=None):
         """The colour frames at `times` between two decoded 8-bit BGR frames
         (H x W x 3, strided rows accepted): uploaded as BGR, converted to grey
         and solved both ways on the GPU, then the motion-compensated blend of
@@ -723,13 +783,14 @@ class Context:
         cols] and trusted uint32 [len(times)] as in interpolate.  prefilter as
         in flow_warped, run on the grey planes; smoothness and finest as in
         flow_warped; projection as in interpolate (the cells come from the grey
-        planes)."""
+        planes); fallback as in interpolate."""
         a, b, rows, cols = _host_bgr_pair(bgr0, bgr1, " (grey frames: Context.interpolate)")
         out, flags, trusted, outs = _host_interp_out(times, (rows, cols, 3), out_dtype,
                                                      (np.uint8, np.float32), with_flags)
         self._call_with(prefilter, smoothness, "hsflow_flow_interp_bgr", *_pair_args(a, b),
                         *_solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                        float(abs), *outs, finest=finest, projection=projection)
+                        float(abs), *outs, finest=finest, projection=projection,
+                        fallback=fallback)
         return (out, flags, trusted) if with_flags else out
 
     def flow_bgr(self, bgr0, bgr1, window: int, iters: int, alpha: float,
@@ -1036,11 +1097,13 @@ def _plane(t, like, dims, name):
     return t
 
 
-def _workspace(workspace, device, size_fn, *size_args, prefilter=None):
+def _workspace(workspace, device, size_fn, *size_args, prefilter=None, fallback=None):
     """The given workspace, or size_fn(rows, cols, batch[, levels]) bytes on
-    `device`, with the prefilter's planes where one is on."""
+    `device`, with the prefilter's planes and the fallback's counts where one
+    is on."""
     if workspace is None:
-        n = size_fn(*size_args) + _pf_extra(prefilter, *size_args[:3])
+        n = size_fn(*size_args) + _pf_extra(prefilter, *size_args[:3]) + \
+            _fb_extra(fallback, size_args[2])
         workspace = torch.empty(n, dtype=torch.uint8, device=device)
     return workspace
 
@@ -1104,6 +1167,27 @@ def _pj_entry(stem, init, dims, finest, projection):
     if not projection:
         return name, lv, start, ()
     return stem + "_pj_device", (int(finest),), start or (None,), (int(projection),)
+
+
+def _fb_entry(stem, init, dims, finest, projection, fallback, cut, device):
+    """_pj_entry plus the fallback's arguments: (name, lv, start, pj, cut
+    tensor, arguments after trusted, arguments after the init).  fallback None
+    and no cut: _pj_entry as it stands; else the *_fb_device call, which takes
+    finest, projection, `cut` (uint8 [B], allocated for True) after trusted and
+    the hsflow_fallback (NULL for None) after an init or NULL."""
+    if fallback is None and (cut is None or cut is False):
+        return _pj_entry(stem, init, dims, finest, projection) + (None, (), ())
+    _, _, start = _init_entry(stem, init, dims, finest)
+    cut = _check_output(cut, (dims[2],), torch.uint8, device, "cut")
+    keep, fb = _option(_Fallback, fallback)
+    return (stem + "_fb_device", (int(finest),), start or (None,), (int(projection),), cut,
+            (_ptr(cut),), (fb,))
+
+
+def _fb_extra(fallback, batch):
+    """The bytes a fused call's workspace grows by with `fallback` on."""
+    on = fallback is not None and int(fallback[0]) != _FALLBACK_OFF
+    return int(lib().hsflow_fallback_counts_bytes(batch)) if on else 0
 
 
 def _pj_size(size_fn, stem, projection, levels, nt):
@@ -1338,7 +1422,8 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
                        alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                        abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                        trusted=None, workspace=None, stream=None, prefilter=None,
-                       smoothness=None, finest: int = 0, projection: int = 0):
+                       smoothness=None, finest: int = 0, projection: int = 0, fallback=None,
+                       cut=None):
     """flow_bidir_device(median=...) into planes of the workspace, then
     frame_interp_device with both masks: one call, the same bits
     (hsflow_flow_interp_device in include/hsflow.h).  `workspace`:
@@ -1351,15 +1436,21 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
     the frames the solve ran on stands between the two and the interpolation
     is projection.frame_interp_device (hsflow_flow_interp_pj_device; the
     workspace grows by the cells, projection.flow_interp_workspace_bytes).
-    Returns (out, flags, trusted) as frame_interp_device.  Stream-ordered."""
+    fallback: a fallback.Fallback; both checks then always run and
+    fallback.frame_fallback_device follows the interpolation
+    (hsflow_flow_interp_fb_device; fallback.counts_bytes more workspace).  cut:
+    True or a uint8 tensor [B] for the verdict per pair (zeros with the
+    fallback off).  Returns (out, flags, trusted) as frame_interp_device, and
+    cut behind them where it was asked for.  Stream-ordered."""
     return _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel,
                                abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
-                               smoothness, finest=finest, projection=projection)
+                               smoothness, finest=finest, projection=projection,
+                               fallback=fallback, cut=cut)
 
 
 def _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median, rel, abs, out,
                         out_dtype, flags, trusted, workspace, stream, prefilter, smoothness,
-                        init=None, finest=0, projection=0):
+                        init=None, finest=0, projection=0, fallback=None, cut=None):
     """flow_interp_device, from `init` (_init_entry) where given."""
     dims = _frame_pair(I0, I1)
     tm = _times_array(times)
@@ -1367,14 +1458,16 @@ def _flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, medi
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     size_fn, size_args = _pj_size(flow_interp_workspace_bytes, "hsflow_flow_interp", projection,
                                   levels, len(tm))
-    workspace = _workspace(workspace, I0.device, size_fn, *dims, *size_args, prefilter=prefilter)
-    name, lv, start, pj = _pj_entry("hsflow_flow_interp", init, dims, finest, projection)
+    workspace = _workspace(workspace, I0.device, size_fn, *dims, *size_args, prefilter=prefilter,
+                           fallback=fallback)
+    name, lv, start, pj, cut, cut_arg, fb = _fb_entry("hsflow_flow_interp", init, dims, finest,
+                                                      projection, fallback, cut, I0.device)
     _device_call(name, I0.device, stream, I0.data_ptr(), I1.data_ptr(),
                  _tensor_dtype(I0), *dims,
                  *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel),
                  float(abs), tm, len(tm), *pj, out.data_ptr(), _out_code(out), _ptr(flags),
-                 _ptr(trusted), pf, sm, *start, *_ws_args(workspace))
-    return out, flags, trusted
+                 _ptr(trusted), *cut_arg, pf, sm, *start, *fb, *_ws_args(workspace))
+    return (out, flags, trusted) if cut is None else (out, flags, trusted, cut)
 
 
 def _check_bgr(t, name):
@@ -1441,7 +1534,8 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
                            alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                            abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                            trusted=None, workspace=None, stream=None, prefilter=None,
-                           smoothness=None, finest: int = 0, projection: int = 0):
+                           smoothness=None, finest: int = 0, projection: int = 0, fallback=None,
+                           cut=None):
     """bgr_to_gray_device of both frames, flow_bidir_device(median=...) on the
     grey planes, then frame_interp_bgr_device with both masks: one call, the
     same bits (hsflow_flow_interp_bgr_device in include/hsflow.h).
@@ -1451,16 +1545,19 @@ def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: i
     workspace).  finest as in flow_interp_device
     (hsflow_flow_interp_bgr_lv_device); projection likewise, the cells made
     from the grey planes (hsflow_flow_interp_bgr_pj_device;
-    projection.flow_interp_bgr_workspace_bytes).  Returns (out, flags, trusted)
-    as frame_interp_bgr_device.  Stream-ordered."""
+    projection.flow_interp_bgr_workspace_bytes); fallback and cut likewise
+    (hsflow_flow_interp_bgr_fb_device).  Returns (out, flags, trusted) as
+    frame_interp_bgr_device, and cut where asked for.  Stream-ordered."""
     return _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median,
                                    rel, abs, out, out_dtype, flags, trusted, workspace, stream,
-                                   prefilter, smoothness, finest=finest, projection=projection)
+                                   prefilter, smoothness, finest=finest, projection=projection,
+                                   fallback=fallback, cut=cut)
 
 
 def _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha, median, rel,
                             abs, out, out_dtype, flags, trusted, workspace, stream, prefilter,
-                            smoothness, init=None, finest=0, projection=0):
+                            smoothness, init=None, finest=0, projection=0, fallback=None,
+                            cut=None):
     """flow_interp_bgr_device, from `init` (_init_entry) where given."""
     dims = _bgr_pair(bgr0, bgr1)
     tm = _times_array(times)
@@ -1468,13 +1565,15 @@ def _flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alp
     pf, sm = _option(Prefilter, prefilter)[1], _option(Smoothness, smoothness)[1]
     size_fn, size_args = _pj_size(flow_interp_bgr_workspace_bytes, "hsflow_flow_interp_bgr",
                                   projection, levels, len(tm))
-    workspace = _workspace(workspace, bgr0.device, size_fn, *dims, *size_args, prefilter=prefilter)
-    name, lv, start, pj = _pj_entry("hsflow_flow_interp_bgr", init, dims, finest, projection)
+    workspace = _workspace(workspace, bgr0.device, size_fn, *dims, *size_args, prefilter=prefilter,
+                           fallback=fallback)
+    name, lv, start, pj, cut, cut_arg, fb = _fb_entry("hsflow_flow_interp_bgr", init, dims, finest,
+                                                      projection, fallback, cut, bgr0.device)
     _device_call(name, bgr0.device, stream, bgr0.data_ptr(), bgr1.data_ptr(), *dims,
                  *_solve_args(levels, warps, median, window, iters, alpha, *lv), float(rel),
                  float(abs), tm, len(tm), *pj, out.data_ptr(), _out_code(out), _ptr(flags),
-                 _ptr(trusted), pf, sm, *start, *_ws_args(workspace))
-    return out, flags, trusted
+                 _ptr(trusted), *cut_arg, pf, sm, *start, *fb, *_ws_args(workspace))
+    return (out, flags, trusted) if cut is None else (out, flags, trusted, cut)
 
 
 def prefilter_planes_bytes(rows: int, cols: int, batch: int = 1) -> int:

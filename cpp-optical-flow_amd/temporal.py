@@ -102,26 +102,31 @@ def flow_interp_device(I0, I1, times, levels: int, warps: int, window: int, iter
                        alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                        abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                        trusted=None, workspace=None, stream=None, prefilter=None,
-                       smoothness=None, finest: int = 0, projection: int = 0, init=None):
+                       smoothness=None, finest: int = 0, projection: int = 0, fallback=None,
+                       cut=None, init=None):
     """hsflow.flow_interp_device with its solve started from `init`
-    (hsflow_flow_interp_init_device); finest and projection as there."""
+    (hsflow_flow_interp_init_device); finest, projection, fallback and cut as
+    there."""
     return hsflow._flow_interp_device(I0, I1, times, levels, warps, window, iters, alpha, median,
                                       rel, abs, out, out_dtype, flags, trusted, workspace, stream,
                                       prefilter, smoothness, init=init, finest=finest,
-                                      projection=projection)
+                                      projection=projection, fallback=fallback, cut=cut)
 
 
 def flow_interp_bgr_device(bgr0, bgr1, times, levels: int, warps: int, window: int, iters: int,
                            alpha: float, median: int = 0, rel: float = CONSISTENCY_REL,
                            abs: float = CONSISTENCY_ABS, out=None, out_dtype=None, flags=None,
                            trusted=None, workspace=None, stream=None, prefilter=None,
-                           smoothness=None, finest: int = 0, projection: int = 0, init=None):
+                           smoothness=None, finest: int = 0, projection: int = 0, fallback=None,
+                           cut=None, init=None):
     """hsflow.flow_interp_bgr_device with its solve started from `init`
-    (hsflow_flow_interp_bgr_init_device); finest and projection as there."""
+    (hsflow_flow_interp_bgr_init_device); finest, projection, fallback and cut as
+    there."""
     return hsflow._flow_interp_bgr_device(bgr0, bgr1, times, levels, warps, window, iters, alpha,
                                           median, rel, abs, out, out_dtype, flags, trusted,
                                           workspace, stream, prefilter, smoothness, init=init,
-                                          finest=finest, projection=projection)
+                                          finest=finest, projection=projection,
+                                          fallback=fallback, cut=cut)
 
 
 # ------------------------------------------------------- sequence mode (host)

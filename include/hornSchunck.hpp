@@ -96,6 +96,22 @@ class hornSchunck {
         return projection;
     }
 
+    // The fallback for a failed pair of the interpolating calls made through
+    // this object (hsflow.h, hsflow_ctx_set_fallback); nullptr, the default:
+    // none.  lastCut: 1 where the last such call found a cut, 0 where the pair
+    // passed, -1 where there was none.
+    void setFallback(const hsflow_fallback *fb) { guarded([&] { impl_.setFallback(fb); }); }
+    hsflow::Fallback fallback() {
+        hsflow::Fallback fb(HSFLOW_FALLBACK_OFF, 0.0f);
+        guarded([&] { fb = impl_.fallback(); });
+        return fb;
+    }
+    int lastCut() {
+        int cut = -1;
+        guarded([&] { cut = impl_.lastCut(); });
+        return cut;
+    }
+
   private:
     hsflow::HornSchunck impl_;
 

@@ -877,8 +877,10 @@ int hsflow_ctx_smoothness(const hsflow_ctx *ctx, hsflow_smoothness *sm);
  * with the pyramid kept, a warm solve beats the cold solve of the same
  * schedule.  A warm start WITHOUT the pyramid (levels = 1) cannot repair a
  * prediction that is off by more than about a pixel.  So: keep `levels` and
- * halve `warps` when motion may change; use levels = 1 only for steady motion;
- * reset the prediction at a scene cut. */
+ * halve `warps` when motion may change; use levels = 1 only for steady motion.
+ * A scene cut makes the prediction worthless: with the fallback on
+ * (hsflow_ctx_set_fallback) the interpolating calls find the cut themselves
+ * and drop the prediction; the other calls' caller resets it. */
 #define HSFLOW_HAS_TEMPORAL 1
 
 /* The start of a solve: dense f32 planes [batch][rows][cols], solver units,
@@ -973,8 +975,11 @@ int hsflow_flow_interp_bgr_init_device(const uint8_t *bgr0, const uint8_t *bgr1,
  * stored prediction is dropped by a failed call, a call of another size,
  * hsflow_ctx_temporal_reset and hsflow_ctx_set_temporal.  Feed the calls the
  * consecutive pairs of one clip, in order.  Keep `levels` and halve `warps`
- * when motion may change; use levels = 1 only for steady motion; call
- * hsflow_ctx_temporal_reset at a scene cut.  hsflow_flow_warped* has no
+ * when motion may change; use levels = 1 only for steady motion.  At a scene
+ * cut hsflow_flow_interp and hsflow_flow_interp_bgr drop the prediction
+ * themselves where the context's fallback is on (hsflow_ctx_set_fallback;
+ * hsflow_ctx_last_cut tells); otherwise call hsflow_ctx_temporal_reset
+ * there.  hsflow_flow_warped* has no
  * backward flow and ignores the mode, as do hsflow_flow, hsflow_flow_bgr,
  * hsflow_flow_pyramid and hsflow_flow_multi.  hsflow_ctx_temporal returns the
  * mode (0 or 1; HSFLOW_ERR_ARG for a null context). */
@@ -1190,6 +1195,128 @@ int hsflow_flow_interp_bgr_pj_device(const uint8_t *bgr0, const uint8_t *bgr1, i
  * for a null context). */
 int hsflow_ctx_set_projection(hsflow_ctx *ctx, int projection);
 int hsflow_ctx_projection(const hsflow_ctx *ctx);
+
+/* ---- fallback for a failed pair: a source frame where the flows are worthless --
+ * A scene cut, a fade the prefilter is not set up for, a motion beyond the
+ * pyramid's reach: the flows of such a pair mean nothing, and the frames
+ * hsflow_frame_interp_device makes from them are morphs of two unrelated
+ * pictures.  The forward-backward check tells such a pair from a good one: the
+ * share of HSFLOW_CONSISTENT pixels, both directions together, is at least 0.55
+ * for related pairs within reach and at most 0.32 for unrelated ones (DESIGN.md,
+ * "Fallback for a failed pair").  The fallback takes that verdict per pair on
+ * the device, with no host synchronisation, and replaces a failed pair's frames
+ * by a source frame or a cross-fade.  A pair that is a cut in half the picture
+ * lands at 0.43 - 0.54: no threshold decides that case.
+ *
+ * Threshold: min_share, finite and in [0, 1] (else HSFLOW_ERR_ARG).
+ *   m = hsflow_fallback_min_consistent(rows, cols, min_share): the smallest
+ *       integer >= (double)min_share * 2.0 * rows * cols, computed in double; 0
+ *       for a bad size.  min_share = 0 gives 0: no pair ever fails.
+ * Verdict of pair b, from the uint32[batch][3] counts of
+ * hsflow_flow_consistency_device in both directions:
+ *   cut[b] = (uint64)counts_f[b][HSFLOW_CONSISTENT]
+ *            + counts_b[b][HSFLOW_CONSISTENT] < m
+ * an integer comparison, the same at every time.
+ * A pair with cut[b] == 1, at every time t of the call, with a, c the pixel of
+ * I0 and of I1 as hsflow_frame_interp_device reads them at zero flow (the
+ * element converted to f32; an f64 element rounded once):
+ *   HSFLOW_FALLBACK_NEAREST  out = t < 0.5f ? a : c
+ *   HSFLOW_FALLBACK_BLEND    out = t == 0 ? a : t == 1 ? c : fma(1 - t, a, t c)
+ *                            (a select; 1 - t and t c are rounded to f32, the
+ *                            multiply-add is fused: the interpolation's own
+ *                            blend with wt = t as the library computes it)
+ *   u8 output: floorf(x + 0.5f) clamped to 0..255, NaN -> 0, as the interpolation
+ *   BGR: the same per channel
+ *   flags = HSFLOW_INTERP_FALLBACK at every pixel, replacing what was there (the
+ *           flags of a meaningless flow say nothing; flags == 0 stays the mark
+ *           of a trusted pixel)
+ *   trusted[b][t] = 0
+ * A pair with cut[b] == 0: nothing of its out, flags or trusted is written.
+ * So for finite frames the BLEND result equals hsflow_frame_interp_device on
+ * four all-zero flow planes with NULL masks bit for bit, and the NEAREST result
+ * equals that call at t = 0 or t = 1. */
+#define HSFLOW_HAS_FALLBACK 1
+#define HSFLOW_FALLBACK_OFF 0
+#define HSFLOW_FALLBACK_NEAREST 1   /* t < 0.5 -> I0, else I1 */
+#define HSFLOW_FALLBACK_BLEND 2     /* (1 - t) I0 + t I1 */
+#define HSFLOW_FALLBACK_MIN_SHARE 0.4f
+#define HSFLOW_INTERP_FALLBACK 32   /* flags: the pixel is the fallback's */
+typedef struct hsflow_fallback { int mode; float min_share; } hsflow_fallback;
+
+/* size_t: 64 bits on every platform the library builds for, so the comparison
+ * above is made in 64 bits whatever the counts hold */
+size_t hsflow_fallback_min_consistent(int rows, int cols, float min_share);
+
+/* KF: the verdict of every pair and the replacement of the failed ones, over
+ * the outputs of hsflow_frame_interp_device (or its _bgr_, _proj_ forms) for the
+ * same frames, times and dtype_out: out [batch][nt] planes (U8 or F32;
+ * required), flags [batch][nt] planes of u8, trusted uint32[batch][nt], cut
+ * uint8[batch]; flags, trusted and cut may each be NULL, and every element of
+ * a given cut is written.  counts_f, counts_b: device arrays, required.  fb:
+ * required, mode NEAREST or BLEND (NULL or mode 0 is HSFLOW_ERR_ARG here).
+ * `times`: host array, read at call time, each in [0, 1], nt in
+ * 1 .. HSFLOW_MAX_TIMES.  Planes need element alignment only.  The outputs
+ * must be disjoint from the inputs and from each other.  All arguments are
+ * checked before any device work.  One launch for all times and pairs; the
+ * blocks of a pair that passes read its two counts and leave.  Stream-ordered,
+ * no workspace, never allocates or synchronises, capturable. */
+int hsflow_frame_fallback_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, const uint32_t *counts_f, const uint32_t *counts_b,
+                                 const hsflow_fallback *fb, const float *times, int nt, void *out,
+                                 int dtype_out, uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                 void *stream);
+int hsflow_frame_fallback_bgr_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, const uint32_t *counts_f,
+                                     const uint32_t *counts_b, const hsflow_fallback *fb,
+                                     const float *times, int nt, void *out, int dtype_out,
+                                     uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                     void *stream);
+
+/* The fused calls: the *_pj_device forms with `const hsflow_fallback *fb` after
+ * `init` and `uint8_t *cut` (uint8[batch], may be NULL) after `trusted`; the
+ * *_pj_device calls are the fb = NULL case of these.  fb == NULL or mode 0
+ * makes exactly the *_pj_device launches and needs that call's workspace only;
+ * a given cut is then zeroed stream-ordered.  With the fallback on both
+ * consistency checks always launch, their counts go into the workspace (the
+ * masks are still written only when flags or trusted is asked for), and
+ * hsflow_frame_fallback*_device follows the interpolation on the stream: the
+ * result is bit for bit the public pieces one after the other.  The workspace
+ * is then the *_pj_device call's for the same projection plus
+ * hsflow_fallback_counts_bytes(batch) -- two 256-byte-aligned uint32[batch][3]
+ * arrays; 0 for a bad batch -- with a prefilter's planes behind it, as ever.
+ * A bad mode or min_share is HSFLOW_ERR_ARG before any device work. */
+size_t hsflow_fallback_counts_bytes(int batch);
+int hsflow_flow_interp_fb_device(const void *I0, const void *I1, int dtype_in, int rows, int cols,
+                                 int batch, int levels, int finest, int warps, int median,
+                                 int window, int iters, float alpha, float rel, float abs_thr,
+                                 const float *times, int nt, int projection, void *out,
+                                 int dtype_out, uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                 const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                 const hsflow_flow_init *init, const hsflow_fallback *fb,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int hsflow_flow_interp_bgr_fb_device(const uint8_t *bgr0, const uint8_t *bgr1, int rows, int cols,
+                                     int batch, int levels, int finest, int warps, int median,
+                                     int window, int iters, float alpha, float rel,
+                                     float abs_thr, const float *times, int nt, int projection,
+                                     void *out, int dtype_out, uint8_t *flags, uint32_t *trusted,
+                                     uint8_t *cut, const hsflow_prefilter *pf,
+                                     const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                     const hsflow_fallback *fb, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
+/* The context's fallback: hsflow_flow_interp and hsflow_flow_interp_bgr honour
+ * it and then equal their *_fb_device form bit for bit; the verdict comes down
+ * with `trusted` on the stream the call drains anyway.  NULL or mode 0: off, the
+ * default.  A bad mode or min_share is HSFLOW_ERR_ARG and leaves the old setting
+ * in place.  hsflow_ctx_fallback reads it back.  hsflow_ctx_last_cut: the
+ * verdict of the last such call on this context, 0 or 1; -1 where there was
+ * none, it failed, or the fallback was off (and for a null context).  In
+ * sequence mode a call whose verdict is a cut drops the stored prediction, so
+ * the next call is the cold call, bit for bit; with the fallback off sequence
+ * mode is what it was. */
+int hsflow_ctx_set_fallback(hsflow_ctx *ctx, const hsflow_fallback *fb);
+int hsflow_ctx_fallback(const hsflow_ctx *ctx, hsflow_fallback *fb);
+int hsflow_ctx_last_cut(const hsflow_ctx *ctx);
 
 /* ---- host utilities on the path to the hot loop ------------------------ */
 

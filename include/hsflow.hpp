@@ -62,6 +62,15 @@ struct BgrView {
     size_t step = 0;
 };
 
+// What the interpolating calls do with a pair whose flows fail the
+// forward-backward check (hsflow.h, "fallback for a failed pair"): mode
+// HSFLOW_FALLBACK_NEAREST or HSFLOW_FALLBACK_BLEND, and the share of consistent
+// pixels below which a pair fails.
+struct Fallback : hsflow_fallback {
+    Fallback(int mode = HSFLOW_FALLBACK_NEAREST, float min_share = HSFLOW_FALLBACK_MIN_SHARE)
+        : hsflow_fallback{mode, min_share} {}
+};
+
 // RAII device context (device, stream, cached buffers).
 class Context {
   public:
@@ -129,6 +138,18 @@ class Context {
         if (rc < 0) check(rc);
         return rc;
     }
+    // The fallback of the interpolating calls (hsflow.h, hsflow_ctx_set_fallback):
+    // a pair whose flows fail the check -- a scene cut, a motion beyond the
+    // pyramid's reach -- comes back as a source frame or a cross-fade; nullptr
+    // or mode 0 = off (default).  lastCut: the last such call's verdict, 1 for
+    // a cut, 0 for a pair that passed, -1 where there was none.
+    void setFallback(const hsflow_fallback *fb) { check(hsflow_ctx_set_fallback(ctx_, fb)); }
+    Fallback fallback() const {
+        Fallback fb(HSFLOW_FALLBACK_OFF, 0.0f);
+        check(hsflow_ctx_fallback(ctx_, &fb));
+        return fb;
+    }
+    int lastCut() const { return hsflow_ctx_last_cut(ctx_); }
 
   private:
     hsflow_ctx *ctx_ = nullptr;
@@ -215,6 +236,11 @@ class HornSchunck {
     // (Context::setProjection)
     void setProjection(int projection) { ctx().setProjection(projection); }
     int projection() { return ctx().projection(); }
+    // the fallback for a failed pair of getFrameInterp and getFrameInterpBgr
+    // (Context::setFallback), and the last call's verdict
+    void setFallback(const hsflow_fallback *fb) { ctx().setFallback(fb); }
+    Fallback fallback() { return ctx().fallback(); }
+    int lastCut() { return ctx().lastCut(); }
     void getFlowWarped(const ImageView &imagePrev, const ImageView &imageNext, int levels,
                        int warps, std::vector<double> &u, std::vector<double> &v,
                        int median = 0, const hsflow_prefilter *prefilter = nullptr) {
