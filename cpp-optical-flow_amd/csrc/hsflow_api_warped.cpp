@@ -2,7 +2,9 @@
 // the warped coarse-to-fine solve, the median and the smoothness weights
 // between its warps, the bidirectional solve with its consistency check, the
 // prefilter in front of them, and the frame warp and frame interpolation
-// (grey and BGR) behind them, with the fallback for a pair whose flows fail.
+// (grey and BGR) behind them, with the fallback for a pair whose flows fail,
+// and the same interpolation for YUV 4:2:0 frames (the grey call on the luma,
+// KIY on the chroma).
 //
 // Every solve of the family is described by one SolveSpec, filled once in the
 // extern "C" entry point and passed down by reference; check_solve checks it,
@@ -1096,6 +1098,187 @@ SolveSpec host_spec(const hsflow_ctx *ctx, int rows, int cols, int levels, int w
                      ctx ? &ctx->fb : nullptr};
 }
 
+// ---- YUV 4:2:0 (KIY) -------------------------------------------------------------
+// the luma's size, even each way, and the chroma's layout
+int check_yuv_shape(hsflow_ctx *ctx, int layout, int rows, int cols, int batch) {
+    const int rc = check_sizes(ctx, rows, cols, batch);
+    if (rc) return rc;
+    if ((rows | cols) & 1)
+        return fail(ctx, HSFLOW_ERR_ARG, "YUV 4:2:0 needs even rows and cols, not %dx%d", rows,
+                    cols);
+    if (layout != HSFLOW_YUV_I420 && layout != HSFLOW_YUV_NV12)
+        return fail(ctx, HSFLOW_ERR_ARG, "YUV layout %d is not 1 (I420) or 2 (NV12)", layout);
+    return HSFLOW_OK;
+}
+
+// the chroma of a call: both frames', and the nt frames (times: host) it writes
+struct ChromaIO {
+    const uint8_t *c0, *c1;
+    int layout;
+    const float *times;
+    int nt;
+    void *out;
+    int dtype_out;
+};
+
+// bytes of the chroma of `batch` frames, and of the output's
+size_t chroma_bytes(int rows, int cols, int batch) { return (size_t)rows * cols * batch / 2; }
+size_t chroma_out_bytes(const ChromaIO &C, int rows, int cols, int batch) {
+    return chroma_bytes(rows, cols, batch) * C.nt * elem_size(C.dtype_out);
+}
+
+// KIY on checked arguments: one launch.  fb: null for no fallback
+int chroma_interp_run(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, int batch,
+                      const FlowsIn &W, const uint32_t *counts_f, const uint32_t *counts_b,
+                      const hsflow_fallback *fb, hipStream_t s) {
+    const bool on = fb_on(fb);
+    hipError_t e = hsflow::launch_chroma_interp(
+        C.c0, C.c1, C.layout, rows, cols, batch, W.uf, W.vf, W.ub, W.vb, on ? counts_f : nullptr,
+        on ? counts_b : nullptr, on ? min_consistent(rows, cols, fb->min_share) : 0,
+        on ? fb->mode : 0, C.times, C.nt, C.out, C.dtype_out == HSFLOW_U8, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "chroma interpolation launch");
+    return HSFLOW_OK;
+}
+
+// hsflow_chroma_interp_device
+int chroma_interp_impl(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, int batch,
+                       const FlowsIn &W, const uint32_t *counts_f, const uint32_t *counts_b,
+                       const hsflow_fallback *fb, hipStream_t s) {
+    int rc = check_yuv_shape(ctx, C.layout, rows, cols, batch);
+    if (rc) return rc;
+    if (!C.c0 || !C.c1 || !W.uf || !W.vf || !W.ub || !W.vb || !C.out) return null_pointer(ctx);
+    if ((rc = check_interp_args(ctx, C.times, C.nt, C.dtype_out, false))) return rc;
+    const bool on = fb_on(fb);
+    if (on) {
+        if ((rc = check_fallback(ctx, fb))) return rc;
+        if (!counts_f || !counts_b) return null_pointer(ctx);
+    }
+    const size_t n = (size_t)rows * cols * batch, cb = chroma_bytes(rows, cols, batch);
+    const size_t kb = (size_t)batch * 3 * 4;
+    const ByteRange in[8] = {{C.c0, cb},    {C.c1, cb},    {W.uf, n * 4},
+                             {W.vf, n * 4}, {W.ub, n * 4}, {W.vb, n * 4},
+                             {on ? counts_f : nullptr, kb}, {on ? counts_b : nullptr, kb}};
+    const ByteRange out{C.out, chroma_out_bytes(C, rows, cols, batch)};
+    if (!outputs_disjoint(in, 8, &out, 1))
+        return fail(ctx, HSFLOW_ERR_ARG, "chroma output overlaps the inputs");
+    return chroma_interp_run(ctx, C, rows, cols, batch, W, counts_f, counts_b, fb, s);
+}
+
+// hsflow_flow_interp_yuv_device: what the chroma adds to the grey call's checks
+// (first, so that nothing has run when one fails), flow_interp_impl on the luma
+// planes, then KIY on the flows and counts that call left in the workspace
+int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma, const ChromaIO &C,
+                         float rel, float abs_thr, const InterpOut &Y, void *ws, size_t ws_bytes,
+                         hipStream_t s) {
+    int rc = check_yuv_shape(ctx, C.layout, S.rows, S.cols, S.batch);
+    if (rc || (rc = check_levels(ctx, S.levels))) return rc;
+    if (!luma.I0 || !luma.I1 || !C.c0 || !C.c1 || !Y.out || !C.out || !ws)
+        return null_pointer(ctx);
+    if ((rc = check_interp_args(ctx, Y.times, Y.nt, Y.dtype_out, false))) return rc;
+    const bool fallback = fb_on(S.fb);
+    if (fallback && (rc = check_fallback(ctx, S.fb))) return rc;
+    const InterpLayout L = interp_layout(S.rows, S.cols, S.batch, S.levels, 1, 0, fallback);
+    const size_t need = L.bytes + (pf_on(S.pf) ? pf_planes_bytes(S.rows, S.cols, S.batch) : 0);
+    const size_t n = (size_t)S.rows * S.cols * S.batch, cb = chroma_bytes(S.rows, S.cols, S.batch);
+    const ByteRange ins[5] = {{luma.I0, n}, {luma.I1, n}, {C.c0, cb}, {C.c1, cb}, {ws, need}};
+    ByteRange outs[5];
+    interp_out_ranges(Y, n, S.batch, 1, outs);
+    outs[4] = {C.out, chroma_out_bytes(C, S.rows, S.cols, S.batch)};
+    if (!outputs_disjoint(ins, 5, outs, 5))
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "interpolation outputs overlap the frames, the workspace or each other");
+    if (S.init) {  // the planes a solve starts from, against the chroma output
+        const float *planes[4] = {S.init->uf, S.init->vf, S.init->ub, S.init->vb};
+        for (const float *p : planes)
+            if (bytes_overlap(p, n * 4, outs[4].p, outs[4].n))
+                return fail(ctx, HSFLOW_ERR_ARG, "init flow overlaps an output");
+    }
+    if ((rc = flow_interp_impl(ctx, S, 1, luma, rel, abs_thr, Y, ws, ws_bytes, s))) return rc;
+    char *base = (char *)ws;
+    const FlowsIn W{(const float *)(base + L.flow[0]), (const float *)(base + L.flow[1]),
+                    (const float *)(base + L.flow[2]), (const float *)(base + L.flow[3]),
+                    nullptr, nullptr, nullptr};
+    return chroma_interp_run(ctx, C, S.rows, S.cols, S.batch, W,
+                             fallback ? (const uint32_t *)(base + L.counts[0]) : nullptr,
+                             fallback ? (const uint32_t *)(base + L.counts[1]) : nullptr, S.fb, s);
+}
+
+// hsflow_flow_interp_yuv: flow_interp_host for packed 4:2:0 frames.  Each frame
+// goes up as it is, rows * 3 / 2 rows of cols bytes; the luma and the chroma of
+// a time come down into its packed host frame.
+int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *f0,
+                         const uint8_t *f1, int layout, float rel, float abs_thr,
+                         const float *times, int nt, void *const *out, int dtype_out,
+                         uint8_t *const *flags, uint32_t *trusted) {
+    SolveSpec S = spec;
+    const int rows = S.rows, cols = S.cols;
+    if (ctx) ctx->last_cut = -1;
+    hsflow_flow_init init;
+    if (ctx && take_prediction(ctx, rows, cols, &init)) S.init = &init;
+    int rc = check_interp_args(ctx, times, nt, dtype_out, false);
+    if (rc) return rc;
+    if (!f0 || !f1) return fail(ctx, HSFLOW_ERR_ARG, "null image");
+    if ((rc = check_yuv_shape(ctx, layout, rows, cols, 1))) return rc;
+    if (!out) return fail(ctx, HSFLOW_ERR_ARG, "null output");
+    for (int k = 0; k < nt; ++k)
+        if (!out[k] || (flags && !flags[k]))
+            return fail(ctx, HSFLOW_ERR_ARG, "null output plane %d", k);
+    if ((rc = check_levels(ctx, S.levels)) || (rc = check_finest(ctx, S)) ||
+        (rc = check_iteration_args(ctx, S)) || (rc = check_thresholds(ctx, rel, abs_thr)))
+        return rc;
+    if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
+    if (S.projection)
+        return fail(ctx, HSFLOW_ERR_ARG,
+                    "the flow projection is not supported on YUV chroma: set the context's "
+                    "projection to 0");
+    const size_t n = (size_t)rows * cols, es = elem_size(dtype_out);
+    // d_out: the nt luma planes, the nt chroma frames, the nt flag planes, trusted
+    const size_t yb = align_up(n * nt * es), cb = align_up(n / 2 * nt * es), flb = align_up(n * nt);
+    const bool fb = fb_on(S.fb);
+    const size_t wsb = interp_layout(rows, cols, 1, S.levels, 1, 0, fb).bytes +
+                       (pf_on(S.pf) ? pf_planes_bytes(rows, cols, 1) : 0);
+    char *in0, *in1;
+    rc = stage_pair(ctx, f0, f1, 1, rows / 2 * 3, cols, (size_t)cols, (size_t)cols,
+                    yb + cb + flb + kAlign, wsb, &in0, &in1);
+    if (rc || (rc = grow_prediction(ctx, rows, cols))) return rc;
+    char *dy = (char *)ctx->d_out, *dc = dy + yb;
+    uint8_t *dfl = (uint8_t *)(dc + cb);
+    uint32_t *dtr = (uint32_t *)(dc + cb + flb);
+    uint8_t *dcut = (uint8_t *)(dtr + HSFLOW_MAX_TIMES);  // within the kAlign bytes
+    const InterpOut Y{times, nt, dy, dtype_out, flags ? dfl : nullptr, trusted ? dtr : nullptr,
+                      fb ? dcut : nullptr};
+    const ChromaIO C{(const uint8_t *)in0 + n, (const uint8_t *)in1 + n, layout, times, nt, dc,
+                     dtype_out};
+    rc = flow_interp_yuv_impl(ctx, S, Frames{in0, in1, HSFLOW_U8}, C, rel, abs_thr, Y, ctx->d_ws,
+                              ctx->d_ws_bytes, ctx->stream);
+    if (rc) return rc;
+    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, 1, 0, fb);
+    rc = predict_run(ctx, (const float *)((char *)ctx->d_ws + L.flow[2]),
+                     (const float *)((char *)ctx->d_ws + L.flow[3]), rows, cols);
+    if (rc) return rc;
+    if (flags)
+        for (int k = 0; k < nt; ++k)
+            HIP_TRY(ctx, hipMemcpyAsync(flags[k], dfl + k * n, n, hipMemcpyDeviceToHost,
+                                        ctx->stream));
+    if (trusted)
+        HIP_TRY(ctx, hipMemcpyAsync(trusted, dtr, (size_t)nt * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (fb)
+        HIP_TRY(ctx, hipMemcpyAsync(&ctx->cut_byte, dcut, 1, hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < nt; ++k) {
+        char *dst = (char *)out[k];
+        HIP_TRY(ctx, hipMemcpyAsync(dst, dy + k * n * es, n * es, hipMemcpyDeviceToHost,
+                                    ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dst + n * es, dc + k * (n / 2) * es, n / 2 * es,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // the stream has drained: the verdict is here, and a cut keeps no prediction
+    if (!fb) return keep_prediction(ctx, HSFLOW_OK);
+    ctx->last_cut = ctx->cut_byte ? 1 : 0;
+    return ctx->last_cut ? HSFLOW_OK : keep_prediction(ctx, HSFLOW_OK);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1889,5 +2072,57 @@ int hsflow_ctx_temporal_reset(hsflow_ctx *ctx) {
     ctx->pred_valid = false;
     return HSFLOW_OK;
 }
+
+int hsflow_chroma_interp_device(const uint8_t *c0, const uint8_t *c1, int layout, int rows,
+                                int cols, int batch, const float *uf, const float *vf,
+                                const float *ub, const float *vb, const uint32_t *counts_f,
+                                const uint32_t *counts_b, const hsflow_fallback *fb,
+                                const float *times, int nt, void *out_c, int dtype_out,
+                                void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return chroma_interp_impl(nullptr, ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rows,
+                              cols, batch, FlowsIn{uf, vf, ub, vb, nullptr, nullptr, nullptr},
+                              counts_f, counts_b, fb, (hipStream_t)stream);
+}
+
+size_t hsflow_flow_interp_yuv_workspace_bytes(int rows, int cols, int batch, int levels,
+                                              int fallback) {
+    if (!sizes_ok(rows, cols, batch) || (rows | cols) & 1 || levels < 1 ||
+        levels > HSFLOW_MAX_LEVELS)
+        return 0;
+    return interp_layout(rows, cols, batch, levels, 1, 0, fallback != 0).bytes;
+}
+
+int hsflow_flow_interp_yuv_device(const uint8_t *y0, const uint8_t *c0, const uint8_t *y1,
+                                  const uint8_t *c1, int layout, int rows, int cols, int batch,
+                                  int levels, int finest, int warps, int median, int window,
+                                  int iters, float alpha, float rel, float abs_thr,
+                                  const float *times, int nt, void *out_y, void *out_c,
+                                  int dtype_out, uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                  const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                  const hsflow_flow_init *init, const hsflow_fallback *fb,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,  cols,  batch, levels, finest, warps, median, window,
+                      iters, alpha, pf,    sm,     init,   0,     fb};
+    return flow_interp_yuv_impl(nullptr, S, Frames{y0, y1, HSFLOW_U8},
+                                ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rel, abs_thr,
+                                InterpOut{times, nt, out_y, dtype_out, flags, trusted, cut},
+                                workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_interp_yuv(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1, int layout,
+                           int rows, int cols, int levels, int warps, int median, int window,
+                           int iters, double alpha, float rel, float abs_thr, const float *times,
+                           int nt, void *const *out, int dtype_out, uint8_t *const *flags,
+                           uint32_t *trusted) {
+    const SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
+    return flow_interp_yuv_host(ctx, S, f0, f1, layout, rel, abs_thr, times, nt, out, dtype_out,
+                                flags, trusted);
+}
+
+int hsflow_chroma_interp_blocks_per_cu(void) { return hsflow::chroma_blocks_per_cu(); }
+
+int hsflow_set_chroma_nv12_loads(int wide) { return hsflow::set_chroma_nv12_wide_loads(wide); }
 
 }  // extern "C"

@@ -2,7 +2,9 @@
 // written once over a frame policy: KI / KIP (hsflow_sampler.h, launched from
 // hsflow_interp.hip and hsflow_interp_bgr.hip) and KF (hsflow_fallback.hip).
 // GreyFrame<T>: one element of T per pixel; BgrFrame<Wide>: three interleaved
-// bytes, with KRC's tap loads and the quad store of a u8 BGR plane.  Device
+// bytes, with KRC's tap loads and the quad store of a u8 BGR plane;
+// ChromaFrame<Layout, Wide>: the U and V samples of a 4:2:0 frame, for KIY
+// (hsflow_yuv.hip), which has a kernel of its own over KI's pieces.  Device
 // code only; every including file gets its own copy (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -128,6 +130,97 @@ struct BgrFrame {
                                                     bool whole, bool valid, const Bgr &o, int lane) {
         store_quad_bgr_u8((uint8_t *)out + (obase + (size_t)q0) * 3, whole, valid, pack_u8(o),
                           lane);
+    }
+};
+
+// ---- KIY: hs_chroma_interp_kernel on the chroma of a 4:2:0 frame
+// (hsflow_yuv.hip).  A pair's chroma is 2 * plane bytes, plane = rc * cc
+// samples of U and of V: I420 [2][rc][cc], U then V; NV12 [rc][cc][2].  An
+// output frame has the same layout in u8 or f32.  One sample of both channels
+// is a Pixel<2>, U in c[0]; the taps are those of one chroma plane.
+constexpr int kYuvI420 = 1, kYuvNv12 = 2;  // HSFLOW_YUV_I420, HSFLOW_YUV_NV12
+using Uv = Pixel<2>;
+
+// one f32 sample of both channels: an 8-byte store (the plane is 4-byte aligned)
+struct alignas(4) Float2 {
+    float c[2];
+};
+
+// Wide (NV12 only): a row's two taps as one unaligned dword where xb == xa + 1
+template <int Layout, bool Wide>
+struct ChromaFrame {
+    using Px = Uv;
+    // 81 (NV12) to 90 (I420) VGPRs: five waves per SIMD, five blocks of four
+    // waves per CU, as KIC
+    static constexpr int kBlocksPerCu = 5;
+    // img: a pair's chroma; sample p of the plane as KI reads it at zero flow
+    static __device__ __forceinline__ Uv at(const uint8_t *__restrict__ img, int plane, int p) {
+        if constexpr (Layout == kYuvI420)
+            return Uv{{(float)img[p], (float)img[(size_t)plane + p]}};
+        else
+            return Uv{{(float)img[2 * (size_t)p], (float)img[2 * (size_t)p + 1]}};
+    }
+    static __device__ __forceinline__ void row_taps(const uint8_t *__restrict__ row, int xa,
+                                                    int xb, Uv &a, Uv &b) {
+        const uint8_t *pa = row + 2 * (size_t)xa;
+        if (Wide && xb != xa) {  // xb == xa + 1: four bytes of this row
+            const uint32_t w = load_u32_unaligned(pa);
+            a.c[0] = (float)(w & 0xFF), a.c[1] = (float)((w >> 8) & 0xFF);
+            b.c[0] = (float)((w >> 16) & 0xFF), b.c[1] = (float)(w >> 24);
+        } else {
+            const uint8_t *pb = row + 2 * (size_t)xb;
+            a.c[0] = (float)pa[0], a.c[1] = (float)pa[1];
+            b.c[0] = (float)pb[0], b.c[1] = (float)pb[1];
+        }
+    }
+    // KR's sample of the U and of the V plane (cc columns) at the taps `t`
+    static __device__ __forceinline__ Uv sample(const uint8_t *__restrict__ img, int plane, int cc,
+                                                const Taps &t) {
+        if constexpr (Layout == kYuvI420) {
+            return Uv{{(float)sample_plane(img, cc, t), (float)sample_plane(img + plane, cc, t)}};
+        } else {
+            Uv ta, tb, ba, bb, r;
+            row_taps(img + 2 * (size_t)t.ya * cc, t.xa, t.xb, ta, tb);
+            row_taps(img + 2 * (size_t)t.yb * cc, t.xa, t.xb, ba, bb);
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                r.c[c] = lerp_taps(ta.c[c], tb.c[c], ba.c[c], bb.c[c], t.fx, t.fy);
+            return r;
+        }
+    }
+    // sample pk of output frame `frame` (pair * nt + time) of the whole output
+    static __device__ __forceinline__ void store_f32(void *out, size_t frame, int plane, int pk,
+                                                     const Uv &o) {
+        if constexpr (Layout == kYuvI420) {
+            float *d = (float *)out + frame * 2 * plane;
+            d[pk] = o.c[0], d[(size_t)plane + pk] = o.c[1];
+        } else {
+            reinterpret_cast<Float2 *>(out)[frame * plane + pk] = Float2{{o.c[0], o.c[1]}};
+        }
+    }
+    // the same into a u8 output, through quads of lanes (q0: the quad's first
+    // sample, whole: its four lie in the plane): I420 as store_quad_u8 of each
+    // plane; NV12 the quad's eight bytes as two dwords where their address
+    // allows, else two bytes per valid lane.  Every lane of the wave calls.
+    static __device__ __forceinline__ void store_u8(void *out, size_t frame, int plane, int pk,
+                                                    int q0, bool whole, bool valid, const Uv &o,
+                                                    int lane) {
+        uint8_t *d = (uint8_t *)out + frame * 2 * plane;
+        if constexpr (Layout == kYuvI420) {
+            store_quad_u8(d, pk, q0, whole, valid, round_u8(o.c[0]), lane);
+            store_quad_u8(d + plane, pk, q0, whole, valid, round_u8(o.c[1]), lane);
+        } else {
+            const uint32_t uv = round_u8(o.c[0]) | round_u8(o.c[1]) << 8;
+            const uint32_t lo = quad_lane<0>(uv) | quad_lane<1>(uv) << 16;
+            const uint32_t hi = quad_lane<2>(uv) | quad_lane<3>(uv) << 16;
+            uint8_t *quad = d + 2 * (size_t)q0;
+            const int j = lane & 3;
+            if (whole && ((uintptr_t)quad & 3) == 0) {
+                if (j < 2) reinterpret_cast<uint32_t *>(quad)[j] = j == 0 ? lo : hi;
+            } else if (valid) {
+                quad[2 * j] = (uint8_t)uv, quad[2 * j + 1] = (uint8_t)(uv >> 8);
+            }
+        }
     }
 };
 

@@ -148,6 +148,24 @@ hipError_t launch_frame_fallback_bgr(const uint8_t *I0, const uint8_t *I1, int r
                                      const float *times, int nt, void *out, bool out_u8,
                                      uint8_t *flags, uint32_t *trusted, uint8_t *cut,
                                      hipStream_t s);
+// KIY (hsflow_yuv.hip): the chroma of the frames between two 4:2:0 frames, from
+// the full-resolution flows of the luma solve (rows, cols: the luma's, even):
+// KD's 2 x 2 reduction and KI on the rc x cc chroma grid for U and V in one
+// launch, for all times and pairs.  layout 1: I420 [batch][2][rc][cc], 2: NV12
+// [batch][rc][cc][2]; out [batch][nt] of that layout, u8 or f32.  With counts
+// (both or neither; null: no fallback) a pair that fails min_consistent gets
+// KF's value by `mode`.  `times` is read on the host at launch.
+hipError_t launch_chroma_interp(const uint8_t *c0, const uint8_t *c1, int layout, int rows,
+                                int cols, int batch, const float *uf, const float *vf,
+                                const float *ub, const float *vb, const uint32_t *counts_f,
+                                const uint32_t *counts_b, uint64_t min_consistent, int mode,
+                                const float *times, int nt, void *out, bool out_u8,
+                                hipStream_t s);
+// the cap of KIY's grid, in blocks per CU
+int chroma_blocks_per_cu();
+// how KIY fetches the two adjacent taps of an NV12 row: as four bytes (on == 0,
+// default) or as one unaligned dword; same bits.  Returns the previous setting.
+int set_chroma_nv12_wide_loads(int on);
 // how KRC and KIC fetch the two adjacent taps of a row: as six bytes (on == 0,
 // default) or as one unaligned dword and halfword; same bits.  Returns the
 // previous setting.

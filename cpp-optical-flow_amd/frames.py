@@ -24,6 +24,10 @@ consecutive pairs to frame_parallel.run_stream with the BGR->gray
 conversion on the GPU (hsflow_bgr_to_gray_device) and libhsflow as solver;
 `interpolate_sequence` yields a BGR source at a multiple of its frame rate
 (hsflow_flow_interp_bgr: the motion-compensated colour frames in between).
+A 4:2:0 clip stays 4:2:0: `Y4MVideo.read_yuv` hands out the packed I420 frame
+as it is stored, `write_y4m_420` writes such a stream, and
+`interpolate_sequence_yuv` is interpolate_sequence on packed frames
+(hsflow_flow_interp_yuv: the luma is the grey frame, no colour conversion).
 """
 from __future__ import annotations
 
@@ -145,6 +149,7 @@ class Y4MVideo:
                                  f"{'/'.join(sorted(self._CHROMA))} only)")
             sub = self._CHROMA[key]
             self.full_range = "XCOLORRANGE=FULL" in params
+            self.chroma = cs
             luma = self.rows * self.cols
             chroma = 0 if sub is None else 2 * (-(-self.cols // sub[0])) * (-(-self.rows // sub[1]))
             self.frame_bytes = luma + chroma
@@ -176,6 +181,17 @@ class Y4MVideo:
         g = (y.astype(np.int32) - 16) * 255 + 109          # round((Y-16)*255/219)
         return np.clip(np.floor_divide(g, 219), 0, 255).astype(np.uint8)
 
+    def read_yuv(self, i: int) -> np.ndarray:
+        """The packed I420 frame of an 8-bit C420* stream of even size, as it is
+        stored: rows * cols * 3 / 2 bytes, Y then U then V, no range expansion
+        (yuv.split takes it apart).  Any other stream raises FrameError."""
+        if not self.chroma.startswith("420") or self.rows % 2 or self.cols % 2:
+            raise FrameError(f"{self.path}: read_yuv needs an 8-bit 4:2:0 stream of even size, "
+                             f"not C{self.chroma} {self.cols}x{self.rows}")
+        if not 0 <= i < len(self.offsets):
+            raise FrameError(f"frame {i} outside [0, {len(self.offsets)})")
+        return np.fromfile(self.path, np.uint8, count=self.frame_bytes, offset=self.offsets[i])
+
 
 def write_y4m(path: str, frames: Iterable[np.ndarray], full_range: bool = True) -> None:
     """Gray frames as a 'Cmono' YUV4MPEG2 stream (test fixtures, examples)."""
@@ -187,6 +203,24 @@ def write_y4m(path: str, frames: Iterable[np.ndarray], full_range: bool = True) 
         for fr in frames:
             f.write(b"FRAME\n")
             f.write(np.ascontiguousarray(fr, np.uint8).tobytes())
+
+
+def write_y4m_420(path: str, frames: Iterable[np.ndarray], rows: int, cols: int,
+                  full_range: bool = False) -> None:
+    """Packed I420 frames (uint8, rows * cols * 3 / 2 bytes each; rows and cols
+    even) as a 'C420jpeg' YUV4MPEG2 stream, byte for byte."""
+    if rows < 2 or cols < 2 or rows % 2 or cols % 2:
+        raise FrameError(f"a 4:2:0 stream needs even rows and cols, not {rows}x{cols}")
+    with open(path, "wb") as f:
+        f.write(b"YUV4MPEG2 W%d H%d F25:1 Ip A1:1 C420jpeg%s\n"
+                % (cols, rows, b" XCOLORRANGE=FULL" if full_range else b""))
+        for fr in frames:
+            a = np.ascontiguousarray(fr, np.uint8).reshape(-1)
+            if a.size != rows * cols * 3 // 2:
+                raise FrameError(f"a packed {rows}x{cols} 4:2:0 frame has "
+                                 f"{rows * cols * 3 // 2} bytes, not {a.size}")
+            f.write(b"FRAME\n")
+            f.write(a.tobytes())
 
 
 def open_source(spec: str, rows: Optional[int] = None, cols: Optional[int] = None):
@@ -403,3 +437,62 @@ def _bgr_frame(src, i: int) -> np.ndarray:
         raise FrameError(f"frame {i} is not 8-bit BGR (H x W x 3): interpolate_sequence needs a "
                          "colour source; for grey frames use Context.interpolate")
     return a
+
+
+def interpolate_sequence_yuv(src, factor: int, levels: int, warps: int, window: int, iters: int,
+                             alpha: float, median: int = 0, context=None, prefilter=None,
+                             smoothness=None, temporal: bool = False, finest=None, fallback=None,
+                             cuts=None):
+    """interpolate_sequence for a 4:2:0 source: a generator of (len(src) - 1) *
+    factor + 1 packed I420 frames (uint8, rows * cols * 3 / 2 bytes).  `src`
+    has `rows`, `cols` and `read_yuv(i)` (Y4MVideo on a C420* stream).  Every
+    factor-th frame is a source frame, byte for byte; the factor - 1 frames
+    between two come from one yuv.interpolate_yuv call per pair: the solve runs
+    on the luma planes as they are, the chroma follows the same flows on its
+    own grid.  context, prefilter, smoothness, temporal, finest, fallback and
+    cuts as in interpolate_sequence; there is no projection (it is not supported
+    on chroma)."""
+    factor = int(factor)
+    if factor < 1:
+        raise ValueError("factor must be at least 1")
+    n = len(src)
+    if n == 0:
+        return
+    rows, cols = src.rows, src.cols
+    prev = _yuv_frame(src, 0)
+    yield prev
+    times = [j / factor for j in range(1, factor)]
+    ctx, started = context, False
+    with contextlib.ExitStack() as mode:
+        for i in range(1, n):
+            nxt = _yuv_frame(src, i)
+            if times:
+                import yuv
+                if ctx is None:
+                    import hsflow
+                    ctx = hsflow.default_context()
+                if temporal and not started:
+                    import temporal as seq
+                    mode.enter_context(seq.sequence(ctx))  # starts without a prediction
+                    started = True
+                mid = yuv.interpolate_yuv(ctx, prev, nxt, times, levels, warps, window, iters,
+                                          alpha, rows, cols, median=median, out_dtype=np.uint8,
+                                          prefilter=prefilter, smoothness=smoothness,
+                                          finest=finest, fallback=fallback)
+                if cuts is not None and ctx.last_cut:
+                    cuts.append(i)
+                for k in range(len(times)):
+                    yield mid[k]
+            yield nxt
+            prev = nxt
+
+
+def _yuv_frame(src, i: int) -> np.ndarray:
+    if not hasattr(src, "read_yuv"):
+        raise FrameError("interpolate_sequence_yuv needs a 4:2:0 source with read_yuv(i) "
+                         "(Y4MVideo); for BGR frames use interpolate_sequence")
+    a = np.asarray(src.read_yuv(i))
+    if a.dtype != np.uint8 or a.size != src.rows * src.cols * 3 // 2:
+        raise FrameError(f"frame {i} is not a packed 8-bit 4:2:0 frame of "
+                         f"{src.cols}x{src.rows}")
+    return a.reshape(-1)

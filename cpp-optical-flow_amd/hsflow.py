@@ -339,6 +339,18 @@ def _prototypes():
         "hsflow_ctx_set_fallback": (i, [vp] + fb),
         "hsflow_ctx_fallback": (i, [vp] + fb),
         "hsflow_ctx_last_cut": (i, [vp]),
+        # YUV 4:2:0 (yuv.py is its public face): KIY on the chroma, the fused
+        # call on luma and chroma planes, the host call on packed frames
+        "hsflow_chroma_interp_device": (i, [vp, vp, i] + shape + flows + [vp, vp] + fb
+                                        + [fp, i, vp, i, vp]),
+        "hsflow_flow_interp_yuv_workspace_bytes": (sz, shape + [i, i]),
+        "hsflow_flow_interp_yuv_device": (i, [vp, vp, vp, vp, i] + shape + solve_lv + thresholds
+                                          + [fp, i, vp, vp, i, vp, vp, vp] + pf + sm + init + fb
+                                          + tail),
+        "hsflow_flow_interp_yuv": (i, [vp, vp, vp, i, i, i] + solve_d + thresholds
+                                   + [fp, i, vpp, i, vpp, vp]),
+        "hsflow_chroma_interp_blocks_per_cu": (i, []),
+        "hsflow_set_chroma_nv12_loads": (i, [i]),
         "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
         "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
         "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),

@@ -1,0 +1,272 @@
+"""YUV 4:2:0 frame interpolation (include/hsflow.h, "YUV 4:2:0 frame
+interpolation"): I420 and NV12 frames in, the same layout out.
+
+Video arrives as 4:2:0, not as BGR.  The luma plane of such a frame is the grey
+frame the solver wants, so it goes through the grey calls as it is -- no colour
+conversion either way and half the bytes of BGR -- and the chroma follows the
+same flows on its own grid: chroma_interp_device (KIY) is, bit for bit,
+temporal.downflow_device on both flow pairs followed by
+hsflow.frame_interp_device on the U planes and on the V planes, in one launch.
+
+A packed frame is a uint8 array of rows * cols * 3 // 2 bytes, the luma plane
+followed by the chroma (I420: the U plane, then the V plane; NV12: U and V
+interleaved); rows and cols are the luma's and even.  On the device luma
+[B, rows, cols] and chroma (I420 [B, 2, rows / 2, cols / 2], NV12 [B, rows / 2,
+cols / 2, 2]) are separate tensors.  The flow projection is not supported on
+chroma; every other option of the BGR calls is.
+
+Everything here calls the HIP path in libhsflow.so through hsflow's front ends.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+import hsflow
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+
+# layouts (HSFLOW_YUV_*)
+YUV_I420, YUV_NV12 = 1, 2
+LAYOUTS = {"i420": YUV_I420, "nv12": YUV_NV12, YUV_I420: YUV_I420, YUV_NV12: YUV_NV12}
+# KIY's tile: a block takes 512 consecutive chroma samples of a pair at a time
+CHROMA_TILE = 512
+
+
+def _layout(layout) -> int:
+    key = layout.lower() if isinstance(layout, str) else layout
+    if key not in LAYOUTS:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG,
+                                 f"layout {layout!r}: need 'i420' (1) or 'nv12' (2)")
+    return LAYOUTS[key]
+
+
+def _even(rows, cols):
+    if rows < 2 or cols < 2 or rows % 2 or cols % 2:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG,
+                                 f"YUV 4:2:0 needs even rows and cols, not {rows}x{cols}")
+
+
+def frame_bytes(rows: int, cols: int) -> int:
+    """Bytes of a packed 8-bit 4:2:0 frame."""
+    _even(rows, cols)
+    return rows * cols * 3 // 2
+
+
+def chroma_shape(rows: int, cols: int, layout=YUV_I420):
+    """The shape of one frame's chroma: (2, rows / 2, cols / 2) for I420,
+    (rows / 2, cols / 2, 2) for NV12."""
+    _even(rows, cols)
+    rc, cc = rows // 2, cols // 2
+    return (2, rc, cc) if _layout(layout) == YUV_I420 else (rc, cc, 2)
+
+
+def split(frame, rows: int, cols: int, layout=YUV_I420):
+    """(y, u, v) of packed frames [..., rows * cols * 3 / 2] (any dtype): views
+    y [..., rows, cols] and u, v [..., rows / 2, cols / 2]."""
+    frame = np.asarray(frame)
+    n = frame_bytes(rows, cols)
+    if frame.shape[-1:] != (n,):
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG,
+                                 f"a packed {rows}x{cols} frame has {n} samples, not "
+                                 f"{frame.shape[-1:]}")
+    lead = frame.shape[:-1]
+    y = frame[..., :rows * cols].reshape(lead + (rows, cols))
+    c = frame[..., rows * cols:].reshape(lead + chroma_shape(rows, cols, layout))
+    if _layout(layout) == YUV_I420:
+        return y, c[..., 0, :, :], c[..., 1, :, :]
+    return y, c[..., 0], c[..., 1]
+
+
+def pack(y, u, v, layout=YUV_I420):
+    """The packed frames [..., rows * cols * 3 / 2] of y [..., rows, cols] and
+    u, v [..., rows / 2, cols / 2], in y's dtype."""
+    y, u, v = np.asarray(y), np.asarray(u), np.asarray(v)
+    rows, cols = y.shape[-2:]
+    _even(rows, cols)
+    lead = y.shape[:-2]
+    if u.shape != lead + (rows // 2, cols // 2) or v.shape != u.shape:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_SIZE, "u, v: need y's shape halved each way")
+    c = np.stack([u, v], axis=-3 if _layout(layout) == YUV_I420 else -1).astype(y.dtype)
+    return np.concatenate([y.reshape(lead + (-1,)), c.reshape(lead + (-1,))], axis=-1)
+
+
+def convert(frame, rows: int, cols: int, src, dst):
+    """Packed frames of layout `src` in layout `dst` (a copy)."""
+    return pack(*split(frame, rows, cols, src), layout=dst)
+
+
+def blocks_per_cu() -> int:
+    """The cap of KIY's grid in blocks per compute unit
+    (hsflow_chroma_interp_blocks_per_cu): a chroma plane of more than
+    blocks_per_cu() * CUs * CHROMA_TILE samples makes a single pair's blocks
+    stride."""
+    return int(hsflow.lib().hsflow_chroma_interp_blocks_per_cu())
+
+
+def set_nv12_loads(wide: bool) -> bool:
+    """How KIY fetches the two adjacent taps of an NV12 row: four byte loads
+    (False, the default) or one unaligned 32-bit load; same bits
+    (hsflow_set_chroma_nv12_loads).  Returns the previous setting."""
+    return bool(hsflow.lib().hsflow_set_chroma_nv12_loads(1 if wide else 0))
+
+
+def _chroma_pair(c0, c1, layout):
+    """(rows, cols, batch) of the luma the uint8 CUDA chroma tensors c0, c1
+    belong to: I420 [B, 2, rc, cc] or [2, rc, cc], NV12 [B, rc, cc, 2] or
+    [rc, cc, 2]."""
+    for t, name in ((c0, "c0"), (c1, "c1")):
+        if torch is None or not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or \
+                t.dim() not in (3, 4) or not t.is_cuda or not t.is_contiguous():
+            raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, f"{name}: need a contiguous uint8 "
+                                     "CUDA tensor, I420 [B, 2, rc, cc] or NV12 [B, rc, cc, 2]")
+    if c1.shape != c0.shape:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_SIZE, "c0/c1 differ in shape")
+    batch = c0.shape[0] if c0.dim() == 4 else 1
+    shape = tuple(c0.shape[-3:])
+    two, (rc, cc) = (shape[0], shape[1:]) if layout == YUV_I420 else (shape[2], shape[:2])
+    if two != 2:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, f"chroma of shape {shape} is not "
+                                 "I420 [2, rc, cc]" if layout == YUV_I420 else
+                                 f"chroma of shape {shape} is not NV12 [rc, cc, 2]")
+    return 2 * rc, 2 * cc, batch
+
+
+def _chroma_out(c0, nt, out, out_dtype):
+    """out_c of `nt` times: [B, nt] + a chroma frame's shape (no B for a single
+    frame's chroma), float32 (default) or uint8."""
+    lead = tuple(c0.shape[:-3])
+    return hsflow._out_frames(out, lead + (nt,) + tuple(c0.shape[-3:]), out_dtype, c0.device)
+
+
+def chroma_interp_device(c0, c1, uf, vf, ub, vb, times, layout=YUV_I420, counts_f=None,
+                         counts_b=None, fallback=None, out=None, out_dtype=None, stream=None):
+    """The chroma of the frames at `times` between the chroma c0 and c1 (uint8
+    CUDA tensors, I420 [B, 2, rc, cc] or NV12 [B, rc, cc, 2]) from the
+    full-resolution flows of the luma solve, float32 [B, 2 rc, 2 cc]
+    (hsflow_chroma_interp_device, KIY): temporal.downflow_device of both flow
+    pairs and hsflow.frame_interp_device on the U and on the V planes, bit for
+    bit, in one launch.  counts_f, counts_b (int32 [B, 3], the luma's from
+    hsflow.consistency_device) and fallback (a fallback.Fallback): a pair that
+    fails fallback.min_consistent(2 rc, 2 cc, min_share) gets
+    fallback.frame_fallback_device's value.  out: float32 (default) or uint8,
+    [B, len(times)] + the chroma's shape.  Returns out.  Stream-ordered."""
+    lay = _layout(layout)
+    dims = _chroma_pair(c0, c1, lay)
+    hsflow._check_planes(dims, uf=uf, vf=vf, ub=ub, vb=vb)
+    tm = hsflow._times_array(times)
+    out = _chroma_out(c0, len(tm), out, out_dtype)
+    keep, fb = hsflow._option(hsflow._Fallback, fallback)
+    counts = [None, None]
+    if fallback is not None:
+        import fallback as _fallback
+        counts = [_fallback._counts(c, dims[2], c0.device, n)
+                  for c, n in ((counts_f, "counts_f"), (counts_b, "counts_b"))]
+    hsflow._device_call("hsflow_chroma_interp_device", c0.device, stream, c0.data_ptr(),
+                        c1.data_ptr(), lay, *dims, uf.data_ptr(), vf.data_ptr(), ub.data_ptr(),
+                        vb.data_ptr(), *counts, fb, tm, len(tm), out.data_ptr(),
+                        hsflow._out_code(out))
+    return out
+
+
+def flow_interp_workspace_bytes(rows: int, cols: int, batch: int, levels: int,
+                                fallback: bool = False) -> int:
+    """The workspace of flow_interp_yuv_device
+    (hsflow_flow_interp_yuv_workspace_bytes): the grey fused call's; a
+    prefilter's planes come on top (hsflow.prefilter_planes_bytes)."""
+    return int(hsflow.lib().hsflow_flow_interp_yuv_workspace_bytes(rows, cols, batch, levels,
+                                                                   1 if fallback else 0))
+
+
+def flow_interp_yuv_device(y0, c0, y1, c1, times, levels: int, warps: int, window: int,
+                           iters: int, alpha: float, layout=YUV_I420, median: int = 0,
+                           rel: float = hsflow.CONSISTENCY_REL,
+                           abs: float = hsflow.CONSISTENCY_ABS, out_y=None, out_c=None,
+                           out_dtype=None, flags=None, trusted=None, workspace=None, stream=None,
+                           prefilter=None, smoothness=None, finest: int = 0, fallback=None,
+                           init=None, cut=None):
+    """hsflow.flow_interp_device on the luma planes y0, y1 (uint8 [B, H, W]) and
+    chroma_interp_device on the flows and counts it leaves in the workspace: one
+    call, the same bits (hsflow_flow_interp_yuv_device).  c0, c1, layout as in
+    chroma_interp_device.  out_y [B, len(times), H, W] and out_c [B, len(times)]
+    + the chroma's shape share their dtype, float32 (default) or uint8; flags,
+    trusted and cut are the luma's.  prefilter, smoothness, finest, fallback,
+    init and cut as in hsflow.flow_interp_bgr_device and
+    temporal.flow_interp_device; there is no projection.  Returns (out_y, out_c,
+    flags, trusted), and cut behind them where it was asked for.
+    Stream-ordered."""
+    lay = _layout(layout)
+    dims = hsflow._frame_pair(y0, y1)
+    if y0.dtype != torch.uint8:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "y0, y1: need uint8 luma planes")
+    if _chroma_pair(c0, c1, lay) != dims or c0.device != y0.device:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_SIZE,
+                                 "the chroma is not that of the luma planes' shape")
+    tm = hsflow._times_array(times)
+    out_y, flags, trusted = hsflow._interp_outputs(y0, (), len(tm), out_y, out_dtype, flags,
+                                                   trusted)
+    out_c = _chroma_out(c0, len(tm), out_c, out_y.dtype)
+    if out_c.dtype != out_y.dtype:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "out_y and out_c differ in dtype")
+    pf = hsflow._option(hsflow.Prefilter, prefilter)[1]
+    sm = hsflow._option(hsflow.Smoothness, smoothness)[1]
+    workspace = hsflow._workspace(workspace, y0.device, hsflow.flow_interp_workspace_bytes, *dims,
+                                  levels, prefilter=prefilter, fallback=fallback)
+    _, _, start = hsflow._init_entry("hsflow_flow_interp", init, dims, 1)
+    cut = hsflow._check_output(cut, (dims[2],), torch.uint8, y0.device, "cut")
+    keep, fb = hsflow._option(hsflow._Fallback, fallback)
+    hsflow._device_call("hsflow_flow_interp_yuv_device", y0.device, stream, y0.data_ptr(),
+                        c0.data_ptr(), y1.data_ptr(), c1.data_ptr(), lay, *dims,
+                        *hsflow._solve_args(levels, warps, median, window, iters, alpha, finest),
+                        float(rel), float(abs), tm, len(tm), out_y.data_ptr(), out_c.data_ptr(),
+                        hsflow._out_code(out_y), hsflow._ptr(flags), hsflow._ptr(trusted),
+                        hsflow._ptr(cut), pf, sm, *start, fb, *hsflow._ws_args(workspace))
+    res = (out_y, out_c, flags, trusted)
+    return res if cut is None else res + (cut,)
+
+
+def interpolate_yuv(ctx, f0, f1, times, levels: int, warps: int, window: int, iters: int,
+                    alpha: float, rows: int, cols: int, layout=YUV_I420, median: int = 0,
+                    rel: float = hsflow.CONSISTENCY_REL, abs: float = hsflow.CONSISTENCY_ABS,
+                    out_dtype=np.uint8, with_flags: bool = False, prefilter=None,
+                    smoothness=None, finest=None, fallback=None):
+    """The packed frames at `times` between the packed 8-bit 4:2:0 frames f0 and
+    f1 (uint8, rows * cols * 3 / 2 bytes each; rows, cols the luma's) on the
+    hsflow.Context `ctx` (hsflow_flow_interp_yuv): the luma through
+    Context.interpolate's path, the chroma through KIY.  Returns an array
+    [len(times), rows * cols * 3 / 2] of out_dtype (uint8 or float32) in the
+    same layout, or with_flags: (frames, flags, trusted) -- the luma's, flags
+    uint8 [len(times), rows, cols].  prefilter, smoothness, finest and fallback
+    as in Context.interpolate_bgr; the context's sequence mode is honoured and
+    Context.last_cut set.  A context with the projection on is refused: the
+    projection is not supported on chroma."""
+    lay = _layout(layout)
+    n = frame_bytes(rows, cols)
+    frames = []
+    for f, name in ((f0, "f0"), (f1, "f1")):
+        a = np.ascontiguousarray(f)
+        if a.dtype != np.uint8 or a.size != n:
+            raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, f"{name}: need a packed uint8 frame "
+                                     f"of {n} bytes ({rows}x{cols} 4:2:0)")
+        frames.append(a)
+    tm = hsflow._times_array(times)
+    nt = len(tm)
+    out = np.empty((nt, n), out_dtype)
+    if out.dtype not in (np.uint8, np.float32):
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "out_dtype: need uint8 or float32")
+    flags = np.empty((nt, rows, cols), np.uint8) if with_flags else None
+    trusted = np.zeros(nt, np.uint32) if with_flags else None
+    vp = ctypes.c_void_p
+    planes = (vp * nt)(*[out[k].ctypes.data for k in range(nt)])
+    fplanes = (vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
+    ctx._call_with(prefilter, smoothness, "hsflow_flow_interp_yuv", frames[0].ctypes.data,
+                   frames[1].ctypes.data, lay, int(rows), int(cols),
+                   *hsflow._solve_args(levels, warps, median, window, iters, alpha), float(rel),
+                   float(abs), tm, nt, planes, hsflow._dtype_code(out), fplanes,
+                   trusted.ctypes.data if with_flags else None, finest=finest, fallback=fallback)
+    return (out, flags, trusted) if with_flags else out

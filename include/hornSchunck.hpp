@@ -19,6 +19,9 @@
 #if __has_include(<opencv2/core.hpp>)
 #include <opencv2/core.hpp>
 
+#include <cstring>
+#include <vector>
+
 #include "hsflow.hpp"
 
 class hornSchunck {
@@ -110,6 +113,38 @@ class hornSchunck {
         int cut = -1;
         guarded([&] { cut = impl_.lastCut(); });
         return cut;
+    }
+
+    // The 4:2:0 frames at `times` between two 8-bit 4:2:0 frames in OpenCV's own
+    // representation of them -- CV_8UC1 of rows * 3 / 2 x cols, continuous: what
+    // cv::cvtColor(COLOR_BGR2YUV_I420) gives and COLOR_YUV2BGR_I420 / _NV12
+    // takes -- in the same layout (hsflow.h, hsflow_flow_interp_yuv): no colour
+    // conversion, the luma is the grey frame.  frames[k] is created like the
+    // inputs.  The settings above apply; with the projection on the call throws.
+    void getFrameInterpYuv(const cv::Mat &imagePrev, const cv::Mat &imageNext,
+                           const std::vector<float> &times, int levels, int warps, int median,
+                           std::vector<cv::Mat> &frames, int layout = HSFLOW_YUV_I420) {
+        sync_params();
+        if (imagePrev.empty() || imageNext.empty()) CV_Error(cv::Error::StsBadArg, "empty image");
+        if (imagePrev.type() != CV_8UC1 || imageNext.type() != CV_8UC1)
+            CV_Error(cv::Error::StsBadArg, "a 4:2:0 frame is CV_8UC1 of rows * 3 / 2 x cols");
+        if (imagePrev.rows != imageNext.rows || imagePrev.cols != imageNext.cols)
+            CV_Error(cv::Error::StsBadArg, "Image sizes are different");
+        if (imagePrev.rows % 3 || imagePrev.step != (size_t)imagePrev.cols ||
+            imageNext.step != (size_t)imageNext.cols)
+            CV_Error(cv::Error::StsBadArg,
+                     "a 4:2:0 frame is continuous and rows * 3 / 2 rows high");
+        const int rows = imagePrev.rows / 3 * 2, cols = imagePrev.cols;
+        std::vector<std::vector<uint8_t>> packed;
+        guarded([&] {
+            impl_.getFrameInterpYuv(imagePrev.data, imageNext.data, layout, rows, cols, times,
+                                    levels, warps, median, packed);
+        });
+        frames.resize(packed.size());
+        for (size_t k = 0; k < packed.size(); ++k) {
+            frames[k].create(imagePrev.rows, cols, CV_8UC1);
+            std::memcpy(frames[k].data, packed[k].data(), packed[k].size());
+        }
     }
 
   private:

@@ -1318,6 +1318,104 @@ int hsflow_ctx_set_fallback(hsflow_ctx *ctx, const hsflow_fallback *fb);
 int hsflow_ctx_fallback(const hsflow_ctx *ctx, hsflow_fallback *fb);
 int hsflow_ctx_last_cut(const hsflow_ctx *ctx);
 
+/* ---- YUV 4:2:0 frame interpolation: I420 and NV12 in, the same layout out --
+ * Video arrives as 4:2:0, not as BGR: a full-resolution luma plane and the two
+ * chroma planes at half the size each way.  The luma plane is the grey frame
+ * the solver wants, so it goes through the grey calls as it is -- no colour
+ * conversion either way and half the bytes of BGR -- and the chroma follows
+ * the same flows on its own grid.
+ *
+ * rows and cols are the luma's and both even (else HSFLOW_ERR_ARG);
+ * rc = rows / 2, cc = cols / 2.  8-bit samples, dense planes.
+ *   HSFLOW_YUV_I420  chroma [batch][2][rc][cc], the U plane then the V plane
+ *   HSFLOW_YUV_NV12  chroma [batch][rc][cc][2], U and V interleaved
+ * A packed frame p of rows * cols * 3 / 2 samples is y = p, c = p + rows * cols
+ * in either layout.  Luma and chroma of a batch are separate dense arrays.
+ *
+ * The chroma of the frame at time t is, by definition and bit for bit,
+ *   hsflow_downflow_device on (uf, vf) and on (ub, vb): per plane
+ *     ((a + b) + (c + d)) * 0.125f over the 2 x 2 luma block, the block's mean
+ *     flow in chroma pixels, and then
+ *   hsflow_frame_interp_device (U8 frames, NULL masks) with those flows on the
+ *     U planes of the two frames, rc x cc, and the same on the V planes.
+ * So the sampler, the displacement clamp, the rim test (on the chroma grid),
+ * the blend, the rounding of a U8 output and the handling of NaN and inf are
+ * that call's.  A displacement is applied within the chroma grid, input and
+ * output share their siting, so chroma siting does not enter.  Chroma has no
+ * flags and no trusted count: the luma's are the frame's.
+ * With a fallback a pair's verdict is the luma's: its counts against
+ * hsflow_fallback_min_consistent(rows, cols, min_share), the luma's size.  A
+ * pair that fails gets, per chroma byte, what hsflow_frame_fallback_device
+ * writes for a grey U8 plane; a pair that passes keeps the interpolated chroma.
+ * The flow projection is not supported on chroma: luma projected and chroma not
+ * would fringe at motion boundaries, so the calls below take no projection and
+ * the host call refuses a context that has it on. */
+#define HSFLOW_HAS_YUV 1
+#define HSFLOW_YUV_I420 1
+#define HSFLOW_YUV_NV12 2
+
+/* KIY: the chroma of `nt` frames (times: host array, read at call time, each in
+ * [0, 1], nt in 1 .. HSFLOW_MAX_TIMES) between the chroma c0 and c1 of `layout`,
+ * from the four full-resolution flows (dense f32 [batch][rows][cols]).  out_c:
+ * [batch][nt] chroma frames of the same layout, dtype_out U8 or F32.
+ * counts_f, counts_b (device, uint32[batch][3], the luma's from
+ * hsflow_flow_consistency_device) and fb: all given and fb's mode NEAREST or
+ * BLEND for the fallback; fb NULL or mode 0 for none, the counts are then not
+ * read.  Planes need element alignment only: flow planes on 8-byte boundaries
+ * are read in 8-byte loads, a U8 output on a 4-byte boundary is written in
+ * whole words, the bits are the same wherever they lie.  out_c must be disjoint
+ * from every input.  All arguments are checked before any device work.  One
+ * launch for both channels, all times and the whole batch.  Stream-ordered, no
+ * workspace, never allocates or synchronises, capturable. */
+int hsflow_chroma_interp_device(const uint8_t *c0, const uint8_t *c1, int layout, int rows,
+                                int cols, int batch, const float *uf, const float *vf,
+                                const float *ub, const float *vb, const uint32_t *counts_f,
+                                const uint32_t *counts_b, const hsflow_fallback *fb,
+                                const float *times, int nt, void *out_c, int dtype_out,
+                                void *stream);
+
+/* The fused call: hsflow_flow_interp_fb_device with projection 0 on the luma
+ * planes y0, y1 (U8, dense [batch][rows][cols]) -- out_y, flags, trusted and cut
+ * are that call's, bit for bit -- and then hsflow_chroma_interp_device on the
+ * flows and counts that call leaves in the workspace.  out_y: [batch][nt] luma
+ * planes, out_c: [batch][nt] chroma frames, both of dtype_out (U8 or F32).  The
+ * workspace is the grey call's: hsflow_flow_interp_yuv_workspace_bytes (fallback
+ * != 0: with the counts of a fallback; 0 for a bad shape), a prefilter's planes
+ * behind it, as ever.  No output may overlap an input, the workspace or another
+ * output.  All arguments are checked before any device work. */
+size_t hsflow_flow_interp_yuv_workspace_bytes(int rows, int cols, int batch, int levels,
+                                              int fallback);
+int hsflow_flow_interp_yuv_device(const uint8_t *y0, const uint8_t *c0, const uint8_t *y1,
+                                  const uint8_t *c1, int layout, int rows, int cols, int batch,
+                                  int levels, int finest, int warps, int median, int window,
+                                  int iters, float alpha, float rel, float abs_thr,
+                                  const float *times, int nt, void *out_y, void *out_c,
+                                  int dtype_out, uint8_t *flags, uint32_t *trusted, uint8_t *cut,
+                                  const hsflow_prefilter *pf, const hsflow_smoothness *sm,
+                                  const hsflow_flow_init *init, const hsflow_fallback *fb,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* Host, blocking: two packed frames f0, f1 of rows * cols * 3 / 2 bytes each in,
+ * out[k] the packed frame at times[k] in the same layout, rows * cols * 3 / 2
+ * elements of dtype_out (U8 or F32).  flags (NULL, or one dense rows x cols u8
+ * plane per time) and trusted (NULL or uint32[nt]) are the luma's.  The context's
+ * prefilter, smoothness, finest level, sequence mode and fallback are honoured
+ * as by hsflow_flow_interp_bgr, and hsflow_ctx_last_cut is set; the result
+ * equals the device call's bit for bit.  A context with the projection on is
+ * HSFLOW_ERR_ARG: the projection is not supported on chroma. */
+int hsflow_flow_interp_yuv(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1, int layout,
+                           int rows, int cols, int levels, int warps, int median, int window,
+                           int iters, double alpha, float rel, float abs_thr, const float *times,
+                           int nt, void *const *out, int dtype_out, uint8_t *const *flags,
+                           uint32_t *trusted);
+
+/* The cap of KIY's grid in blocks per compute unit (each block takes tiles of
+ * 512 chroma samples of one pair and strides), and how it fetches the two
+ * adjacent taps of an NV12 row: as four bytes (0, the default) or as one
+ * unaligned 32-bit load (1); same bits.  Returns the previous setting. */
+int hsflow_chroma_interp_blocks_per_cu(void);
+int hsflow_set_chroma_nv12_loads(int wide);
+
 /* ---- host utilities on the path to the hot loop ------------------------ */
 
 /* main.cpp:13-14 cv::cvtColor(BGR2GRAY) for 8-bit BGR, OpenCV 4.x 15-bit

@@ -151,6 +151,39 @@ class Context {
     }
     int lastCut() const { return hsflow_ctx_last_cut(ctx_); }
 
+    // The packed 4:2:0 frames at `times` between two packed 8-bit 4:2:0 frames
+    // of `layout` (HSFLOW_YUV_I420 or HSFLOW_YUV_NV12), rows * cols * 3 / 2 bytes
+    // each, rows and cols the luma's and even (hsflow.h, hsflow_flow_interp_yuv):
+    // the solve runs on the luma planes as they are, the chroma follows the same
+    // flows on its own grid; no colour conversion.  frames[k]: the frame at
+    // times[k] in the same layout; flags[k]: rows * cols HSFLOW_INTERP_* bytes,
+    // the luma's.  The context's prefilter, smoothness, finest level, sequence
+    // mode and fallback apply, lastCut() is set; with the projection on the
+    // call throws (it is not supported on chroma).
+    void getFrameInterpYuv(const uint8_t *prev, const uint8_t *next, int layout, int rows,
+                           int cols, const std::vector<float> &times, int levels, int warps,
+                           int median, int windowSize, int maxIterations, double alpha,
+                           std::vector<std::vector<uint8_t>> &frames,
+                           std::vector<std::vector<uint8_t>> *flags = nullptr) {
+        if (!prev || !next) throw Error(HSFLOW_ERR_ARG, "empty image");
+        if (rows < 2 || cols < 2 || rows % 2 || cols % 2)
+            throw Error(HSFLOW_ERR_ARG, "YUV 4:2:0 needs even rows and cols");
+        const size_t n = (size_t)rows * cols;
+        frames.resize(times.size());
+        if (flags) flags->resize(times.size());
+        std::vector<void *> out(times.size());
+        std::vector<uint8_t *> fl(times.size());
+        for (size_t k = 0; k < times.size(); ++k) {
+            frames[k].resize(n / 2 * 3);
+            out[k] = frames[k].data();
+            if (flags) (*flags)[k].resize(n), fl[k] = (*flags)[k].data();
+        }
+        check(hsflow_flow_interp_yuv(ctx_, prev, next, layout, rows, cols, levels, warps, median,
+                                     windowSize, maxIterations, alpha, HSFLOW_CONSISTENCY_REL,
+                                     HSFLOW_CONSISTENCY_ABS, times.data(), (int)times.size(),
+                                     out.data(), HSFLOW_U8, flags ? fl.data() : nullptr, nullptr));
+    }
+
   private:
     hsflow_ctx *ctx_ = nullptr;
 };
@@ -362,6 +395,16 @@ class HornSchunck {
             alpha, HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS, times.data(),
             (int)times.size(), out.data(), HSFLOW_U8, dense, flags ? fl.data() : nullptr,
             (size_t)prev.cols, nullptr));
+    }
+
+    // getFrameInterp for packed 8-bit 4:2:0 frames (Context::getFrameInterpYuv,
+    // with this object's window, iterations and alpha)
+    void getFrameInterpYuv(const uint8_t *prev, const uint8_t *next, int layout, int rows,
+                           int cols, const std::vector<float> &times, int levels, int warps,
+                           int median, std::vector<std::vector<uint8_t>> &frames,
+                           std::vector<std::vector<uint8_t>> *flags = nullptr) {
+        ctx().getFrameInterpYuv(prev, next, layout, rows, cols, times, levels, warps, median,
+                                windowSize, maxIterations, alpha, frames, flags);
     }
 
     // Raw form for callers that own output rows (cv::Mat adapter): dtype_out
