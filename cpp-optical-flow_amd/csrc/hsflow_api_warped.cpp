@@ -1127,7 +1127,8 @@ size_t chroma_out_bytes(const ChromaIO &C, int rows, int cols, int batch) {
     return chroma_bytes(rows, cols, batch) * C.nt * elem_size(C.dtype_out);
 }
 
-// KIY on checked arguments: one launch.  fb: null for no fallback
+// KIY, or with W.cells KIYP, on checked arguments: one launch.  fb: null for no
+// fallback
 int chroma_interp_run(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, int batch,
                       const FlowsIn &W, const uint32_t *counts_f, const uint32_t *counts_b,
                       const hsflow_fallback *fb, hipStream_t s) {
@@ -1135,19 +1136,21 @@ int chroma_interp_run(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, in
     hipError_t e = hsflow::launch_chroma_interp(
         C.c0, C.c1, C.layout, rows, cols, batch, W.uf, W.vf, W.ub, W.vb, on ? counts_f : nullptr,
         on ? counts_b : nullptr, on ? min_consistent(rows, cols, fb->min_share) : 0,
-        on ? fb->mode : 0, C.times, C.nt, C.out, C.dtype_out == HSFLOW_U8, s);
+        on ? fb->mode : 0, C.times, C.nt, C.out, C.dtype_out == HSFLOW_U8, s, W.cells);
     if (e != hipSuccess) return hip_fail(ctx, e, "chroma interpolation launch");
     return HSFLOW_OK;
 }
 
-// hsflow_chroma_interp_device
+// hsflow_chroma_interp_device and, `proj`, hsflow_chroma_interp_proj_device, which
+// reads W.cells (KS's, of the luma)
 int chroma_interp_impl(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, int batch,
                        const FlowsIn &W, const uint32_t *counts_f, const uint32_t *counts_b,
-                       const hsflow_fallback *fb, hipStream_t s) {
+                       const hsflow_fallback *fb, bool proj, hipStream_t s) {
     int rc = check_yuv_shape(ctx, C.layout, rows, cols, batch);
     if (rc) return rc;
     if (!C.c0 || !C.c1 || !W.uf || !W.vf || !W.ub || !W.vb || !C.out) return null_pointer(ctx);
     if ((rc = check_interp_args(ctx, C.times, C.nt, C.dtype_out, false))) return rc;
+    if (proj && (rc = check_cells(ctx, W.cells))) return rc;
     const bool on = fb_on(fb);
     if (on) {
         if ((rc = check_fallback(ctx, fb))) return rc;
@@ -1155,18 +1158,41 @@ int chroma_interp_impl(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, i
     }
     const size_t n = (size_t)rows * cols * batch, cb = chroma_bytes(rows, cols, batch);
     const size_t kb = (size_t)batch * 3 * 4;
-    const ByteRange in[8] = {{C.c0, cb},    {C.c1, cb},    {W.uf, n * 4},
+    const ByteRange in[9] = {{C.c0, cb},    {C.c1, cb},    {W.uf, n * 4},
                              {W.vf, n * 4}, {W.ub, n * 4}, {W.vb, n * 4},
-                             {on ? counts_f : nullptr, kb}, {on ? counts_b : nullptr, kb}};
+                             {on ? counts_f : nullptr, kb}, {on ? counts_b : nullptr, kb},
+                             {proj ? W.cells : nullptr, n * C.nt * 8}};
     const ByteRange out{C.out, chroma_out_bytes(C, rows, cols, batch)};
-    if (!outputs_disjoint(in, 8, &out, 1))
+    if (!outputs_disjoint(in, 9, &out, 1))
         return fail(ctx, HSFLOW_ERR_ARG, "chroma output overlaps the inputs");
     return chroma_interp_run(ctx, C, rows, cols, batch, W, counts_f, counts_b, fb, s);
 }
 
-// hsflow_flow_interp_yuv_device: what the chroma adds to the grey call's checks
-// (first, so that nothing has run when one fails), flow_interp_impl on the luma
-// planes, then KIY on the flows and counts that call left in the workspace
+// hsflow_cells_down_device (KSD)
+int cells_down_impl(hsflow_ctx *ctx, const uint64_t *cells, int rows, int cols, int batch, int nt,
+                    uint64_t *cells_c, hipStream_t s) {
+    int rc = check_sizes(ctx, rows, cols, batch);
+    if (rc) return rc;
+    if ((rows | cols) & 1)
+        return fail(ctx, HSFLOW_ERR_ARG, "YUV 4:2:0 needs even rows and cols, not %dx%d", rows,
+                    cols);
+    if (nt < 1 || nt > HSFLOW_MAX_TIMES)
+        return fail(ctx, HSFLOW_ERR_ARG, "nt %d outside [1, %d]", nt, HSFLOW_MAX_TIMES);
+    if ((rc = check_cells(ctx, cells)) || (rc = check_cells(ctx, cells_c))) return rc;
+    const size_t n = (size_t)rows * cols * batch * nt;
+    const ByteRange in{cells, n * 8}, out{cells_c, n * 2};
+    if (!outputs_disjoint(&in, 1, &out, 1))
+        return fail(ctx, HSFLOW_ERR_ARG, "the chroma cells overlap the luma cells");
+    hipError_t e = hsflow::launch_cells_down(cells, rows, cols, batch * nt, cells_c, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "cells reduction launch");
+    return HSFLOW_OK;
+}
+
+// hsflow_flow_interp_yuv_device, hsflow_flow_interp_yuv_pj_device: what the chroma
+// adds to the grey call's checks (first, so that nothing has run when one
+// fails), flow_interp_impl on the luma planes, then KIY on the flows and counts
+// that call left in the workspace; S.projection = 1: KIYP on those and on the
+// cells KS left there
 int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma, const ChromaIO &C,
                          float rel, float abs_thr, const InterpOut &Y, void *ws, size_t ws_bytes,
                          hipStream_t s) {
@@ -1175,9 +1201,11 @@ int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma
     if (!luma.I0 || !luma.I1 || !C.c0 || !C.c1 || !Y.out || !C.out || !ws)
         return null_pointer(ctx);
     if ((rc = check_interp_args(ctx, Y.times, Y.nt, Y.dtype_out, false))) return rc;
+    if ((rc = check_projection(ctx, S.projection))) return rc;
     const bool fallback = fb_on(S.fb);
     if (fallback && (rc = check_fallback(ctx, S.fb))) return rc;
-    const InterpLayout L = interp_layout(S.rows, S.cols, S.batch, S.levels, 1, 0, fallback);
+    const InterpLayout L = interp_layout(S.rows, S.cols, S.batch, S.levels, 1,
+                                         S.projection ? Y.nt : 0, fallback);
     const size_t need = L.bytes + (pf_on(S.pf) ? pf_planes_bytes(S.rows, S.cols, S.batch) : 0);
     const size_t n = (size_t)S.rows * S.cols * S.batch, cb = chroma_bytes(S.rows, S.cols, S.batch);
     const ByteRange ins[5] = {{luma.I0, n}, {luma.I1, n}, {C.c0, cb}, {C.c1, cb}, {ws, need}};
@@ -1197,7 +1225,8 @@ int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma
     char *base = (char *)ws;
     const FlowsIn W{(const float *)(base + L.flow[0]), (const float *)(base + L.flow[1]),
                     (const float *)(base + L.flow[2]), (const float *)(base + L.flow[3]),
-                    nullptr, nullptr, nullptr};
+                    nullptr, nullptr,
+                    S.projection ? (const uint64_t *)(base + L.cells) : nullptr};
     return chroma_interp_run(ctx, C, S.rows, S.cols, S.batch, W,
                              fallback ? (const uint32_t *)(base + L.counts[0]) : nullptr,
                              fallback ? (const uint32_t *)(base + L.counts[1]) : nullptr, S.fb, s);
@@ -1205,11 +1234,13 @@ int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma
 
 // hsflow_flow_interp_yuv: flow_interp_host for packed 4:2:0 frames.  Each frame
 // goes up as it is, rows * 3 / 2 rows of cols bytes; the luma and the chroma of
-// a time come down into its packed host frame.
+// a time come down into its packed host frame.  projection < 0
+// (hsflow_flow_interp_yuv): none, and a context that has it on is refused; 0 or
+// 1 (hsflow_flow_interp_yuv_pj): that, whatever the context's setting.
 int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *f0,
                          const uint8_t *f1, int layout, float rel, float abs_thr,
-                         const float *times, int nt, void *const *out, int dtype_out,
-                         uint8_t *const *flags, uint32_t *trusted) {
+                         const float *times, int nt, int projection, void *const *out,
+                         int dtype_out, uint8_t *const *flags, uint32_t *trusted) {
     SolveSpec S = spec;
     const int rows = S.rows, cols = S.cols;
     if (ctx) ctx->last_cut = -1;
@@ -1219,6 +1250,7 @@ int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *
     if (rc) return rc;
     if (!f0 || !f1) return fail(ctx, HSFLOW_ERR_ARG, "null image");
     if ((rc = check_yuv_shape(ctx, layout, rows, cols, 1))) return rc;
+    if (projection >= 0 && (rc = check_projection(ctx, projection))) return rc;
     if (!out) return fail(ctx, HSFLOW_ERR_ARG, "null output");
     for (int k = 0; k < nt; ++k)
         if (!out[k] || (flags && !flags[k]))
@@ -1227,15 +1259,18 @@ int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *
         (rc = check_iteration_args(ctx, S)) || (rc = check_thresholds(ctx, rel, abs_thr)))
         return rc;
     if (!ctx) return fail(nullptr, HSFLOW_ERR_ARG, "null context");
-    if (S.projection)
+    if (projection >= 0)
+        S.projection = projection;
+    else if (S.projection)
         return fail(ctx, HSFLOW_ERR_ARG,
                     "the flow projection is not supported on YUV chroma: set the context's "
                     "projection to 0");
+    const int cell_nt = S.projection ? nt : 0;
     const size_t n = (size_t)rows * cols, es = elem_size(dtype_out);
     // d_out: the nt luma planes, the nt chroma frames, the nt flag planes, trusted
     const size_t yb = align_up(n * nt * es), cb = align_up(n / 2 * nt * es), flb = align_up(n * nt);
     const bool fb = fb_on(S.fb);
-    const size_t wsb = interp_layout(rows, cols, 1, S.levels, 1, 0, fb).bytes +
+    const size_t wsb = interp_layout(rows, cols, 1, S.levels, 1, cell_nt, fb).bytes +
                        (pf_on(S.pf) ? pf_planes_bytes(rows, cols, 1) : 0);
     char *in0, *in1;
     rc = stage_pair(ctx, f0, f1, 1, rows / 2 * 3, cols, (size_t)cols, (size_t)cols,
@@ -1252,7 +1287,7 @@ int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *
     rc = flow_interp_yuv_impl(ctx, S, Frames{in0, in1, HSFLOW_U8}, C, rel, abs_thr, Y, ctx->d_ws,
                               ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
-    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, 1, 0, fb);
+    const InterpLayout L = interp_layout(rows, cols, 1, S.levels, 1, cell_nt, fb);
     rc = predict_run(ctx, (const float *)((char *)ctx->d_ws + L.flow[2]),
                      (const float *)((char *)ctx->d_ws + L.flow[3]), rows, cols);
     if (rc) return rc;
@@ -2082,7 +2117,7 @@ int hsflow_chroma_interp_device(const uint8_t *c0, const uint8_t *c1, int layout
     DeviceGuard g((hipStream_t)stream);
     return chroma_interp_impl(nullptr, ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rows,
                               cols, batch, FlowsIn{uf, vf, ub, vb, nullptr, nullptr, nullptr},
-                              counts_f, counts_b, fb, (hipStream_t)stream);
+                              counts_f, counts_b, fb, false, (hipStream_t)stream);
 }
 
 size_t hsflow_flow_interp_yuv_workspace_bytes(int rows, int cols, int batch, int levels,
@@ -2117,9 +2152,67 @@ int hsflow_flow_interp_yuv(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1
                            int nt, void *const *out, int dtype_out, uint8_t *const *flags,
                            uint32_t *trusted) {
     const SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
-    return flow_interp_yuv_host(ctx, S, f0, f1, layout, rel, abs_thr, times, nt, out, dtype_out,
-                                flags, trusted);
+    return flow_interp_yuv_host(ctx, S, f0, f1, layout, rel, abs_thr, times, nt, -1, out,
+                                dtype_out, flags, trusted);
 }
+
+int hsflow_cells_down_device(const uint64_t *cells, int rows, int cols, int batch, int nt,
+                             uint64_t *cells_c, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return cells_down_impl(nullptr, cells, rows, cols, batch, nt, cells_c, (hipStream_t)stream);
+}
+
+int hsflow_chroma_interp_proj_device(const uint8_t *c0, const uint8_t *c1, int layout, int rows,
+                                     int cols, int batch, const float *uf, const float *vf,
+                                     const float *ub, const float *vb, const uint64_t *cells,
+                                     const uint32_t *counts_f, const uint32_t *counts_b,
+                                     const hsflow_fallback *fb, const float *times, int nt,
+                                     void *out_c, int dtype_out, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return chroma_interp_impl(nullptr, ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rows,
+                              cols, batch, FlowsIn{uf, vf, ub, vb, nullptr, nullptr, cells},
+                              counts_f, counts_b, fb, true, (hipStream_t)stream);
+}
+
+size_t hsflow_flow_interp_yuv_pj_workspace_bytes(int rows, int cols, int batch, int levels,
+                                                 int nt, int projection, int fallback) {
+    if (!sizes_ok(rows, cols, batch) || (rows | cols) & 1 || levels < 1 ||
+        levels > HSFLOW_MAX_LEVELS || nt < 1 || nt > HSFLOW_MAX_TIMES ||
+        (projection != 0 && projection != 1))
+        return 0;
+    return interp_layout(rows, cols, batch, levels, 1, projection ? nt : 0, fallback != 0).bytes;
+}
+
+int hsflow_flow_interp_yuv_pj_device(const uint8_t *y0, const uint8_t *c0, const uint8_t *y1,
+                                     const uint8_t *c1, int layout, int rows, int cols, int batch,
+                                     int levels, int finest, int warps, int median, int window,
+                                     int iters, float alpha, float rel, float abs_thr,
+                                     const float *times, int nt, int projection, void *out_y,
+                                     void *out_c, int dtype_out, uint8_t *flags,
+                                     uint32_t *trusted, uint8_t *cut, const hsflow_prefilter *pf,
+                                     const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                     const hsflow_fallback *fb, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,  cols,  batch, levels, finest, warps,      median, window,
+                      iters, alpha, pf,    sm,     init,   projection, fb};
+    return flow_interp_yuv_impl(nullptr, S, Frames{y0, y1, HSFLOW_U8},
+                                ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rel, abs_thr,
+                                InterpOut{times, nt, out_y, dtype_out, flags, trusted, cut},
+                                workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_interp_yuv_pj(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1, int layout,
+                              int rows, int cols, int levels, int warps, int median, int window,
+                              int iters, double alpha, float rel, float abs_thr,
+                              const float *times, int nt, int projection, void *const *out,
+                              int dtype_out, uint8_t *const *flags, uint32_t *trusted) {
+    const SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
+    return flow_interp_yuv_host(ctx, S, f0, f1, layout, rel, abs_thr, times, nt,
+                                projection < 0 ? 2 : projection, out, dtype_out, flags, trusted);
+}
+
+int hsflow_chroma_interp_proj_blocks_per_cu(void) { return hsflow::chroma_proj_blocks_per_cu(); }
 
 int hsflow_chroma_interp_blocks_per_cu(void) { return hsflow::chroma_blocks_per_cu(); }
 

@@ -160,9 +160,18 @@ hipError_t launch_chroma_interp(const uint8_t *c0, const uint8_t *c1, int layout
                                 const float *ub, const float *vb, const uint32_t *counts_f,
                                 const uint32_t *counts_b, uint64_t min_consistent, int mode,
                                 const float *times, int nt, void *out, bool out_u8,
-                                hipStream_t s);
+                                hipStream_t s, const uint64_t *cells = nullptr);
 // the cap of KIY's grid, in blocks per CU
 int chroma_blocks_per_cu();
+// KSD (hsflow_yuv.hip): KS's cells [planes][rows][cols] (planes = batch * nt)
+// reduced to the chroma grid, cells_c [planes][rows / 2][cols / 2]: the 64-bit
+// minimum of each 2 x 2 block, the winner's index re-coded to the chroma grid.
+// KIYP: launch_chroma_interp with `cells` (KS's, [batch][nt][rows][cols]) reads
+// each sample's time-t flow through that minimum, taken in registers.
+hipError_t launch_cells_down(const uint64_t *cells, int rows, int cols, int planes,
+                             uint64_t *cells_c, hipStream_t s);
+// the cap of KIYP's grid, in blocks per CU
+int chroma_proj_blocks_per_cu();
 // how KIY fetches the two adjacent taps of an NV12 row: as four bytes (on == 0,
 // default) or as one unaligned dword; same bits.  Returns the previous setting.
 int set_chroma_nv12_wide_loads(int on);

@@ -442,7 +442,7 @@ def _bgr_frame(src, i: int) -> np.ndarray:
 def interpolate_sequence_yuv(src, factor: int, levels: int, warps: int, window: int, iters: int,
                              alpha: float, median: int = 0, context=None, prefilter=None,
                              smoothness=None, temporal: bool = False, finest=None, fallback=None,
-                             cuts=None):
+                             cuts=None, projection=None):
     """interpolate_sequence for a 4:2:0 source: a generator of (len(src) - 1) *
     factor + 1 packed I420 frames (uint8, rows * cols * 3 / 2 bytes).  `src`
     has `rows`, `cols` and `read_yuv(i)` (Y4MVideo on a C420* stream).  Every
@@ -450,8 +450,9 @@ def interpolate_sequence_yuv(src, factor: int, levels: int, warps: int, window: 
     between two come from one yuv.interpolate_yuv call per pair: the solve runs
     on the luma planes as they are, the chroma follows the same flows on its
     own grid.  context, prefilter, smoothness, temporal, finest, fallback and
-    cuts as in interpolate_sequence; there is no projection (it is not supported
-    on chroma)."""
+    cuts as in interpolate_sequence.  projection None: none (a context with the
+    projection on is refused); 0 or 1: yuv.interpolate_yuv(projection=), luma and
+    chroma through the same winners."""
     factor = int(factor)
     if factor < 1:
         raise ValueError("factor must be at least 1")
@@ -478,7 +479,8 @@ def interpolate_sequence_yuv(src, factor: int, levels: int, warps: int, window: 
                 mid = yuv.interpolate_yuv(ctx, prev, nxt, times, levels, warps, window, iters,
                                           alpha, rows, cols, median=median, out_dtype=np.uint8,
                                           prefilter=prefilter, smoothness=smoothness,
-                                          finest=finest, fallback=fallback)
+                                          finest=finest, fallback=fallback,
+                                          projection=projection)
                 if cuts is not None and ctx.last_cut:
                     cuts.append(i)
                 for k in range(len(times)):

@@ -351,6 +351,18 @@ def _prototypes():
                                    + [fp, i, vpp, i, vpp, vp]),
         "hsflow_chroma_interp_blocks_per_cu": (i, []),
         "hsflow_set_chroma_nv12_loads": (i, [i]),
+        # ... with the flow projection: KSD, KIYP, the fused and the host call
+        # with `projection` after nt
+        "hsflow_cells_down_device": (i, [vp] + shape + [i, vp, vp]),
+        "hsflow_chroma_interp_proj_device": (i, [vp, vp, i] + shape + flows + [vp, vp, vp] + fb
+                                             + [fp, i, vp, i, vp]),
+        "hsflow_flow_interp_yuv_pj_workspace_bytes": (sz, shape + [i, i, i, i]),
+        "hsflow_flow_interp_yuv_pj_device": (i, [vp, vp, vp, vp, i] + shape + solve_lv + thresholds
+                                             + [fp, i, i, vp, vp, i, vp, vp, vp] + pf + sm + init
+                                             + fb + tail),
+        "hsflow_flow_interp_yuv_pj": (i, [vp, vp, vp, i, i, i] + solve_d + thresholds
+                                      + [fp, i, i, vpp, i, vpp, vp]),
+        "hsflow_chroma_interp_proj_blocks_per_cu": (i, []),
         "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
         "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
         "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),

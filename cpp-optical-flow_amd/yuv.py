@@ -12,8 +12,17 @@ A packed frame is a uint8 array of rows * cols * 3 // 2 bytes, the luma plane
 followed by the chroma (I420: the U plane, then the V plane; NV12: U and V
 interleaved); rows and cols are the luma's and even.  On the device luma
 [B, rows, cols] and chroma (I420 [B, 2, rows / 2, cols / 2], NV12 [B, rows / 2,
-cols / 2, 2]) are separate tensors.  The flow projection is not supported on
-chroma; every other option of the BGR calls is.
+cols / 2, 2]) are separate tensors.
+
+With the flow projection (projection.py) the chroma reads its time-t flow
+through the luma's own winners, so that luma and chroma follow the same surface
+at a motion boundary: chroma_interp_proj_device (KIYP) is, bit for bit,
+temporal.downflow_device on both flow pairs, cells_down_device (KSD) on
+projection.project_device's cells of the luma, and
+projection.frame_interp_device on the U and on the V planes, in one launch.
+flow_interp_yuv_proj_device, interpolate_yuv(projection=) and
+frames.interpolate_sequence_yuv(projection=) are the fused, the host and the
+clip form.
 
 Everything here calls the HIP path in libhsflow.so through hsflow's front ends.
 """
@@ -174,6 +183,85 @@ def chroma_interp_device(c0, c1, uf, vf, ub, vb, times, layout=YUV_I420, counts_
     return out
 
 
+def proj_blocks_per_cu() -> int:
+    """The cap of KIYP's grid in blocks per compute unit
+    (hsflow_chroma_interp_proj_blocks_per_cu); tiles as KIY's."""
+    return int(hsflow.lib().hsflow_chroma_interp_proj_blocks_per_cu())
+
+
+def _luma_cells(cells, dims, nt, device, lead):
+    """KS's cells of the luma, int64 [B, nt, rows, cols] (no B for a single
+    frame's chroma), checked."""
+    rows, cols, _ = dims
+    import projection as _projection
+    return _projection._cells(cells, lead + (rows, cols), nt, device)
+
+
+def cells_down_device(cells, cells_c=None, stream=None):
+    """projection.project_device's cells of the luma, int64 [B, nt, rows, cols]
+    or [nt, rows, cols] (rows, cols even), reduced to the chroma grid
+    (hsflow_cells_down_device, KSD): the unsigned 64-bit minimum of each 2 x 2
+    block, the winner's source index re-coded to the chroma grid; a chroma cell
+    is empty only where all four are.  Returns cells_c, int64 [..., rows / 2,
+    cols / 2], for projection.frame_interp_device on a chroma plane.  One
+    launch.  Stream-ordered."""
+    if torch is None or not isinstance(cells, torch.Tensor) or cells.dtype != torch.int64 or \
+            cells.dim() not in (3, 4) or not cells.is_cuda or not cells.is_contiguous():
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "cells: need a contiguous int64 CUDA "
+                                 "tensor [B, nt, rows, cols] or [nt, rows, cols]")
+    rows, cols = cells.shape[-2:]
+    _even(rows, cols)
+    batch = cells.shape[0] if cells.dim() == 4 else 1
+    nt = cells.shape[-3]
+    shape = tuple(cells.shape[:-2]) + (rows // 2, cols // 2)
+    cells_c = hsflow._check_output(True if cells_c is None else cells_c, shape, torch.int64,
+                                   cells.device, "cells_c")
+    hsflow._device_call("hsflow_cells_down_device", cells.device, stream, cells.data_ptr(),
+                        int(rows), int(cols), int(batch), int(nt), cells_c.data_ptr())
+    return cells_c
+
+
+def chroma_interp_proj_device(c0, c1, uf, vf, ub, vb, times, cells, layout=YUV_I420,
+                              counts_f=None, counts_b=None, fallback=None, out=None,
+                              out_dtype=None, stream=None):
+    """chroma_interp_device with each sample's time-t flow read through `cells`,
+    projection.project_device's tensor of the luma for the same `times`
+    (hsflow_chroma_interp_proj_device, KIYP): temporal.downflow_device of both
+    flow pairs, cells_down_device and projection.frame_interp_device on the U
+    and on the V planes, bit for bit, in one launch; a sample whose four luma
+    cells are empty is chroma_interp_device's.  Every other argument as there.
+    Returns out.  Stream-ordered."""
+    lay = _layout(layout)
+    dims = _chroma_pair(c0, c1, lay)
+    hsflow._check_planes(dims, uf=uf, vf=vf, ub=ub, vb=vb)
+    tm = hsflow._times_array(times)
+    if cells is None:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "cells: need the luma's cells")
+    cells = _luma_cells(cells, dims, len(tm), c0.device, tuple(c0.shape[:-3]))
+    out = _chroma_out(c0, len(tm), out, out_dtype)
+    keep, fb = hsflow._option(hsflow._Fallback, fallback)
+    counts = [None, None]
+    if fallback is not None:
+        import fallback as _fallback
+        counts = [_fallback._counts(c, dims[2], c0.device, n)
+                  for c, n in ((counts_f, "counts_f"), (counts_b, "counts_b"))]
+    hsflow._device_call("hsflow_chroma_interp_proj_device", c0.device, stream, c0.data_ptr(),
+                        c1.data_ptr(), lay, *dims, uf.data_ptr(), vf.data_ptr(), ub.data_ptr(),
+                        vb.data_ptr(), cells.data_ptr(), *counts, fb, tm, len(tm),
+                        out.data_ptr(), hsflow._out_code(out))
+    return out
+
+
+def flow_interp_proj_workspace_bytes(rows: int, cols: int, batch: int, levels: int, nt: int,
+                                     projection: int = 1, fallback: bool = False) -> int:
+    """The workspace of flow_interp_yuv_proj_device
+    (hsflow_flow_interp_yuv_pj_workspace_bytes): flow_interp_workspace_bytes
+    plus, with projection 1, the cells of nt times; a prefilter's planes come on
+    top (hsflow.prefilter_planes_bytes).  0 for a bad shape, nt or projection."""
+    return int(hsflow.lib().hsflow_flow_interp_yuv_pj_workspace_bytes(
+        rows, cols, batch, levels, nt, projection, 1 if fallback else 0))
+
+
 def flow_interp_workspace_bytes(rows: int, cols: int, batch: int, levels: int,
                                 fallback: bool = False) -> int:
     """The workspace of flow_interp_yuv_device
@@ -199,7 +287,37 @@ def flow_interp_yuv_device(y0, c0, y1, c1, times, levels: int, warps: int, windo
     init and cut as in hsflow.flow_interp_bgr_device and
     temporal.flow_interp_device; there is no projection.  Returns (out_y, out_c,
     flags, trusted), and cut behind them where it was asked for.
-    Stream-ordered."""
+    Stream-ordered.  flow_interp_yuv_proj_device is the form with a projection."""
+    return _flow_interp_yuv(None, y0, c0, y1, c1, times, levels, warps, window, iters, alpha,
+                            layout, median, rel, abs, out_y, out_c, out_dtype, flags, trusted,
+                            workspace, stream, prefilter, smoothness, finest, fallback, init, cut)
+
+
+def flow_interp_yuv_proj_device(y0, c0, y1, c1, times, levels: int, warps: int, window: int,
+                                iters: int, alpha: float, layout=YUV_I420, median: int = 0,
+                                rel: float = hsflow.CONSISTENCY_REL,
+                                abs: float = hsflow.CONSISTENCY_ABS, out_y=None, out_c=None,
+                                out_dtype=None, flags=None, trusted=None, workspace=None,
+                                stream=None, prefilter=None, smoothness=None, finest: int = 0,
+                                fallback=None, init=None, cut=None, projection: int = 1):
+    """flow_interp_yuv_device with a projection
+    (hsflow_flow_interp_yuv_pj_device).  projection = 0: that call's launches
+    and bits.  1: hsflow.flow_interp_device(projection=1) on the luma -- out_y,
+    flags (FLAG_HOLE included), trusted and cut are its -- and
+    chroma_interp_proj_device on the flows, cells and counts it leaves in the
+    workspace (flow_interp_proj_workspace_bytes).  Returns as
+    flow_interp_yuv_device.  Stream-ordered."""
+    return _flow_interp_yuv(int(projection), y0, c0, y1, c1, times, levels, warps, window, iters,
+                            alpha, layout, median, rel, abs, out_y, out_c, out_dtype, flags,
+                            trusted, workspace, stream, prefilter, smoothness, finest, fallback,
+                            init, cut)
+
+
+def _flow_interp_yuv(projection, y0, c0, y1, c1, times, levels, warps, window, iters, alpha,
+                     layout, median, rel, abs, out_y, out_c, out_dtype, flags, trusted, workspace,
+                     stream, prefilter, smoothness, finest, fallback, init, cut):
+    """Both fused device calls: projection None is hsflow_flow_interp_yuv_device,
+    else hsflow_flow_interp_yuv_pj_device with that projection."""
     lay = _layout(layout)
     dims = hsflow._frame_pair(y0, y1)
     if y0.dtype != torch.uint8:
@@ -215,15 +333,23 @@ def flow_interp_yuv_device(y0, c0, y1, c1, times, levels: int, warps: int, windo
         raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "out_y and out_c differ in dtype")
     pf = hsflow._option(hsflow.Prefilter, prefilter)[1]
     sm = hsflow._option(hsflow.Smoothness, smoothness)[1]
-    workspace = hsflow._workspace(workspace, y0.device, hsflow.flow_interp_workspace_bytes, *dims,
-                                  levels, prefilter=prefilter, fallback=fallback)
+    size_fn = hsflow.flow_interp_workspace_bytes
+    if projection == 1:
+        def size_fn(rows, cols, batch, lv):
+            return flow_interp_proj_workspace_bytes(rows, cols, batch, lv, len(tm))
+    workspace = hsflow._workspace(workspace, y0.device, size_fn, *dims, levels,
+                                  prefilter=prefilter, fallback=fallback)
     _, _, start = hsflow._init_entry("hsflow_flow_interp", init, dims, 1)
     cut = hsflow._check_output(cut, (dims[2],), torch.uint8, y0.device, "cut")
     keep, fb = hsflow._option(hsflow._Fallback, fallback)
-    hsflow._device_call("hsflow_flow_interp_yuv_device", y0.device, stream, y0.data_ptr(),
+    name = "hsflow_flow_interp_yuv_device" if projection is None else \
+        "hsflow_flow_interp_yuv_pj_device"
+    proj = () if projection is None else (projection,)
+    hsflow._device_call(name, y0.device, stream, y0.data_ptr(),
                         c0.data_ptr(), y1.data_ptr(), c1.data_ptr(), lay, *dims,
                         *hsflow._solve_args(levels, warps, median, window, iters, alpha, finest),
-                        float(rel), float(abs), tm, len(tm), out_y.data_ptr(), out_c.data_ptr(),
+                        float(rel), float(abs), tm, len(tm), *proj, out_y.data_ptr(),
+                        out_c.data_ptr(),
                         hsflow._out_code(out_y), hsflow._ptr(flags), hsflow._ptr(trusted),
                         hsflow._ptr(cut), pf, sm, *start, fb, *hsflow._ws_args(workspace))
     res = (out_y, out_c, flags, trusted)
@@ -234,7 +360,7 @@ def interpolate_yuv(ctx, f0, f1, times, levels: int, warps: int, window: int, it
                     alpha: float, rows: int, cols: int, layout=YUV_I420, median: int = 0,
                     rel: float = hsflow.CONSISTENCY_REL, abs: float = hsflow.CONSISTENCY_ABS,
                     out_dtype=np.uint8, with_flags: bool = False, prefilter=None,
-                    smoothness=None, finest=None, fallback=None):
+                    smoothness=None, finest=None, fallback=None, projection=None):
     """The packed frames at `times` between the packed 8-bit 4:2:0 frames f0 and
     f1 (uint8, rows * cols * 3 / 2 bytes each; rows, cols the luma's) on the
     hsflow.Context `ctx` (hsflow_flow_interp_yuv): the luma through
@@ -243,8 +369,10 @@ def interpolate_yuv(ctx, f0, f1, times, levels: int, warps: int, window: int, it
     same layout, or with_flags: (frames, flags, trusted) -- the luma's, flags
     uint8 [len(times), rows, cols].  prefilter, smoothness, finest and fallback
     as in Context.interpolate_bgr; the context's sequence mode is honoured and
-    Context.last_cut set.  A context with the projection on is refused: the
-    projection is not supported on chroma."""
+    Context.last_cut set.  projection None: no projection, and a context with
+    the projection on is refused; 0 or 1: that, whatever the context's setting
+    (hsflow_flow_interp_yuv_pj: the luma through the projected path, the chroma
+    through KIYP)."""
     lay = _layout(layout)
     n = frame_bytes(rows, cols)
     frames = []
@@ -264,9 +392,11 @@ def interpolate_yuv(ctx, f0, f1, times, levels: int, warps: int, window: int, it
     vp = ctypes.c_void_p
     planes = (vp * nt)(*[out[k].ctypes.data for k in range(nt)])
     fplanes = (vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
-    ctx._call_with(prefilter, smoothness, "hsflow_flow_interp_yuv", frames[0].ctypes.data,
+    name = "hsflow_flow_interp_yuv" if projection is None else "hsflow_flow_interp_yuv_pj"
+    proj = () if projection is None else (int(projection),)
+    ctx._call_with(prefilter, smoothness, name, frames[0].ctypes.data,
                    frames[1].ctypes.data, lay, int(rows), int(cols),
                    *hsflow._solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                   float(abs), tm, nt, planes, hsflow._dtype_code(out), fplanes,
+                   float(abs), tm, nt, *proj, planes, hsflow._dtype_code(out), fplanes,
                    trusted.ctypes.data if with_flags else None, finest=finest, fallback=fallback)
     return (out, flags, trusted) if with_flags else out

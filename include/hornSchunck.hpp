@@ -120,10 +120,13 @@ class hornSchunck {
     // cv::cvtColor(COLOR_BGR2YUV_I420) gives and COLOR_YUV2BGR_I420 / _NV12
     // takes -- in the same layout (hsflow.h, hsflow_flow_interp_yuv): no colour
     // conversion, the luma is the grey frame.  frames[k] is created like the
-    // inputs.  The settings above apply; with the projection on the call throws.
+    // inputs.  The settings above apply.  projection -1: none, and with the
+    // projection setting on the call throws; 0 or 1: that, whatever the setting
+    // (hsflow_flow_interp_yuv_pj).
     void getFrameInterpYuv(const cv::Mat &imagePrev, const cv::Mat &imageNext,
                            const std::vector<float> &times, int levels, int warps, int median,
-                           std::vector<cv::Mat> &frames, int layout = HSFLOW_YUV_I420) {
+                           std::vector<cv::Mat> &frames, int layout = HSFLOW_YUV_I420,
+                           int projection = -1) {
         sync_params();
         if (imagePrev.empty() || imageNext.empty()) CV_Error(cv::Error::StsBadArg, "empty image");
         if (imagePrev.type() != CV_8UC1 || imageNext.type() != CV_8UC1)
@@ -138,7 +141,7 @@ class hornSchunck {
         std::vector<std::vector<uint8_t>> packed;
         guarded([&] {
             impl_.getFrameInterpYuv(imagePrev.data, imageNext.data, layout, rows, cols, times,
-                                    levels, warps, median, packed);
+                                    levels, warps, median, packed, nullptr, projection);
         });
         frames.resize(packed.size());
         for (size_t k = 0; k < packed.size(); ++k) {

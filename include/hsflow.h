@@ -1347,9 +1347,10 @@ int hsflow_ctx_last_cut(const hsflow_ctx *ctx);
  * hsflow_fallback_min_consistent(rows, cols, min_share), the luma's size.  A
  * pair that fails gets, per chroma byte, what hsflow_frame_fallback_device
  * writes for a grey U8 plane; a pair that passes keeps the interpolated chroma.
- * The flow projection is not supported on chroma: luma projected and chroma not
- * would fringe at motion boundaries, so the calls below take no projection and
- * the host call refuses a context that has it on. */
+ * Luma projected and chroma not would fringe at motion boundaries, so the calls
+ * below take no projection and the host call refuses a context that has it on;
+ * the projected forms are further down ("YUV 4:2:0 with the flow projection":
+ * hsflow_flow_interp_yuv_pj_device, hsflow_flow_interp_yuv_pj). */
 #define HSFLOW_HAS_YUV 1
 #define HSFLOW_YUV_I420 1
 #define HSFLOW_YUV_NV12 2
@@ -1379,6 +1380,7 @@ int hsflow_chroma_interp_device(const uint8_t *c0, const uint8_t *c1, int layout
  * are that call's, bit for bit -- and then hsflow_chroma_interp_device on the
  * flows and counts that call leaves in the workspace.  out_y: [batch][nt] luma
  * planes, out_c: [batch][nt] chroma frames, both of dtype_out (U8 or F32).  The
+ * form with a `projection` argument is hsflow_flow_interp_yuv_pj_device.  The
  * workspace is the grey call's: hsflow_flow_interp_yuv_workspace_bytes (fallback
  * != 0: with the counts of a fallback; 0 for a bad shape), a prefilter's planes
  * behind it, as ever.  No output may overlap an input, the workspace or another
@@ -1402,7 +1404,8 @@ int hsflow_flow_interp_yuv_device(const uint8_t *y0, const uint8_t *c0, const ui
  * prefilter, smoothness, finest level, sequence mode and fallback are honoured
  * as by hsflow_flow_interp_bgr, and hsflow_ctx_last_cut is set; the result
  * equals the device call's bit for bit.  A context with the projection on is
- * HSFLOW_ERR_ARG: the projection is not supported on chroma. */
+ * HSFLOW_ERR_ARG: this call projects nothing; hsflow_flow_interp_yuv_pj takes the
+ * projection as an argument. */
 int hsflow_flow_interp_yuv(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1, int layout,
                            int rows, int cols, int levels, int warps, int median, int window,
                            int iters, double alpha, float rel, float abs_thr, const float *times,
@@ -1415,6 +1418,88 @@ int hsflow_flow_interp_yuv(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1
  * unaligned 32-bit load (1); same bits.  Returns the previous setting. */
 int hsflow_chroma_interp_blocks_per_cu(void);
 int hsflow_set_chroma_nv12_loads(int wide);
+
+/* ---- YUV 4:2:0 with the flow projection ---------------------------------------
+ * The chroma reads its time-t flow through the luma's own winners, so that both
+ * follow the same surface at a motion boundary.  `cells` is KS's plane
+ * [batch][nt][rows][cols] from hsflow_flow_project_device on the luma frames
+ * the solve ran on; rc = rows / 2, cc = cols / 2.
+ *
+ * KSD, the reduction: chroma cell (yc, xc) of a pair and time is the unsigned
+ * 64-bit minimum of the luma cells (2 yc + {0, 1}, 2 xc + {0, 1}).  All ones is
+ * the largest word: a hole loses to every candidate, and a chroma cell is a hole
+ * only where all four are.  The winner keeps its upper word and its direction
+ * bit; its source index p is clamped to rows * cols - 1, as KIP clamps a foreign
+ * cell, and re-coded to the chroma grid, (p / cols >> 1) * cc + (p % cols >> 1).
+ * The minimum comes first and the re-coding after it, so ties are the luma's:
+ * the lower cost, then direction 0, then the lower luma index.
+ *
+ * The chroma of the frame at time t is, by definition and bit for bit,
+ *   hsflow_downflow_device on (uf, vf) and on (ub, vb),
+ *   hsflow_cells_down_device, and
+ *   hsflow_frame_interp_proj_device (U8 frames, NULL masks, flags and trusted)
+ *     with those flows and cells on the U planes, rc x cc, and on the V planes.
+ * So a sample's time-t flow is the mean flow of the 2 x 2 luma block that holds
+ * the winner, negated behind the mean for direction 1; a hole gets
+ * hsflow_chroma_interp_device's value exactly.  No flags and no trusted count;
+ * with a fallback a failed pair gets KF's value, as in
+ * hsflow_chroma_interp_device. */
+#define HSFLOW_HAS_YUV_PROJECTION 1
+
+/* KSD: cells [batch][nt][rows][cols] -> cells_c [batch][nt][rc][cc], both
+ * 8-byte aligned (a cell plane on a 16-byte boundary is read in 16-byte loads;
+ * same words) and disjoint; rows and cols even, nt in 1 .. HSFLOW_MAX_TIMES.
+ * All arguments are checked before any device work.  One launch.
+ * Stream-ordered, no workspace, never allocates or synchronises, capturable. */
+int hsflow_cells_down_device(const uint64_t *cells, int rows, int cols, int batch, int nt,
+                             uint64_t *cells_c, void *stream);
+
+/* KIYP: hsflow_chroma_interp_device with `cells` (KS's, of the luma, 8-byte
+ * aligned) behind the flows: one launch for the three steps above on both
+ * channels, all times and the whole batch; the chroma cells never reach memory.
+ * Every other argument, the checks and the contract are that call's; out_c must
+ * be disjoint from the cells too. */
+int hsflow_chroma_interp_proj_device(const uint8_t *c0, const uint8_t *c1, int layout, int rows,
+                                     int cols, int batch, const float *uf, const float *vf,
+                                     const float *ub, const float *vb, const uint64_t *cells,
+                                     const uint32_t *counts_f, const uint32_t *counts_b,
+                                     const hsflow_fallback *fb, const float *times, int nt,
+                                     void *out_c, int dtype_out, void *stream);
+
+/* hsflow_flow_interp_yuv_device with `projection` after nt.  0: exactly that
+ * call's launches and bits.  1: hsflow_flow_interp_fb_device with projection 1
+ * on the luma -- out_y, flags (bit 16 for a hole), trusted and cut are that
+ * call's -- and then hsflow_chroma_interp_proj_device on the flows, cells and
+ * counts it leaves in the workspace.  Any other value is HSFLOW_ERR_ARG.  The
+ * workspace: hsflow_flow_interp_yuv_pj_workspace_bytes (0 for a bad shape, nt or
+ * projection), a prefilter's planes behind it. */
+size_t hsflow_flow_interp_yuv_pj_workspace_bytes(int rows, int cols, int batch, int levels,
+                                                 int nt, int projection, int fallback);
+int hsflow_flow_interp_yuv_pj_device(const uint8_t *y0, const uint8_t *c0, const uint8_t *y1,
+                                     const uint8_t *c1, int layout, int rows, int cols, int batch,
+                                     int levels, int finest, int warps, int median, int window,
+                                     int iters, float alpha, float rel, float abs_thr,
+                                     const float *times, int nt, int projection, void *out_y,
+                                     void *out_c, int dtype_out, uint8_t *flags,
+                                     uint32_t *trusted, uint8_t *cut, const hsflow_prefilter *pf,
+                                     const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                     const hsflow_fallback *fb, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
+/* hsflow_flow_interp_yuv with an explicit `projection` (0 or 1, else
+ * HSFLOW_ERR_ARG) after nt; the context's projection setting is not consulted.
+ * Prefilter, smoothness, finest level, sequence mode and fallback are
+ * honoured and hsflow_ctx_last_cut is set, as by that call; the result equals
+ * hsflow_flow_interp_yuv_pj_device's bit for bit. */
+int hsflow_flow_interp_yuv_pj(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1, int layout,
+                              int rows, int cols, int levels, int warps, int median, int window,
+                              int iters, double alpha, float rel, float abs_thr,
+                              const float *times, int nt, int projection, void *const *out,
+                              int dtype_out, uint8_t *const *flags, uint32_t *trusted);
+
+/* The cap of KIYP's grid in blocks per compute unit (tiles of 512 chroma
+ * samples of one pair, striding, as KIY). */
+int hsflow_chroma_interp_proj_blocks_per_cu(void);
 
 /* ---- host utilities on the path to the hot loop ------------------------ */
 

@@ -158,13 +158,16 @@ class Context {
     // flows on its own grid; no colour conversion.  frames[k]: the frame at
     // times[k] in the same layout; flags[k]: rows * cols HSFLOW_INTERP_* bytes,
     // the luma's.  The context's prefilter, smoothness, finest level, sequence
-    // mode and fallback apply, lastCut() is set; with the projection on the
-    // call throws (it is not supported on chroma).
+    // mode and fallback apply, lastCut() is set.  projection -1: none, and on
+    // a context with the projection on the call throws; 0 or 1: that, whatever
+    // the context's setting (hsflow_flow_interp_yuv_pj: the chroma reads its
+    // time-t flow through the luma's winners).
     void getFrameInterpYuv(const uint8_t *prev, const uint8_t *next, int layout, int rows,
                            int cols, const std::vector<float> &times, int levels, int warps,
                            int median, int windowSize, int maxIterations, double alpha,
                            std::vector<std::vector<uint8_t>> &frames,
-                           std::vector<std::vector<uint8_t>> *flags = nullptr) {
+                           std::vector<std::vector<uint8_t>> *flags = nullptr,
+                           int projection = -1) {
         if (!prev || !next) throw Error(HSFLOW_ERR_ARG, "empty image");
         if (rows < 2 || cols < 2 || rows % 2 || cols % 2)
             throw Error(HSFLOW_ERR_ARG, "YUV 4:2:0 needs even rows and cols");
@@ -178,10 +181,19 @@ class Context {
             out[k] = frames[k].data();
             if (flags) (*flags)[k].resize(n), fl[k] = (*flags)[k].data();
         }
-        check(hsflow_flow_interp_yuv(ctx_, prev, next, layout, rows, cols, levels, warps, median,
-                                     windowSize, maxIterations, alpha, HSFLOW_CONSISTENCY_REL,
-                                     HSFLOW_CONSISTENCY_ABS, times.data(), (int)times.size(),
-                                     out.data(), HSFLOW_U8, flags ? fl.data() : nullptr, nullptr));
+        if (projection < 0) {
+            check(hsflow_flow_interp_yuv(ctx_, prev, next, layout, rows, cols, levels, warps,
+                                         median, windowSize, maxIterations, alpha,
+                                         HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS,
+                                         times.data(), (int)times.size(), out.data(), HSFLOW_U8,
+                                         flags ? fl.data() : nullptr, nullptr));
+            return;
+        }
+        check(hsflow_flow_interp_yuv_pj(ctx_, prev, next, layout, rows, cols, levels, warps,
+                                        median, windowSize, maxIterations, alpha,
+                                        HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS,
+                                        times.data(), (int)times.size(), projection, out.data(),
+                                        HSFLOW_U8, flags ? fl.data() : nullptr, nullptr));
     }
 
   private:
@@ -402,9 +414,10 @@ class HornSchunck {
     void getFrameInterpYuv(const uint8_t *prev, const uint8_t *next, int layout, int rows,
                            int cols, const std::vector<float> &times, int levels, int warps,
                            int median, std::vector<std::vector<uint8_t>> &frames,
-                           std::vector<std::vector<uint8_t>> *flags = nullptr) {
+                           std::vector<std::vector<uint8_t>> *flags = nullptr,
+                           int projection = -1) {
         ctx().getFrameInterpYuv(prev, next, layout, rows, cols, times, levels, warps, median,
-                                windowSize, maxIterations, alpha, frames, flags);
+                                windowSize, maxIterations, alpha, frames, flags, projection);
     }
 
     // Raw form for callers that own output rows (cv::Mat adapter): dtype_out
