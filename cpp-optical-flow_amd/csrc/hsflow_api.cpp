@@ -557,6 +557,7 @@ int elem_size(int dtype) {
     case HSFLOW_F32: return 4;
     case HSFLOW_F64: return 8;
     case HSFLOW_F16: return 2;
+    case HSFLOW_U16: return 2;
     default: return 0;
     }
 }
@@ -701,7 +702,8 @@ int check_host_args(hsflow_ctx *ctx, const void *I0, const void *I1, int dtype_i
     if (!I0 || !I1) return fail(ctx, HSFLOW_ERR_ARG, "null image");
     if (!sizes_ok(rows, cols, 1))
         return fail(ctx, HSFLOW_ERR_ARG, "bad size %dx%d", rows, cols);
-    const int es = elem_size(dtype_in);
+    // 16-bit frames enter through the YUV 4:2:0 calls only
+    const int es = dtype_in == HSFLOW_U16 ? 0 : elem_size(dtype_in);
     if (!es) return fail(ctx, HSFLOW_ERR_ARG, "unsupported input dtype %d", dtype_in);
     if (step0 < (size_t)cols * es || step1 < (size_t)cols * es)
         return fail(ctx, HSFLOW_ERR_ARG, "input steps %zu, %zu < row bytes %zu", step0, step1,
@@ -741,14 +743,20 @@ int build_levels(hsflow_ctx *ctx, const Frames &fr, int rows, int cols, int batc
                  const PyrLayout &L, void *ws, hipStream_t s) {
     if (L.levels <= 1) return HSFLOW_OK;
     char *base = (char *)ws;
-    // integrality of each pair (K1's flag at level 0) decides the rounding
-    // of every level; saved because each level's K1 rewrites the flags
-    int rc = gradients_impl(ctx, fr, rows, cols, batch, nullptr, nullptr, nullptr, ws,
-                            L.jac_bytes, s);
-    if (rc) return rc;
     uint32_t *intf = (uint32_t *)(base + L.flags_off);
-    HIP_TRY(ctx, hipMemcpyAsync(intf, carve(ws, rows, cols, batch).flags, (size_t)batch * 4,
-                                hipMemcpyDeviceToDevice, s));
+    if (fr.dtype == HSFLOW_U16) {
+        // K1 has no 16-bit frames, and a 16-bit pair is never treated as 8-bit:
+        // a non-zero flag for every pair, the levels unrounded
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)intf, 1, (size_t)batch, s));
+    } else {
+        // integrality of each pair (K1's flag at level 0) decides the rounding
+        // of every level; saved because each level's K1 rewrites the flags
+        int rc = gradients_impl(ctx, fr, rows, cols, batch, nullptr, nullptr, nullptr, ws,
+                                L.jac_bytes, s);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(intf, carve(ws, rows, cols, batch).flags, (size_t)batch * 4,
+                                    hipMemcpyDeviceToDevice, s));
+    }
     for (int l = 1; l < L.levels; ++l)
         for (int k = 0; k < 2; ++k) {
             const void *src = l == 1 ? (k ? fr.I1 : fr.I0) : base + L.off[l - 1][k];

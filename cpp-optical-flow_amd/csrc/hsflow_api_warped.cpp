@@ -273,7 +273,9 @@ int check_finest(hsflow_ctx *ctx, const SolveSpec &S) {
 // the median, the smoothness and the window it needs, levels, the finest
 // level, sizes, and the frames' type.  Null pointers, thresholds and the workspace's size follow in
 // the caller, each through its one routine.
-int check_solve(hsflow_ctx *ctx, const SolveSpec &S, int dtype_in, PfPlan *P) {
+// u16: a call that takes 16-bit frames (the YUV 4:2:0 ones), which every other
+// call refuses with the text it always had.
+int check_solve(hsflow_ctx *ctx, const SolveSpec &S, int dtype_in, PfPlan *P, bool u16 = false) {
     int rc = pf_on(S.pf) ? plan_prefilter(ctx, S.pf, P) : HSFLOW_OK;
     if (rc || (rc = check_iteration_args(ctx, S))) return rc;
     if (sm_on(S.sm)) {
@@ -285,6 +287,7 @@ int check_solve(hsflow_ctx *ctx, const SolveSpec &S, int dtype_in, PfPlan *P) {
     if ((rc = check_levels(ctx, S.levels)) || (rc = check_finest(ctx, S)) ||
         (rc = check_sizes(ctx, S.rows, S.cols, S.batch)))
         return rc;
+    if (u16 && dtype_in == HSFLOW_U16) return HSFLOW_OK;
     return check_device_dtype(ctx, dtype_in);
 }
 
@@ -724,13 +727,27 @@ int check_times(hsflow_ctx *ctx, const float *times, int nt) {
     return HSFLOW_OK;
 }
 
-int check_interp_args(hsflow_ctx *ctx, const float *times, int nt, int dtype_out, bool f64) {
+// u16: the output of a call on 16-bit frames, U16 or F32
+int check_interp_args(hsflow_ctx *ctx, const float *times, int nt, int dtype_out, bool f64,
+                      bool u16 = false) {
     const int rc = check_times(ctx, times, nt);
     if (rc) return rc;
+    if (u16) {
+        if (dtype_out != HSFLOW_F32 && dtype_out != HSFLOW_U16)
+            return fail(ctx, HSFLOW_ERR_ARG, "16-bit output dtype must be U16 or F32");
+        return HSFLOW_OK;
+    }
     if (dtype_out != HSFLOW_F32 && dtype_out != HSFLOW_U8 && !(f64 && dtype_out == HSFLOW_F64))
         return fail(ctx, HSFLOW_ERR_ARG, f64 ? "output dtype must be U8, F32 or F64"
                                              : "device output dtype must be U8 or F32");
     return HSFLOW_OK;
+}
+
+// what a launch writes for a checked dtype_out
+int out_kind(int dtype_out) {
+    return dtype_out == HSFLOW_U8    ? hsflow::kOutU8
+           : dtype_out == HSFLOW_U16 ? hsflow::kOutU16
+                                     : hsflow::kOutF32;
 }
 
 // the byte ranges an interpolation of `channels`-channel frames writes
@@ -747,9 +764,10 @@ void interp_out_ranges(const InterpOut &O, size_t n, int batch, int channels, By
 int frame_interp_run(hsflow_ctx *ctx, int channels, const Frames &fr, int rows, int cols, int batch,
                      const FlowsIn &W, const InterpOut &O, hipStream_t s) {
     if (O.trusted) HIP_TRY(ctx, hipMemsetAsync(O.trusted, 0, (size_t)batch * O.nt * 4, s));
-    const bool u8 = O.dtype_out == HSFLOW_U8;
+    const int kind = out_kind(O.dtype_out);
     hipError_t e;
     if (channels == 3) {
+        const bool u8 = kind == hsflow::kOutU8;  // the BGR calls have no u16 output
         const uint8_t *b0 = (const uint8_t *)fr.I0, *b1 = (const uint8_t *)fr.I1;
         e = W.cells ? hsflow::launch_frame_interp_bgr_proj(b0, b1, rows, cols, batch, W.uf, W.vf,
                                                            W.ub, W.vb, W.mask_f, W.mask_b, W.cells,
@@ -763,10 +781,11 @@ int frame_interp_run(hsflow_ctx *ctx, int channels, const Frames &fr, int rows, 
     }
     e = W.cells ? hsflow::launch_frame_interp_proj(fr.I0, fr.I1, fr.dtype, rows, cols, batch, W.uf,
                                                    W.vf, W.ub, W.vb, W.mask_f, W.mask_b, W.cells,
-                                                   O.times, O.nt, O.out, u8, O.flags, O.trusted, s)
+                                                   O.times, O.nt, O.out, kind, O.flags, O.trusted,
+                                                   s)
                 : hsflow::launch_frame_interp(fr.I0, fr.I1, fr.dtype, rows, cols, batch, W.uf, W.vf,
                                               W.ub, W.vb, W.mask_f, W.mask_b, O.times, O.nt, O.out,
-                                              u8, O.flags, O.trusted, s);
+                                              kind, O.flags, O.trusted, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "frame interpolation launch");
     return HSFLOW_OK;
 }
@@ -860,15 +879,15 @@ int fallback_run(hsflow_ctx *ctx, int channels, const Frames &fr, int rows, int 
                  const uint32_t *counts_f, const uint32_t *counts_b, const hsflow_fallback &fb,
                  const InterpOut &O, hipStream_t s) {
     const uint64_t m = min_consistent(rows, cols, fb.min_share);
-    const bool u8 = O.dtype_out == HSFLOW_U8;
+    const int kind = out_kind(O.dtype_out);
     hipError_t e =
         channels == 3
             ? hsflow::launch_frame_fallback_bgr((const uint8_t *)fr.I0, (const uint8_t *)fr.I1,
                                                 rows, cols, batch, counts_f, counts_b, m, fb.mode,
-                                                O.times, O.nt, O.out, u8, O.flags, O.trusted,
-                                                O.cut, s)
+                                                O.times, O.nt, O.out, kind == hsflow::kOutU8,
+                                                O.flags, O.trusted, O.cut, s)
             : hsflow::launch_frame_fallback(fr.I0, fr.I1, fr.dtype, rows, cols, batch, counts_f,
-                                            counts_b, m, fb.mode, O.times, O.nt, O.out, u8,
+                                            counts_b, m, fb.mode, O.times, O.nt, O.out, kind,
                                             O.flags, O.trusted, O.cut, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "frame fallback launch");
     return HSFLOW_OK;
@@ -936,13 +955,13 @@ InterpLayout interp_layout(int rows, int cols, int batch, int levels, int channe
 // are unchanged and a given O.cut is zeroed.
 int flow_interp_impl(hsflow_ctx *ctx, const SolveSpec &S, int channels, const Frames &in,
                      float rel, float abs_thr, const InterpOut &O, void *ws, size_t ws_bytes,
-                     hipStream_t s) {
+                     hipStream_t s, bool u16 = false) {
     PfPlan P;
-    int rc = check_solve(ctx, S, in.dtype, &P);
+    int rc = check_solve(ctx, S, in.dtype, &P, u16);
     if (rc) return rc;
     if (!in.I0 || !in.I1 || !O.out || !ws) return null_pointer(ctx);
     if ((rc = check_thresholds(ctx, rel, abs_thr))) return rc;
-    if ((rc = check_interp_args(ctx, O.times, O.nt, O.dtype_out, false))) return rc;
+    if ((rc = check_interp_args(ctx, O.times, O.nt, O.dtype_out, false, u16))) return rc;
     if ((rc = check_projection(ctx, S.projection))) return rc;
     const bool fallback = fb_on(S.fb);
     if (fallback && (rc = check_fallback(ctx, S.fb))) return rc;
@@ -1112,8 +1131,10 @@ int check_yuv_shape(hsflow_ctx *ctx, int layout, int rows, int cols, int batch) 
 }
 
 // the chroma of a call: both frames', and the nt frames (times: host) it writes
+// dtype: the samples', HSFLOW_U8 or HSFLOW_U16 (the *16 calls)
 struct ChromaIO {
-    const uint8_t *c0, *c1;
+    const void *c0, *c1;
+    int dtype;
     int layout;
     const float *times;
     int nt;
@@ -1121,10 +1142,13 @@ struct ChromaIO {
     int dtype_out;
 };
 
-// bytes of the chroma of `batch` frames, and of the output's
-size_t chroma_bytes(int rows, int cols, int batch) { return (size_t)rows * cols * batch / 2; }
+// samples of the chroma of `batch` frames; the bytes of a call's, and of its output's
+size_t chroma_samples(int rows, int cols, int batch) { return (size_t)rows * cols * batch / 2; }
+size_t chroma_bytes(const ChromaIO &C, int rows, int cols, int batch) {
+    return chroma_samples(rows, cols, batch) * elem_size(C.dtype);
+}
 size_t chroma_out_bytes(const ChromaIO &C, int rows, int cols, int batch) {
-    return chroma_bytes(rows, cols, batch) * C.nt * elem_size(C.dtype_out);
+    return chroma_samples(rows, cols, batch) * C.nt * elem_size(C.dtype_out);
 }
 
 // KIY, or with W.cells KIYP, on checked arguments: one launch.  fb: null for no
@@ -1134,9 +1158,10 @@ int chroma_interp_run(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, in
                       const hsflow_fallback *fb, hipStream_t s) {
     const bool on = fb_on(fb);
     hipError_t e = hsflow::launch_chroma_interp(
-        C.c0, C.c1, C.layout, rows, cols, batch, W.uf, W.vf, W.ub, W.vb, on ? counts_f : nullptr,
-        on ? counts_b : nullptr, on ? min_consistent(rows, cols, fb->min_share) : 0,
-        on ? fb->mode : 0, C.times, C.nt, C.out, C.dtype_out == HSFLOW_U8, s, W.cells);
+        C.c0, C.c1, C.dtype, C.layout, rows, cols, batch, W.uf, W.vf, W.ub, W.vb,
+        on ? counts_f : nullptr, on ? counts_b : nullptr,
+        on ? min_consistent(rows, cols, fb->min_share) : 0, on ? fb->mode : 0, C.times, C.nt,
+        C.out, out_kind(C.dtype_out), s, W.cells);
     if (e != hipSuccess) return hip_fail(ctx, e, "chroma interpolation launch");
     return HSFLOW_OK;
 }
@@ -1149,14 +1174,15 @@ int chroma_interp_impl(hsflow_ctx *ctx, const ChromaIO &C, int rows, int cols, i
     int rc = check_yuv_shape(ctx, C.layout, rows, cols, batch);
     if (rc) return rc;
     if (!C.c0 || !C.c1 || !W.uf || !W.vf || !W.ub || !W.vb || !C.out) return null_pointer(ctx);
-    if ((rc = check_interp_args(ctx, C.times, C.nt, C.dtype_out, false))) return rc;
+    const bool u16 = C.dtype == HSFLOW_U16;
+    if ((rc = check_interp_args(ctx, C.times, C.nt, C.dtype_out, false, u16))) return rc;
     if (proj && (rc = check_cells(ctx, W.cells))) return rc;
     const bool on = fb_on(fb);
     if (on) {
         if ((rc = check_fallback(ctx, fb))) return rc;
         if (!counts_f || !counts_b) return null_pointer(ctx);
     }
-    const size_t n = (size_t)rows * cols * batch, cb = chroma_bytes(rows, cols, batch);
+    const size_t n = (size_t)rows * cols * batch, cb = chroma_bytes(C, rows, cols, batch);
     const size_t kb = (size_t)batch * 3 * 4;
     const ByteRange in[9] = {{C.c0, cb},    {C.c1, cb},    {W.uf, n * 4},
                              {W.vf, n * 4}, {W.ub, n * 4}, {W.vb, n * 4},
@@ -1200,15 +1226,17 @@ int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma
     if (rc || (rc = check_levels(ctx, S.levels))) return rc;
     if (!luma.I0 || !luma.I1 || !C.c0 || !C.c1 || !Y.out || !C.out || !ws)
         return null_pointer(ctx);
-    if ((rc = check_interp_args(ctx, Y.times, Y.nt, Y.dtype_out, false))) return rc;
+    const bool u16 = luma.dtype == HSFLOW_U16;
+    if ((rc = check_interp_args(ctx, Y.times, Y.nt, Y.dtype_out, false, u16))) return rc;
     if ((rc = check_projection(ctx, S.projection))) return rc;
     const bool fallback = fb_on(S.fb);
     if (fallback && (rc = check_fallback(ctx, S.fb))) return rc;
     const InterpLayout L = interp_layout(S.rows, S.cols, S.batch, S.levels, 1,
                                          S.projection ? Y.nt : 0, fallback);
     const size_t need = L.bytes + (pf_on(S.pf) ? pf_planes_bytes(S.rows, S.cols, S.batch) : 0);
-    const size_t n = (size_t)S.rows * S.cols * S.batch, cb = chroma_bytes(S.rows, S.cols, S.batch);
-    const ByteRange ins[5] = {{luma.I0, n}, {luma.I1, n}, {C.c0, cb}, {C.c1, cb}, {ws, need}};
+    const size_t n = (size_t)S.rows * S.cols * S.batch;
+    const size_t yb = n * elem_size(luma.dtype), cb = chroma_bytes(C, S.rows, S.cols, S.batch);
+    const ByteRange ins[5] = {{luma.I0, yb}, {luma.I1, yb}, {C.c0, cb}, {C.c1, cb}, {ws, need}};
     ByteRange outs[5];
     interp_out_ranges(Y, n, S.batch, 1, outs);
     outs[4] = {C.out, chroma_out_bytes(C, S.rows, S.cols, S.batch)};
@@ -1221,7 +1249,7 @@ int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma
             if (bytes_overlap(p, n * 4, outs[4].p, outs[4].n))
                 return fail(ctx, HSFLOW_ERR_ARG, "init flow overlaps an output");
     }
-    if ((rc = flow_interp_impl(ctx, S, 1, luma, rel, abs_thr, Y, ws, ws_bytes, s))) return rc;
+    if ((rc = flow_interp_impl(ctx, S, 1, luma, rel, abs_thr, Y, ws, ws_bytes, s, u16))) return rc;
     char *base = (char *)ws;
     const FlowsIn W{(const float *)(base + L.flow[0]), (const float *)(base + L.flow[1]),
                     (const float *)(base + L.flow[2]), (const float *)(base + L.flow[3]),
@@ -1237,16 +1265,19 @@ int flow_interp_yuv_impl(hsflow_ctx *ctx, const SolveSpec &S, const Frames &luma
 // a time come down into its packed host frame.  projection < 0
 // (hsflow_flow_interp_yuv): none, and a context that has it on is refused; 0 or
 // 1 (hsflow_flow_interp_yuv_pj): that, whatever the context's setting.
-int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *f0,
-                         const uint8_t *f1, int layout, float rel, float abs_thr,
-                         const float *times, int nt, int projection, void *const *out,
-                         int dtype_out, uint8_t *const *flags, uint32_t *trusted) {
+// dtype_in: HSFLOW_U8, or HSFLOW_U16 (hsflow_flow_interp_yuv16): frames of
+// 2-byte samples, out U16 or F32.
+int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const void *f0, const void *f1,
+                         int dtype_in, int layout, float rel, float abs_thr, const float *times,
+                         int nt, int projection, void *const *out, int dtype_out,
+                         uint8_t *const *flags, uint32_t *trusted) {
     SolveSpec S = spec;
     const int rows = S.rows, cols = S.cols;
     if (ctx) ctx->last_cut = -1;
     hsflow_flow_init init;
     if (ctx && take_prediction(ctx, rows, cols, &init)) S.init = &init;
-    int rc = check_interp_args(ctx, times, nt, dtype_out, false);
+    const size_t is = elem_size(dtype_in);
+    int rc = check_interp_args(ctx, times, nt, dtype_out, false, dtype_in == HSFLOW_U16);
     if (rc) return rc;
     if (!f0 || !f1) return fail(ctx, HSFLOW_ERR_ARG, "null image");
     if ((rc = check_yuv_shape(ctx, layout, rows, cols, 1))) return rc;
@@ -1273,7 +1304,7 @@ int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *
     const size_t wsb = interp_layout(rows, cols, 1, S.levels, 1, cell_nt, fb).bytes +
                        (pf_on(S.pf) ? pf_planes_bytes(rows, cols, 1) : 0);
     char *in0, *in1;
-    rc = stage_pair(ctx, f0, f1, 1, rows / 2 * 3, cols, (size_t)cols, (size_t)cols,
+    rc = stage_pair(ctx, f0, f1, is, rows / 2 * 3, cols, (size_t)cols * is, (size_t)cols * is,
                     yb + cb + flb + kAlign, wsb, &in0, &in1);
     if (rc || (rc = grow_prediction(ctx, rows, cols))) return rc;
     char *dy = (char *)ctx->d_out, *dc = dy + yb;
@@ -1282,9 +1313,8 @@ int flow_interp_yuv_host(hsflow_ctx *ctx, const SolveSpec &spec, const uint8_t *
     uint8_t *dcut = (uint8_t *)(dtr + HSFLOW_MAX_TIMES);  // within the kAlign bytes
     const InterpOut Y{times, nt, dy, dtype_out, flags ? dfl : nullptr, trusted ? dtr : nullptr,
                       fb ? dcut : nullptr};
-    const ChromaIO C{(const uint8_t *)in0 + n, (const uint8_t *)in1 + n, layout, times, nt, dc,
-                     dtype_out};
-    rc = flow_interp_yuv_impl(ctx, S, Frames{in0, in1, HSFLOW_U8}, C, rel, abs_thr, Y, ctx->d_ws,
+    const ChromaIO C{in0 + n * is, in1 + n * is, dtype_in, layout, times, nt, dc, dtype_out};
+    rc = flow_interp_yuv_impl(ctx, S, Frames{in0, in1, dtype_in}, C, rel, abs_thr, Y, ctx->d_ws,
                               ctx->d_ws_bytes, ctx->stream);
     if (rc) return rc;
     const InterpLayout L = interp_layout(rows, cols, 1, S.levels, 1, cell_nt, fb);
@@ -2115,9 +2145,10 @@ int hsflow_chroma_interp_device(const uint8_t *c0, const uint8_t *c1, int layout
                                 const float *times, int nt, void *out_c, int dtype_out,
                                 void *stream) {
     DeviceGuard g((hipStream_t)stream);
-    return chroma_interp_impl(nullptr, ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rows,
-                              cols, batch, FlowsIn{uf, vf, ub, vb, nullptr, nullptr, nullptr},
-                              counts_f, counts_b, fb, false, (hipStream_t)stream);
+    const ChromaIO C{c0, c1, HSFLOW_U8, layout, times, nt, out_c, dtype_out};
+    return chroma_interp_impl(nullptr, C, rows, cols, batch,
+                              FlowsIn{uf, vf, ub, vb, nullptr, nullptr, nullptr}, counts_f,
+                              counts_b, fb, false, (hipStream_t)stream);
 }
 
 size_t hsflow_flow_interp_yuv_workspace_bytes(int rows, int cols, int batch, int levels,
@@ -2141,7 +2172,8 @@ int hsflow_flow_interp_yuv_device(const uint8_t *y0, const uint8_t *c0, const ui
     const SolveSpec S{rows,  cols,  batch, levels, finest, warps, median, window,
                       iters, alpha, pf,    sm,     init,   0,     fb};
     return flow_interp_yuv_impl(nullptr, S, Frames{y0, y1, HSFLOW_U8},
-                                ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rel, abs_thr,
+                                ChromaIO{c0, c1, HSFLOW_U8, layout, times, nt, out_c, dtype_out},
+                                rel, abs_thr,
                                 InterpOut{times, nt, out_y, dtype_out, flags, trusted, cut},
                                 workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2152,8 +2184,8 @@ int hsflow_flow_interp_yuv(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1
                            int nt, void *const *out, int dtype_out, uint8_t *const *flags,
                            uint32_t *trusted) {
     const SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
-    return flow_interp_yuv_host(ctx, S, f0, f1, layout, rel, abs_thr, times, nt, -1, out,
-                                dtype_out, flags, trusted);
+    return flow_interp_yuv_host(ctx, S, f0, f1, HSFLOW_U8, layout, rel, abs_thr, times, nt, -1,
+                                out, dtype_out, flags, trusted);
 }
 
 int hsflow_cells_down_device(const uint64_t *cells, int rows, int cols, int batch, int nt,
@@ -2169,9 +2201,10 @@ int hsflow_chroma_interp_proj_device(const uint8_t *c0, const uint8_t *c1, int l
                                      const hsflow_fallback *fb, const float *times, int nt,
                                      void *out_c, int dtype_out, void *stream) {
     DeviceGuard g((hipStream_t)stream);
-    return chroma_interp_impl(nullptr, ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rows,
-                              cols, batch, FlowsIn{uf, vf, ub, vb, nullptr, nullptr, cells},
-                              counts_f, counts_b, fb, true, (hipStream_t)stream);
+    const ChromaIO C{c0, c1, HSFLOW_U8, layout, times, nt, out_c, dtype_out};
+    return chroma_interp_impl(nullptr, C, rows, cols, batch,
+                              FlowsIn{uf, vf, ub, vb, nullptr, nullptr, cells}, counts_f, counts_b,
+                              fb, true, (hipStream_t)stream);
 }
 
 size_t hsflow_flow_interp_yuv_pj_workspace_bytes(int rows, int cols, int batch, int levels,
@@ -2197,7 +2230,8 @@ int hsflow_flow_interp_yuv_pj_device(const uint8_t *y0, const uint8_t *c0, const
     const SolveSpec S{rows,  cols,  batch, levels, finest, warps,      median, window,
                       iters, alpha, pf,    sm,     init,   projection, fb};
     return flow_interp_yuv_impl(nullptr, S, Frames{y0, y1, HSFLOW_U8},
-                                ChromaIO{c0, c1, layout, times, nt, out_c, dtype_out}, rel, abs_thr,
+                                ChromaIO{c0, c1, HSFLOW_U8, layout, times, nt, out_c, dtype_out},
+                                rel, abs_thr,
                                 InterpOut{times, nt, out_y, dtype_out, flags, trusted, cut},
                                 workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2208,7 +2242,50 @@ int hsflow_flow_interp_yuv_pj(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t 
                               const float *times, int nt, int projection, void *const *out,
                               int dtype_out, uint8_t *const *flags, uint32_t *trusted) {
     const SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
-    return flow_interp_yuv_host(ctx, S, f0, f1, layout, rel, abs_thr, times, nt,
+    return flow_interp_yuv_host(ctx, S, f0, f1, HSFLOW_U8, layout, rel, abs_thr, times, nt,
+                                projection < 0 ? 2 : projection, out, dtype_out, flags, trusted);
+}
+
+int hsflow_chroma_interp16_device(const uint16_t *c0, const uint16_t *c1, int layout, int rows,
+                                  int cols, int batch, const float *uf, const float *vf,
+                                  const float *ub, const float *vb, const uint64_t *cells,
+                                  const uint32_t *counts_f, const uint32_t *counts_b,
+                                  const hsflow_fallback *fb, const float *times, int nt,
+                                  void *out_c, int dtype_out, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    return chroma_interp_impl(nullptr,
+                              ChromaIO{c0, c1, HSFLOW_U16, layout, times, nt, out_c, dtype_out},
+                              rows, cols, batch, FlowsIn{uf, vf, ub, vb, nullptr, nullptr, cells},
+                              counts_f, counts_b, fb, cells != nullptr, (hipStream_t)stream);
+}
+
+int hsflow_flow_interp_yuv16_device(const uint16_t *y0, const uint16_t *c0, const uint16_t *y1,
+                                    const uint16_t *c1, int layout, int rows, int cols, int batch,
+                                    int levels, int finest, int warps, int median, int window,
+                                    int iters, float alpha, float rel, float abs_thr,
+                                    const float *times, int nt, int projection, void *out_y,
+                                    void *out_c, int dtype_out, uint8_t *flags,
+                                    uint32_t *trusted, uint8_t *cut, const hsflow_prefilter *pf,
+                                    const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                    const hsflow_fallback *fb, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    DeviceGuard g((hipStream_t)stream);
+    const SolveSpec S{rows,  cols,  batch, levels, finest, warps,      median, window,
+                      iters, alpha, pf,    sm,     init,   projection, fb};
+    return flow_interp_yuv_impl(nullptr, S, Frames{y0, y1, HSFLOW_U16},
+                                ChromaIO{c0, c1, HSFLOW_U16, layout, times, nt, out_c, dtype_out},
+                                rel, abs_thr,
+                                InterpOut{times, nt, out_y, dtype_out, flags, trusted, cut},
+                                workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int hsflow_flow_interp_yuv16(hsflow_ctx *ctx, const uint16_t *f0, const uint16_t *f1, int layout,
+                             int rows, int cols, int levels, int warps, int median, int window,
+                             int iters, double alpha, float rel, float abs_thr,
+                             const float *times, int nt, int projection, void *const *out,
+                             int dtype_out, uint8_t *const *flags, uint32_t *trusted) {
+    const SolveSpec S = host_spec(ctx, rows, cols, levels, warps, median, window, iters, alpha);
+    return flow_interp_yuv_host(ctx, S, f0, f1, HSFLOW_U16, layout, rel, abs_thr, times, nt,
                                 projection < 0 ? 2 : projection, out, dtype_out, flags, trusted);
 }
 

@@ -16,7 +16,7 @@
 //                compiler contracts its (1 - wt) s0 + wt s1 to that
 //                multiply-add).  Here it is spelled out, with contraction
 //                off, so that KF's bits do not hang on a compiler's choice.
-//     a u8 output through KI's round_u8, flags = 32 (HSFLOW_INTERP_FALLBACK)
+//     a u8 output through KI's round_u8 (u16: round_u16), flags = 32 (HSFLOW_INTERP_FALLBACK)
 //     replacing what was there, trusted[b][t] = 0, cut[b] = 1.
 //
 // One launch serves all times and the whole batch.  The map is KI's (256
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_fallback_kernel(
     const typename Frame::Elem *__restrict__ I0, const typename Frame::Elem *__restrict__ I1,
     const uint32_t *__restrict__ counts_f, const uint32_t *__restrict__ counts_b,
     uint64_t min_consistent, int mode, int plane, InterpTimes times, int nt,
-    void *__restrict__ out, int out_u8, uint8_t *__restrict__ flags,
+    void *__restrict__ out, int out_kind, uint8_t *__restrict__ flags,
     uint32_t *__restrict__ trusted, uint8_t *__restrict__ cut) {
     constexpr int kThreads = kInterpThreads, kPix = kInterpPix, kTile = kInterpTile;
     constexpr int kCh = Frame::kChannels;
@@ -111,8 +111,10 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_fallback_kernel(
                 }
                 const int q0 = pk[k] - (t & 3);  // the quad's first pixel, >= 0
                 const bool whole = q0 + 3 < plane;
-                if (out_u8) {  // uniform
+                if (out_kind == kOutU8) {  // uniform
                     Frame::store_u8(out, obase, pk[k], q0, whole, valid, o, t);
+                } else if (Frame::kU16Out && out_kind == kOutU16) {  // uniform
+                    if constexpr (Frame::kU16Out) Frame::store_u16(out, obase, pk[k], plane, o, t);
                 } else if (valid) {
                     Frame::store_f32(out, obase + pk[k], o);
                 }
@@ -128,10 +130,12 @@ template <typename Frame>
 hipError_t launch_frame_fallback_as(const void *I0, const void *I1, int rows, int cols, int batch,
                                     const uint32_t *counts_f, const uint32_t *counts_b,
                                     uint64_t min_consistent, int mode, const float *times, int nt,
-                                    void *out, bool out_u8, uint8_t *flags, uint32_t *trusted,
+                                    void *out, int out_kind, uint8_t *flags, uint32_t *trusted,
                                     uint8_t *cut, hipStream_t s) {
     using Elem = typename Frame::Elem;
     if (nt < 1 || nt > kInterpMaxTimes) return hipErrorInvalidValue;
+    if (out_kind != kOutF32 && out_kind != kOutU8 && !(Frame::kU16Out && out_kind == kOutU16))
+        return hipErrorInvalidValue;
     InterpTimes tm{};
     for (int k = 0; k < nt; ++k) tm.t[k] = times[k];
     const size_t plane = (size_t)rows * cols;
@@ -140,7 +144,7 @@ hipError_t launch_frame_fallback_as(const void *I0, const void *I1, int rows, in
     dim3 blk(kInterpThreads, 1, 1), grd(std::min(ntiles, cap), batch, 1);
     hipLaunchKernelGGL(hs_frame_fallback_kernel<Frame>, grd, blk, 0, s, (const Elem *)I0,
                        (const Elem *)I1, counts_f, counts_b, min_consistent, mode, (int)plane, tm,
-                       nt, out, out_u8 ? 1 : 0, flags, trusted, cut);
+                       nt, out, out_kind, flags, trusted, cut);
     return hipGetLastError();
 }
 
@@ -149,14 +153,14 @@ hipError_t launch_frame_fallback_as(const void *I0, const void *I1, int rows, in
 hipError_t launch_frame_fallback(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                  int batch, const uint32_t *counts_f, const uint32_t *counts_b,
                                  uint64_t min_consistent, int mode, const float *times, int nt,
-                                 void *out, bool out_u8, uint8_t *flags, uint32_t *trusted,
+                                 void *out, int out_kind, uint8_t *flags, uint32_t *trusted,
                                  uint8_t *cut, hipStream_t s) {
     hipError_t e = hipErrorInvalidValue;  // stays for an unknown dtype
     dispatch_frame_type(dtype_in, [&](auto t) {
         e = launch_frame_fallback_as<GreyFrame<decltype(t)>>(I0, I1, rows, cols, batch, counts_f,
                                                              counts_b, min_consistent, mode, times,
-                                                             nt, out, out_u8, flags, trusted, cut,
-                                                             s);
+                                                             nt, out, out_kind, flags, trusted,
+                                                             cut, s);
     });
     return e;
 }

@@ -16,8 +16,8 @@ __device__ __forceinline__ int clampi(int p, int len) { return min(max(p, 0), le
 template <typename T> struct FrameMath { using type = float; };
 template <> struct FrameMath<double> { using type = double; };
 
-// f(T{}) for the element type T of dtype code HSFLOW_U8 / F32 / F64 / F16;
-// false for any other code, f not called
+// f(T{}) for the element type T of dtype code HSFLOW_U8 / F32 / F64 / F16 /
+// U16; false for any other code, f not called
 template <typename Fn>
 bool dispatch_frame_type(int dtype_in, Fn &&f) {
     switch (dtype_in) {
@@ -25,6 +25,7 @@ bool dispatch_frame_type(int dtype_in, Fn &&f) {
     case 1: f(float{}); return true;
     case 2: f(double{}); return true;
     case 3: f(_Float16{}); return true;
+    case 4: f(uint16_t{}); return true;
     default: return false;
     }
 }

@@ -51,7 +51,7 @@ hipError_t launch_gradients_f32(const void *I0, const void *I1, int dtype_in, in
                                 int cols, int batch, float *gx, float *gy, float *gt,
                                 const uint32_t *flags, hipStream_t s);
 hipError_t launch_jacobi(JacobiArgs a, int W, int KB, hipStream_t s);
-// config 5 pyramid (hsflow_pyramid.hip); dtype as HSFLOW_U8/F32/F16
+// config 5 pyramid (hsflow_pyramid.hip); dtype as HSFLOW_U8/F32/F16/U16
 hipError_t launch_pyrdown(const void *src, int dtype, int rows, int cols, int batch,
                           float *dst, const uint32_t *flags, hipStream_t s);
 // GPU input path (hsflow_input.hip): dense BGR u8 planes -> gray u8
@@ -86,15 +86,17 @@ hipError_t launch_warp_image(const void *I, int dtype_in, int rows, int cols, in
                              const float *u, const float *v, float *out, uint8_t *oof,
                              hipStream_t s);
 // KI (hsflow_interp.hip): the frames at `nt` (1..kInterpMaxTimes) times between
-// I0 and I1 from the flows both ways -> out [batch][nt] planes (f32, or u8 when
-// out_u8), flags (u8, may be null) and trusted[batch][nt] (may be null; must be
-// zero before the launch: the kernel adds).  mask_f / mask_b: KC's masks, each
-// may be null.  `times` is read on the host at launch.
+// I0 and I1 from the flows both ways -> out [batch][nt] planes (out_kind: f32,
+// u8 or, for 16-bit frames only, u16), flags (u8, may be null) and
+// trusted[batch][nt] (may be null; must be zero before the launch: the kernel
+// adds).  mask_f / mask_b: KC's masks, each may be null.  `times` is read on the
+// host at launch.
 constexpr int kInterpMaxTimes = 16;
+constexpr int kOutF32 = 0, kOutU8 = 1, kOutU16 = 2;  // what an interpolation writes
 hipError_t launch_frame_interp(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                int batch, const float *uf, const float *vf, const float *ub,
                                const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
-                               const float *times, int nt, void *out, bool out_u8,
+                               const float *times, int nt, void *out, int out_kind,
                                uint8_t *flags, uint32_t *trusted, hipStream_t s);
 // KRC, KIC (hsflow_interp_bgr.hip): KR and KI on dense 8-bit interleaved BGR
 // frames [batch][rows][cols][3] -> out [..][rows][cols][3] (f32, or u8 when
@@ -123,7 +125,7 @@ hipError_t launch_frame_interp_proj(const void *I0, const void *I1, int dtype_in
                                     int cols, int batch, const float *uf, const float *vf,
                                     const float *ub, const float *vb, const uint8_t *mask_f,
                                     const uint8_t *mask_b, const uint64_t *cells,
-                                    const float *times, int nt, void *out, bool out_u8,
+                                    const float *times, int nt, void *out, int out_kind,
                                     uint8_t *flags, uint32_t *trusted, hipStream_t s);
 hipError_t launch_frame_interp_bgr_proj(const uint8_t *I0, const uint8_t *I1, int rows, int cols,
                                         int batch, const float *uf, const float *vf,
@@ -140,7 +142,7 @@ hipError_t launch_frame_interp_bgr_proj(const uint8_t *I0, const uint8_t *I1, in
 hipError_t launch_frame_fallback(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                  int batch, const uint32_t *counts_f, const uint32_t *counts_b,
                                  uint64_t min_consistent, int mode, const float *times, int nt,
-                                 void *out, bool out_u8, uint8_t *flags, uint32_t *trusted,
+                                 void *out, int out_kind, uint8_t *flags, uint32_t *trusted,
                                  uint8_t *cut, hipStream_t s);
 hipError_t launch_frame_fallback_bgr(const uint8_t *I0, const uint8_t *I1, int rows, int cols,
                                      int batch, const uint32_t *counts_f,
@@ -152,14 +154,16 @@ hipError_t launch_frame_fallback_bgr(const uint8_t *I0, const uint8_t *I1, int r
 // the full-resolution flows of the luma solve (rows, cols: the luma's, even):
 // KD's 2 x 2 reduction and KI on the rc x cc chroma grid for U and V in one
 // launch, for all times and pairs.  layout 1: I420 [batch][2][rc][cc], 2: NV12
-// [batch][rc][cc][2]; out [batch][nt] of that layout, u8 or f32.  With counts
-// (both or neither; null: no fallback) a pair that fails min_consistent gets
-// KF's value by `mode`.  `times` is read on the host at launch.
-hipError_t launch_chroma_interp(const uint8_t *c0, const uint8_t *c1, int layout, int rows,
-                                int cols, int batch, const float *uf, const float *vf,
+// [batch][rc][cc][2], of 8-bit (dtype_in 0) or 16-bit (dtype_in 4) samples; out
+// [batch][nt] of that layout: f32 or the frames' own integer type (out_kind).
+// With counts (both or neither; null: no fallback) a pair that fails
+// min_consistent gets KF's value by `mode`.  `times` is read on the host at
+// launch.
+hipError_t launch_chroma_interp(const void *c0, const void *c1, int dtype_in, int layout,
+                                int rows, int cols, int batch, const float *uf, const float *vf,
                                 const float *ub, const float *vb, const uint32_t *counts_f,
                                 const uint32_t *counts_b, uint64_t min_consistent, int mode,
-                                const float *times, int nt, void *out, bool out_u8,
+                                const float *times, int nt, void *out, int out_kind,
                                 hipStream_t s, const uint64_t *cells = nullptr);
 // the cap of KIY's grid, in blocks per CU
 int chroma_blocks_per_cu();

@@ -91,13 +91,13 @@ hipError_t launch_warp_image(const void *I, int dtype_in, int rows, int cols, in
 hipError_t launch_frame_interp(const void *I0, const void *I1, int dtype_in, int rows, int cols,
                                int batch, const float *uf, const float *vf, const float *ub,
                                const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
-                               const float *times, int nt, void *out, bool out_u8,
+                               const float *times, int nt, void *out, int out_kind,
                                uint8_t *flags, uint32_t *trusted, hipStream_t s) {
     hipError_t e = hipErrorInvalidValue;  // stays for an unknown dtype
     dispatch_frame_type(dtype_in, [&](auto t) {
         e = launch_frame_interp_as<GreyFrame<decltype(t)>>(I0, I1, rows, cols, batch, uf, vf, ub,
                                                            vb, mask_f, mask_b, times, nt, out,
-                                                           out_u8, flags, trusted, s);
+                                                           out_kind, flags, trusted, s);
     });
     return e;
 }
@@ -108,14 +108,14 @@ hipError_t launch_frame_interp_proj(const void *I0, const void *I1, int dtype_in
                                     int cols, int batch, const float *uf, const float *vf,
                                     const float *ub, const float *vb, const uint8_t *mask_f,
                                     const uint8_t *mask_b, const uint64_t *cells,
-                                    const float *times, int nt, void *out, bool out_u8,
+                                    const float *times, int nt, void *out, int out_kind,
                                     uint8_t *flags, uint32_t *trusted, hipStream_t s) {
     hipError_t e = hipErrorInvalidValue;  // stays for an unknown dtype or null cells
     if (!cells) return e;
     dispatch_frame_type(dtype_in, [&](auto t) {
         e = launch_frame_interp_as<GreyFrame<decltype(t)>>(I0, I1, rows, cols, batch, uf, vf, ub,
                                                            vb, mask_f, mask_b, times, nt, out,
-                                                           out_u8, flags, trusted, s, cells);
+                                                           out_kind, flags, trusted, s, cells);
     });
     return e;
 }

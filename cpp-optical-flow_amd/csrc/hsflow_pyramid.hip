@@ -108,6 +108,10 @@ hipError_t launch_pyrdown(const void *src, int dtype, int rows, int cols, int ba
         hipLaunchKernelGGL(hs_pyrdown_kernel<_Float16>, grd, blk, 0, s,
                            (const _Float16 *)src, rows, cols, dst, r2, c2, flags);
         break;
+    case 4:  // HSFLOW_U16
+        hipLaunchKernelGGL(hs_pyrdown_kernel<uint16_t>, grd, blk, 0, s,
+                           (const uint16_t *)src, rows, cols, dst, r2, c2, flags);
+        break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

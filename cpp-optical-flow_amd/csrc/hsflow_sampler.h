@@ -109,6 +109,26 @@ __device__ __forceinline__ void store_quad_u8(uint8_t *dst, int pk, int q0, bool
     }
 }
 
+// value of the other lane of the caller's pair (2j, 2j + 1): quad_perm 1 0 3 2
+__device__ __forceinline__ uint32_t pair_lane(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, true);
+}
+
+// One 16-bit sample per lane into a u16 plane at dst + pk (pk: the lane's
+// pixel; its parity is the lane's, so the pair holds pk & ~1 and the next): an
+// aligned dword per pair where both lie in the plane and the address allows,
+// else two bytes per valid lane.  Every lane of the wave calls.
+__device__ __forceinline__ void store_pair_u16(uint16_t *dst, int pk, int plane, uint32_t half,
+                                               int lane) {
+    const uint32_t other = pair_lane(half);
+    const int p0 = pk - (lane & 1);  // the pair's first pixel, >= 0
+    if (p0 + 1 < plane && ((uintptr_t)(dst + p0) & 3) == 0) {
+        if ((lane & 1) == 0) *reinterpret_cast<uint32_t *>(dst + p0) = half | other << 16;
+    } else if (pk < plane) {
+        dst[pk] = (uint16_t)half;
+    }
+}
+
 // ---- frame interpolation (KI, KIC)
 
 // the weight of s1: t where both targets are in the frame or neither is
@@ -124,6 +144,11 @@ __device__ __forceinline__ float blend(float wt, float s0, float s1) {
 // floorf(o + 0.5f) clamped to 0..255; NaN -> 0 (fmaxf drops it)
 __device__ __forceinline__ uint32_t round_u8(float o) {
     return (uint32_t)fminf(fmaxf(floorf(o + 0.5f), 0.0f), 255.0f);
+}
+
+// the same rule with the bound of a 16-bit sample
+__device__ __forceinline__ uint32_t round_u16(float o) {
+    return (uint32_t)fminf(fmaxf(floorf(o + 0.5f), 0.0f), 65535.0f);
 }
 
 // a sampled colour pixel: C channels in f32 (a grey one is a float)
@@ -148,6 +173,9 @@ constexpr int kInterpThreads = 256, kInterpPix = 2, kInterpTile = kInterpThreads
 //   store_u8(out, obase, pk, q0, whole, valid, o, lane)   into the u8 plane
 //       that starts at pixel obase of the whole output; a quad store as
 //       store_quad_u8, every lane calls
+//   kU16Out, store_u16(out, obase, pk, plane, o, lane)   whether the frame has
+//       a u16 output (16-bit grey frames), and the pair store into it as
+//       store_pair_u16, every lane calls
 //   kBlocksPerCu        the grid's cap
 // Proj says where the time-t flow of an output pixel comes from: false (KI,
 // KIC) from the four flows at the pixel itself; true (KIP, DESIGN.md "Flow
@@ -164,7 +192,7 @@ __device__ __forceinline__ void frame_interp_body(
     const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
     const float *__restrict__ vb, const uint8_t *__restrict__ mask_f,
     const uint8_t *__restrict__ mask_b, const uint64_t *__restrict__ cells, int rows, int cols,
-    const InterpTimes &times, int nt, void *__restrict__ out, int out_u8,
+    const InterpTimes &times, int nt, void *__restrict__ out, int out_kind,
     uint8_t *__restrict__ flags, uint32_t *__restrict__ trusted) {
     constexpr int kThreads = kInterpThreads, kPix = kInterpPix, kTile = kInterpTile;
     constexpr int kCh = Frame::kChannels;
@@ -254,8 +282,10 @@ __device__ __forceinline__ void frame_interp_body(
                 good += valid && fl == 0u;
                 const int q0 = pk[k] - (t & 3);  // the quad's first pixel, >= 0
                 const bool whole = q0 + 3 < plane;
-                if (out_u8) {  // uniform
+                if (out_kind == kOutU8) {  // uniform
                     Frame::store_u8(out, obase, pk[k], q0, whole, valid, o, t);
+                } else if (Frame::kU16Out && out_kind == kOutU16) {  // uniform
+                    if constexpr (Frame::kU16Out) Frame::store_u16(out, obase, pk[k], plane, o, t);
                 } else if (valid) {
                     Frame::store_f32(out, obase + pk[k], o);
                 }
@@ -283,10 +313,10 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_kernel(
     const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
     const float *__restrict__ vb, const uint8_t *__restrict__ mask_f,
     const uint8_t *__restrict__ mask_b, int rows, int cols, InterpTimes times, int nt,
-    void *__restrict__ out, int out_u8, uint8_t *__restrict__ flags,
+    void *__restrict__ out, int out_kind, uint8_t *__restrict__ flags,
     uint32_t *__restrict__ trusted) {
     frame_interp_body<Frame, false>(I0, I1, uf, vf, ub, vb, mask_f, mask_b, nullptr, rows, cols,
-                                    times, nt, out, out_u8, flags, trusted);
+                                    times, nt, out, out_kind, flags, trusted);
 }
 
 // KIP: the same over KS's cells [batch][nt][rows][cols]
@@ -296,25 +326,28 @@ __global__ __launch_bounds__(kInterpThreads) void hs_frame_interp_proj_kernel(
     const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
     const float *__restrict__ vb, const uint8_t *__restrict__ mask_f,
     const uint8_t *__restrict__ mask_b, const uint64_t *__restrict__ cells, int rows, int cols,
-    InterpTimes times, int nt, void *__restrict__ out, int out_u8, uint8_t *__restrict__ flags,
-    uint32_t *__restrict__ trusted) {
+    InterpTimes times, int nt, void *__restrict__ out, int out_kind,
+    uint8_t *__restrict__ flags, uint32_t *__restrict__ trusted) {
     frame_interp_body<Frame, true>(I0, I1, uf, vf, ub, vb, mask_f, mask_b, cells, rows, cols,
-                                   times, nt, out, out_u8, flags, trusted);
+                                   times, nt, out, out_kind, flags, trusted);
 }
 
 // `times` is read here, on the host.  The grid is capped at what a CU holds
 // (Frame::kBlocksPerCu blocks of four waves): more blocks would wait for a
 // slot and only add atomics on the counts, which share a cache line.  With
-// `cells` the launch is KIP's.
+// `cells` the launch is KIP's.  out_kind: kOutF32, kOutU8 or, for a frame that
+// has it, kOutU16.
 template <typename Frame>
 hipError_t launch_frame_interp_as(const void *I0, const void *I1, int rows, int cols, int batch,
                                   const float *uf, const float *vf, const float *ub,
                                   const float *vb, const uint8_t *mask_f, const uint8_t *mask_b,
-                                  const float *times, int nt, void *out, bool out_u8,
+                                  const float *times, int nt, void *out, int out_kind,
                                   uint8_t *flags, uint32_t *trusted, hipStream_t s,
                                   const uint64_t *cells = nullptr) {
     using Elem = typename Frame::Elem;
     if (nt < 1 || nt > kInterpMaxTimes) return hipErrorInvalidValue;
+    if (out_kind != kOutF32 && out_kind != kOutU8 && !(Frame::kU16Out && out_kind == kOutU16))
+        return hipErrorInvalidValue;
     InterpTimes tm{};
     for (int k = 0; k < nt; ++k) tm.t[k] = times[k];
     const size_t plane = (size_t)rows * cols;
@@ -324,11 +357,11 @@ hipError_t launch_frame_interp_as(const void *I0, const void *I1, int rows, int 
     if (cells)
         hipLaunchKernelGGL(hs_frame_interp_proj_kernel<Frame>, grd, blk, 0, s, (const Elem *)I0,
                            (const Elem *)I1, uf, vf, ub, vb, mask_f, mask_b, cells, rows, cols, tm,
-                           nt, out, out_u8 ? 1 : 0, flags, trusted);
+                           nt, out, out_kind, flags, trusted);
     else
         hipLaunchKernelGGL(hs_frame_interp_kernel<Frame>, grd, blk, 0, s, (const Elem *)I0,
                            (const Elem *)I1, uf, vf, ub, vb, mask_f, mask_b, rows, cols, tm, nt,
-                           out, out_u8 ? 1 : 0, flags, trusted);
+                           out, out_kind, flags, trusted);
     return hipGetLastError();
 }
 

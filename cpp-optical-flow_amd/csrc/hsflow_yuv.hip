@@ -42,6 +42,14 @@
 //     loads the sample's own four blocks, for KIY's value.  Thread map, stores
 //     and fallback verdict are KIY's.
 //
+//  16-bit samples (ChromaFrame16; yuv420p10le .. p16le, P010 .. P016): the same
+//     kernels over a policy whose element is uint16_t.  I420-16 samples the two
+//     planes as KI samples a 16-bit grey plane and stores through pairs of
+//     lanes; NV12-16 holds a sample's U and V in one dword, so a tap is one
+//     (unaligned) dword load and a lane's U16 output one dword store.  A U16
+//     output is round_u16 of the f32 value.  8 B read and 4 or 8 B written per
+//     sample and time.
+//
 // Traffic: 16 B per luma pixel of flows once (64 B per chroma sample) and, per
 // time, 4 B of chroma read (the taps of neighbouring samples overlap) and 2 or
 // 8 B written per sample; at one time the flows bound the kernel, every further
@@ -93,14 +101,15 @@ __device__ __forceinline__ float fallback_value(int mode, float tt, float a, flo
     return tt == 0.0f ? a : (tt == 1.0f ? c : __builtin_fmaf(1.0f - tt, a, tt * c));
 }
 
+// out_kind: kOutF32 or the frame's own integer type (the launch has checked)
 template <typename Frame>
-__device__ __forceinline__ void store_sample(void *__restrict__ out, int out_u8, size_t frame,
+__device__ __forceinline__ void store_sample(void *__restrict__ out, int out_kind, size_t frame,
                                              int plane, int pk, int t, const Uv &o) {
     const bool valid = pk < plane;
     const int q0 = pk - (t & 3);  // the quad's first sample, >= 0
     const bool whole = q0 + 3 < plane;
-    if (out_u8) {  // uniform
-        Frame::store_u8(out, frame, plane, pk, q0, whole, valid, o, t);
+    if (out_kind != kOutF32) {  // uniform
+        Frame::store_int(out, frame, plane, pk, q0, whole, valid, o, t);
     } else if (valid) {
         Frame::store_f32(out, frame, plane, pk, o);
     }
@@ -108,10 +117,11 @@ __device__ __forceinline__ void store_sample(void *__restrict__ out, int out_u8,
 
 // KF's value for every sample of a failed pair, over KIY's tiles
 template <typename Frame>
-__device__ __forceinline__ void fallback_tiles(const uint8_t *__restrict__ p0,
-                                               const uint8_t *__restrict__ p1, int plane, int pair,
-                                               int mode, const InterpTimes &times, int nt,
-                                               void *__restrict__ out, int out_u8) {
+__device__ __forceinline__ void fallback_tiles(const typename Frame::Elem *__restrict__ p0,
+                                               const typename Frame::Elem *__restrict__ p1,
+                                               int plane, int pair, int mode,
+                                               const InterpTimes &times, int nt,
+                                               void *__restrict__ out, int out_kind) {
     constexpr int kThreads = kInterpThreads, kPix = kInterpPix, kTile = kInterpTile;
     const int t = threadIdx.x;
     const int ntiles = (plane + kTile - 1) / kTile;
@@ -131,7 +141,7 @@ __device__ __forceinline__ void fallback_tiles(const uint8_t *__restrict__ p0,
             for (int k = 0; k < kPix; ++k) {
                 const Uv o{{fallback_value(mode, tt, a[k].c[0], c[k].c[0]),
                             fallback_value(mode, tt, a[k].c[1], c[k].c[1])}};
-                store_sample<Frame>(out, out_u8, (size_t)pair * nt + ti, plane, pk[k], t, o);
+                store_sample<Frame>(out, out_kind, (size_t)pair * nt + ti, plane, pk[k], t, o);
             }
         }
     }
@@ -140,22 +150,23 @@ __device__ __forceinline__ void fallback_tiles(const uint8_t *__restrict__ p0,
 // grid (blocks per pair, batch); rows, cols: the luma's
 template <typename Frame>
 __global__ __launch_bounds__(kInterpThreads) void hs_chroma_interp_kernel(
-    const uint8_t *__restrict__ C0, const uint8_t *__restrict__ C1, const float *__restrict__ uf,
-    const float *__restrict__ vf, const float *__restrict__ ub, const float *__restrict__ vb,
-    const uint32_t *__restrict__ counts_f, const uint32_t *__restrict__ counts_b,
-    uint64_t min_consistent, int mode, int rows, int cols, InterpTimes times, int nt,
-    void *__restrict__ out, int out_u8) {
+    const typename Frame::Elem *__restrict__ C0, const typename Frame::Elem *__restrict__ C1,
+    const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
+    const float *__restrict__ vb, const uint32_t *__restrict__ counts_f,
+    const uint32_t *__restrict__ counts_b, uint64_t min_consistent, int mode, int rows, int cols,
+    InterpTimes times, int nt, void *__restrict__ out, int out_kind) {
     constexpr int kThreads = kInterpThreads, kPix = kInterpPix, kTile = kInterpTile;
     const int rc = rows >> 1, cc = cols >> 1;
     const int plane = rc * cc;  // <= 2^27
     const int pair = blockIdx.y, t = threadIdx.x;
     const int ntiles = (plane + kTile - 1) / kTile;
-    const uint8_t *p0 = C0 + (size_t)pair * 2 * plane, *p1 = C1 + (size_t)pair * 2 * plane;
+    const typename Frame::Elem *p0 = C0 + (size_t)pair * 2 * plane,
+                               *p1 = C1 + (size_t)pair * 2 * plane;
 
     // block-uniform, as KF: element 0 of a pair's three counts is HSFLOW_CONSISTENT
     if (counts_f &&
         (uint64_t)counts_f[(size_t)pair * 3] + counts_b[(size_t)pair * 3] < min_consistent) {
-        fallback_tiles<Frame>(p0, p1, plane, pair, mode, times, nt, out, out_u8);
+        fallback_tiles<Frame>(p0, p1, plane, pair, mode, times, nt, out, out_kind);
         return;
     }
 
@@ -196,7 +207,7 @@ __global__ __launch_bounds__(kInterpThreads) void hs_chroma_interp_kernel(
                 const Uv s1 = Frame::sample(p1, plane, cc, t1);
                 const float wt = blend_weight(in0, in1, tt);
                 const Uv o{{blend(wt, s0.c[0], s1.c[0]), blend(wt, s0.c[1], s1.c[1])}};
-                store_sample<Frame>(out, out_u8, (size_t)pair * nt + ti, plane, pk[k], t, o);
+                store_sample<Frame>(out, out_kind, (size_t)pair * nt + ti, plane, pk[k], t, o);
             }
         }
     }
@@ -260,23 +271,25 @@ __global__ __launch_bounds__(256) void hs_cells_down_kernel(
 // [batch][nt][rows][cols]
 template <typename Frame>
 __global__ __launch_bounds__(kInterpThreads) void hs_chroma_interp_proj_kernel(
-    const uint8_t *__restrict__ C0, const uint8_t *__restrict__ C1, const float *__restrict__ uf,
-    const float *__restrict__ vf, const float *__restrict__ ub, const float *__restrict__ vb,
-    const unsigned long long *__restrict__ cells, const uint32_t *__restrict__ counts_f,
-    const uint32_t *__restrict__ counts_b, uint64_t min_consistent, int mode, int rows, int cols,
-    InterpTimes times, int nt, void *__restrict__ out, int out_u8) {
+    const typename Frame::Elem *__restrict__ C0, const typename Frame::Elem *__restrict__ C1,
+    const float *__restrict__ uf, const float *__restrict__ vf, const float *__restrict__ ub,
+    const float *__restrict__ vb, const unsigned long long *__restrict__ cells,
+    const uint32_t *__restrict__ counts_f, const uint32_t *__restrict__ counts_b,
+    uint64_t min_consistent, int mode, int rows, int cols, InterpTimes times, int nt,
+    void *__restrict__ out, int out_kind) {
     constexpr int kThreads = kInterpThreads, kPix = kInterpPix, kTile = kInterpTile;
     const int rc = rows >> 1, cc = cols >> 1;
     const int plane = rc * cc;  // <= 2^27
     const int lplane = rows * cols;  // <= 2^29 - 4
     const int pair = blockIdx.y, t = threadIdx.x;
     const int ntiles = (plane + kTile - 1) / kTile;
-    const uint8_t *p0 = C0 + (size_t)pair * 2 * plane, *p1 = C1 + (size_t)pair * 2 * plane;
+    const typename Frame::Elem *p0 = C0 + (size_t)pair * 2 * plane,
+                               *p1 = C1 + (size_t)pair * 2 * plane;
 
     // block-uniform, as KF: element 0 of a pair's three counts is HSFLOW_CONSISTENT
     if (counts_f &&
         (uint64_t)counts_f[(size_t)pair * 3] + counts_b[(size_t)pair * 3] < min_consistent) {
-        fallback_tiles<Frame>(p0, p1, plane, pair, mode, times, nt, out, out_u8);
+        fallback_tiles<Frame>(p0, p1, plane, pair, mode, times, nt, out, out_kind);
         return;
     }
 
@@ -335,41 +348,40 @@ __global__ __launch_bounds__(kInterpThreads) void hs_chroma_interp_proj_kernel(
                 const Uv s1 = Frame::sample(p1, plane, cc, t1);
                 const float wt = blend_weight(in0, in1, tt);
                 const Uv o{{blend(wt, s0.c[0], s1.c[0]), blend(wt, s0.c[1], s1.c[1])}};
-                store_sample<Frame>(out, out_u8, (size_t)pair * nt + ti, plane, pk[k], t, o);
+                store_sample<Frame>(out, out_kind, (size_t)pair * nt + ti, plane, pk[k], t, o);
             }
         }
     }
 }
-
-// KIYP's cap: 111 (NV12) to 120 (I420) VGPRs, four waves per SIMD, four blocks
-// of four waves per CU
-constexpr int kProjBlocksPerCu = 4;
 
 int g_nv12_wide = 0;
 
 // `times` is read here, on the host; KI's grid on the chroma plane.  With
 // `cells` the launch is KIYP's.
 template <typename Frame>
-hipError_t launch_as(const uint8_t *c0, const uint8_t *c1, int rows, int cols, int batch,
+hipError_t launch_as(const void *c0v, const void *c1v, int rows, int cols, int batch,
                      const float *uf, const float *vf, const float *ub, const float *vb,
                      const uint32_t *counts_f, const uint32_t *counts_b, uint64_t min_consistent,
-                     int mode, const float *times, int nt, void *out, bool out_u8, hipStream_t s,
+                     int mode, const float *times, int nt, void *out, int out_kind, hipStream_t s,
                      const uint64_t *cells = nullptr) {
+    using Elem = typename Frame::Elem;
+    if (out_kind != kOutF32 && out_kind != Frame::kIntOut) return hipErrorInvalidValue;
+    const Elem *c0 = (const Elem *)c0v, *c1 = (const Elem *)c1v;
     InterpTimes tm{};
     for (int k = 0; k < nt; ++k) tm.t[k] = times[k];
     const size_t plane = (size_t)(rows / 2) * (cols / 2);
     const int ntiles = (int)((plane + kInterpTile - 1) / kInterpTile);
-    const int per_cu = cells ? kProjBlocksPerCu : Frame::kBlocksPerCu;
+    const int per_cu = cells ? Frame::kProjBlocksPerCu : Frame::kBlocksPerCu;
     const int cap = std::max(1, (per_cu * device_cus() + batch - 1) / batch);
     dim3 blk(kInterpThreads, 1, 1), grd(std::min(ntiles, cap), batch, 1);
     if (cells)
         hipLaunchKernelGGL(hs_chroma_interp_proj_kernel<Frame>, grd, blk, 0, s, c0, c1, uf, vf, ub,
                            vb, (const unsigned long long *)cells, counts_f, counts_b,
-                           min_consistent, mode, rows, cols, tm, nt, out, out_u8 ? 1 : 0);
+                           min_consistent, mode, rows, cols, tm, nt, out, out_kind);
     else
         hipLaunchKernelGGL(hs_chroma_interp_kernel<Frame>, grd, blk, 0, s, c0, c1, uf, vf, ub, vb,
                            counts_f, counts_b, min_consistent, mode, rows, cols, tm, nt, out,
-                           out_u8 ? 1 : 0);
+                           out_kind);
     return hipGetLastError();
 }
 
@@ -377,7 +389,7 @@ hipError_t launch_as(const uint8_t *c0, const uint8_t *c1, int rows, int cols, i
 
 int chroma_blocks_per_cu() { return ChromaFrame<kYuvI420, false>::kBlocksPerCu; }
 
-int chroma_proj_blocks_per_cu() { return kProjBlocksPerCu; }
+int chroma_proj_blocks_per_cu() { return ChromaFrame<kYuvI420, false>::kProjBlocksPerCu; }
 
 hipError_t launch_cells_down(const uint64_t *cells, int rows, int cols, int planes,
                              uint64_t *cells_c, hipStream_t s) {
@@ -398,21 +410,27 @@ int set_chroma_nv12_wide_loads(int on) {
     return prev;
 }
 
-hipError_t launch_chroma_interp(const uint8_t *c0, const uint8_t *c1, int layout, int rows,
-                                int cols, int batch, const float *uf, const float *vf,
+hipError_t launch_chroma_interp(const void *c0, const void *c1, int dtype_in, int layout,
+                                int rows, int cols, int batch, const float *uf, const float *vf,
                                 const float *ub, const float *vb, const uint32_t *counts_f,
                                 const uint32_t *counts_b, uint64_t min_consistent, int mode,
-                                const float *times, int nt, void *out, bool out_u8,
+                                const float *times, int nt, void *out, int out_kind,
                                 hipStream_t s, const uint64_t *cells) {
     if (nt < 1 || nt > kInterpMaxTimes || rows < 2 || cols < 2 || (rows | cols) & 1)
         return hipErrorInvalidValue;
+    if (dtype_in != 0 && dtype_in != 4) return hipErrorInvalidValue;  // HSFLOW_U8, HSFLOW_U16
     const auto go = [&](auto frame) {
         return launch_as<decltype(frame)>(c0, c1, rows, cols, batch, uf, vf, ub, vb, counts_f,
-                                          counts_b, min_consistent, mode, times, nt, out, out_u8,
-                                          s, cells);
+                                          counts_b, min_consistent, mode, times, nt, out,
+                                          out_kind, s, cells);
     };
+    if (layout != kYuvI420 && layout != kYuvNv12) return hipErrorInvalidValue;
+    if (dtype_in == 4) {
+        if (layout == kYuvI420) return go(ChromaFrame16<kYuvI420, false>{});
+        return g_nv12_wide ? go(ChromaFrame16<kYuvNv12, true>{})
+                           : go(ChromaFrame16<kYuvNv12, false>{});
+    }
     if (layout == kYuvI420) return go(ChromaFrame<kYuvI420, false>{});
-    if (layout != kYuvNv12) return hipErrorInvalidValue;
     return g_nv12_wide ? go(ChromaFrame<kYuvNv12, true>{}) : go(ChromaFrame<kYuvNv12, false>{});
 }
 

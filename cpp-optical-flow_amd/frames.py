@@ -193,6 +193,63 @@ class Y4MVideo:
         return np.fromfile(self.path, np.uint8, count=self.frame_bytes, offset=self.offsets[i])
 
 
+class Y4MVideo16:
+    """A high-bit-depth 4:2:0 YUV4MPEG2 stream: C420p10, C420p12, C420p14 or
+    C420p16, planar with 2-byte little-endian samples (ffmpeg's yuv420p10le ..
+    yuv420p16le).  `bit_depth`, `rows`, `cols` and len(); read_yuv(i) hands out
+    the packed I420 frame as it is stored, rows * cols * 3 / 2 uint16 samples,
+    for yuv.interpolate_yuv and interpolate_sequence_yuv.  An 8-bit stream is
+    Y4MVideo's and raises FrameError here."""
+    _DEPTHS = {"420p10": 10, "420p12": 12, "420p14": 14, "420p16": 16}
+
+    def __init__(self, path: str):
+        self.path = path
+        with open(path, "rb") as f:
+            head = f.readline()
+            if not head.startswith(b"YUV4MPEG2"):
+                raise FrameError(f"{path}: not a YUV4MPEG2 stream")
+            params = head.decode("ascii").split()[1:]
+            d = {p[0]: p[1:] for p in params}
+            self.cols, self.rows = int(d["W"]), int(d["H"])
+            cs = d.get("C", "420jpeg")
+            if cs not in self._DEPTHS:
+                raise FrameError(f"{path}: chroma {cs} unsupported (16-bit-sample "
+                                 f"{'/'.join(sorted(self._DEPTHS))} only; Y4MVideo reads 8-bit "
+                                 "streams)")
+            if self.rows < 2 or self.cols < 2 or self.rows % 2 or self.cols % 2:
+                raise FrameError(f"{path}: a 4:2:0 stream of 16-bit samples needs even rows "
+                                 f"and cols, not {self.cols}x{self.rows}")
+            self.bit_depth = self._DEPTHS[cs]
+            self.chroma = cs
+            self.full_range = "XCOLORRANGE=FULL" in params
+            self.frame_samples = self.rows * self.cols * 3 // 2
+            self.frame_bytes = 2 * self.frame_samples
+            self.offsets: List[int] = []
+            pos = len(head)
+            size = os.path.getsize(path)
+            while pos < size:
+                f.seek(pos)
+                line = f.readline()
+                if not line.startswith(b"FRAME"):
+                    raise FrameError(f"{path}: bad frame header at byte {pos}")
+                data = pos + len(line)
+                if data + self.frame_bytes > size:
+                    break  # truncated last frame
+                self.offsets.append(data)
+                pos = data + self.frame_bytes
+
+    def __len__(self):
+        return len(self.offsets)
+
+    def read_yuv(self, i: int) -> np.ndarray:
+        """The packed I420 frame as it is stored: rows * cols * 3 / 2 samples, Y
+        then U then V, uint16, no range expansion (yuv.split takes it apart)."""
+        if not 0 <= i < len(self.offsets):
+            raise FrameError(f"frame {i} outside [0, {len(self.offsets)})")
+        a = np.fromfile(self.path, "<u2", count=self.frame_samples, offset=self.offsets[i])
+        return a.astype(np.uint16, copy=False)
+
+
 def write_y4m(path: str, frames: Iterable[np.ndarray], full_range: bool = True) -> None:
     """Gray frames as a 'Cmono' YUV4MPEG2 stream (test fixtures, examples)."""
     frames = list(frames)
@@ -206,19 +263,27 @@ def write_y4m(path: str, frames: Iterable[np.ndarray], full_range: bool = True) 
 
 
 def write_y4m_420(path: str, frames: Iterable[np.ndarray], rows: int, cols: int,
-                  full_range: bool = False) -> None:
+                  full_range: bool = False, depth: int = 8) -> None:
     """Packed I420 frames (uint8, rows * cols * 3 / 2 bytes each; rows and cols
-    even) as a 'C420jpeg' YUV4MPEG2 stream, byte for byte."""
+    even) as a 'C420jpeg' YUV4MPEG2 stream, byte for byte.  depth 10, 12, 14 or
+    16: uint16 frames as a 'C420p<depth>' stream of 2-byte little-endian samples
+    (Y4MVideo16 reads it); a sample that does not fit the depth raises FrameError."""
     if rows < 2 or cols < 2 or rows % 2 or cols % 2:
         raise FrameError(f"a 4:2:0 stream needs even rows and cols, not {rows}x{cols}")
+    if depth not in (8, 10, 12, 14, 16):
+        raise FrameError(f"depth {depth} is not 8, 10, 12, 14 or 16")
+    tag = b"420jpeg" if depth == 8 else b"420p%d" % depth
     with open(path, "wb") as f:
-        f.write(b"YUV4MPEG2 W%d H%d F25:1 Ip A1:1 C420jpeg%s\n"
-                % (cols, rows, b" XCOLORRANGE=FULL" if full_range else b""))
+        f.write(b"YUV4MPEG2 W%d H%d F25:1 Ip A1:1 C%s%s\n"
+                % (cols, rows, tag, b" XCOLORRANGE=FULL" if full_range else b""))
         for fr in frames:
-            a = np.ascontiguousarray(fr, np.uint8).reshape(-1)
+            a = np.ascontiguousarray(fr, np.uint8 if depth == 8 else "<u2").reshape(-1)
             if a.size != rows * cols * 3 // 2:
                 raise FrameError(f"a packed {rows}x{cols} 4:2:0 frame has "
-                                 f"{rows * cols * 3 // 2} bytes, not {a.size}")
+                                 f"{rows * cols * 3 // 2} {'bytes' if depth == 8 else 'samples'}"
+                                 f", not {a.size}")
+            if depth not in (8, 16) and a.size and int(a.max()) >> depth:
+                raise FrameError(f"a sample of {int(a.max())} does not fit a depth of {depth} bits")
             f.write(b"FRAME\n")
             f.write(a.tobytes())
 
@@ -452,7 +517,13 @@ def interpolate_sequence_yuv(src, factor: int, levels: int, warps: int, window: 
     own grid.  context, prefilter, smoothness, temporal, finest, fallback and
     cuts as in interpolate_sequence.  projection None: none (a context with the
     projection on is refused); 0 or 1: yuv.interpolate_yuv(projection=), luma and
-    chroma through the same winners."""
+    chroma through the same winners.
+    A source whose read_yuv returns uint16 (Y4MVideo16 on a C420p10 .. p16
+    stream) gives uint16 frames the same way; projection None is then 0.  alpha
+    is used as given and is not rescaled: a frame scaled by k behaves like alpha
+    divided by k, so pass alpha x 4 for 10-bit LSB-aligned content (alpha x 256
+    for P010-style MSB-aligned samples) relative to the 8-bit recommendation of
+    about 100."""
     factor = int(factor)
     if factor < 1:
         raise ValueError("factor must be at least 1")
@@ -477,7 +548,7 @@ def interpolate_sequence_yuv(src, factor: int, levels: int, warps: int, window: 
                     mode.enter_context(seq.sequence(ctx))  # starts without a prediction
                     started = True
                 mid = yuv.interpolate_yuv(ctx, prev, nxt, times, levels, warps, window, iters,
-                                          alpha, rows, cols, median=median, out_dtype=np.uint8,
+                                          alpha, rows, cols, median=median, out_dtype=prev.dtype,
                                           prefilter=prefilter, smoothness=smoothness,
                                           finest=finest, fallback=fallback,
                                           projection=projection)
@@ -494,7 +565,10 @@ def _yuv_frame(src, i: int) -> np.ndarray:
         raise FrameError("interpolate_sequence_yuv needs a 4:2:0 source with read_yuv(i) "
                          "(Y4MVideo); for BGR frames use interpolate_sequence")
     a = np.asarray(src.read_yuv(i))
-    if a.dtype != np.uint8 or a.size != src.rows * src.cols * 3 // 2:
+    if a.dtype == np.uint16 and a.size != src.rows * src.cols * 3 // 2:
+        raise FrameError(f"frame {i} is not a packed 4:2:0 frame of {src.rows * src.cols * 3 // 2} "
+                         f"16-bit samples ({src.cols}x{src.rows}): it has {a.size}")
+    if a.dtype not in (np.uint8, np.uint16) or a.size != src.rows * src.cols * 3 // 2:
         raise FrameError(f"frame {i} is not a packed 8-bit 4:2:0 frame of "
                          f"{src.cols}x{src.rows}")
     return a.reshape(-1)

@@ -41,6 +41,7 @@ HSFLOW_ERR_OOM = -3
 HSFLOW_ERR_NODEV = -4
 HSFLOW_ERR_SIZE = -5
 U8, F32, F64, F16 = 0, 1, 2, 3
+_U16 = 4  # HSFLOW_U16, 16-bit samples: the 16-bit YUV 4:2:0 calls only (yuv.U16)
 MAX_LEVELS = 8
 MAX_WARPS = 16
 SOBEL_GAIN = 8.0
@@ -363,6 +364,15 @@ def _prototypes():
         "hsflow_flow_interp_yuv_pj": (i, [vp, vp, vp, i, i, i] + solve_d + thresholds
                                       + [fp, i, i, vpp, i, vpp, vp]),
         "hsflow_chroma_interp_proj_blocks_per_cu": (i, []),
+        # ... on 16-bit samples (yuv420p10le .. p16le, P010 .. P016): KIY / KIYP
+        # (cells null or given), the fused and the host call
+        "hsflow_chroma_interp16_device": (i, [vp, vp, i] + shape + flows + [vp, vp, vp] + fb
+                                          + [fp, i, vp, i, vp]),
+        "hsflow_flow_interp_yuv16_device": (i, [vp, vp, vp, vp, i] + shape + solve_lv + thresholds
+                                            + [fp, i, i, vp, vp, i, vp, vp, vp] + pf + sm + init
+                                            + fb + tail),
+        "hsflow_flow_interp_yuv16": (i, [vp, vp, vp, i, i, i] + solve_d + thresholds
+                                     + [fp, i, i, vpp, i, vpp, vp]),
         "hsflow_bgr_to_gray": (i, [vp, i, i, sz, vp, sz]),
         "hsflow_bgr_to_gray_device": (i, [vp] + shape + [vp, vp]),
         "hsflow_flow_bgr": (i, host_bgr_pair + plain_d + host_uv),
@@ -1063,9 +1073,16 @@ def _ws_args(workspace):
     return workspace.data_ptr(), workspace.numel()
 
 
+def _is16(dtype) -> bool:
+    """A torch dtype that holds 16-bit samples: uint16, or int16 read as the same
+    16 bits (torch has few uint16 operators)."""
+    return dtype == torch.int16 or dtype == getattr(torch, "uint16", torch.int16)
+
+
 def _out_code(out) -> int:
-    """The code of a warped or interpolated device output: uint8, else float32."""
-    return U8 if out.dtype == torch.uint8 else F32
+    """The code of a warped or interpolated device output: uint8, 16-bit samples
+    (the 16-bit YUV calls), else float32."""
+    return U8 if out.dtype == torch.uint8 else (_U16 if _is16(out.dtype) else F32)
 
 
 def _dims(shape):
@@ -1146,23 +1163,28 @@ def _check_output(want, shape, dtype, device, name):
     return want
 
 
-def _out_frames(out, shape, out_dtype, device):
+def _out_frames(out, shape, out_dtype, device, wide=False):
     """The `out` of a colour warp or an interpolation: the given tensor, or a
-    new one of out_dtype (float32 when None); float32 or uint8, of `shape`."""
+    new one of out_dtype (float32 when None); float32 or uint8, of `shape`.
+    wide: of 16-bit frames, float32 or uint16 (int16: the same bits)."""
     if out is None:
         out = torch.empty(shape, dtype=out_dtype or torch.float32, device=device)
-    if out.dtype not in (torch.float32, torch.uint8):
+    if wide:
+        if out.dtype != torch.float32 and not _is16(out.dtype):
+            raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint16 (int16) for 16-bit "
+                              "frames")
+    elif out.dtype not in (torch.float32, torch.uint8):
         raise HsflowError(HSFLOW_ERR_ARG, "out: need float32 or uint8")
     return _check_output(out, shape, out.dtype, device, "out")
 
 
-def _interp_outputs(frames, channels, nt, out, out_dtype, flags, trusted):
+def _interp_outputs(frames, channels, nt, out, out_dtype, flags, trusted, wide=False):
     """out / flags / trusted of an interpolation of `nt` times of `frames`,
     [B, H, W] + channels or [H, W] + channels (channels () or (3,)):
     [B, nt, H, W] + channels, [B, nt, H, W] and [B, nt]."""
     plane = tuple(frames.shape[:frames.dim() - len(channels)])
     shape = plane[:-2] + (nt,) + plane[-2:]
-    out = _out_frames(out, shape + channels, out_dtype, frames.device)
+    out = _out_frames(out, shape + channels, out_dtype, frames.device, wide)
     flags = _check_output(flags, shape, torch.uint8, frames.device, "flags")
     trusted = _check_output(trusted, (math.prod(plane[:-2]), nt), torch.int32, frames.device,
                             "trusted")

@@ -24,6 +24,20 @@ flow_interp_yuv_proj_device, interpolate_yuv(projection=) and
 frames.interpolate_sequence_yuv(projection=) are the fused, the host and the
 clip form.
 
+16-bit samples (include/hsflow.h, "16-bit YUV 4:2:0"): yuv420p10le .. p16le are
+the I420 layout and P010 .. P016 the NV12 layout with 2-byte samples.  Every
+device call here takes such frames as torch.uint16 tensors -- or torch.int16,
+read as the same 16 bits, because torch has few uint16 operators -- and
+interpolate_yuv as np.uint16 arrays; they route to the 16-bit entry points and
+return uint16 (int16 where an int16 `out` is given) or float32.  A sample is its
+value, 0 .. 65535: the results are, bit for bit, those of the same values as
+float32 planes in the pieces named above, the pyramid never rounded to integers
+(a 16-bit pair is never treated as 8-bit), a uint16 output floor(x + 0.5)
+clamped to 0 .. 65535.  A frame scaled by k behaves like alpha divided by k: use
+alpha x 4 for 10-bit LSB-aligned content and alpha x 256 for P010, relative to
+the 8-bit recommendation of about 100.  A P010 result is a valid P016 frame:
+the low six bits of its samples are in general not zero.
+
 Everything here calls the HIP path in libhsflow.so through hsflow's front ends.
 """
 from __future__ import annotations
@@ -42,6 +56,8 @@ except Exception:  # pragma: no cover
 
 # layouts (HSFLOW_YUV_*)
 YUV_I420, YUV_NV12 = 1, 2
+# HSFLOW_U16: the dtype code of 16-bit samples, taken by the 16-bit calls only
+U16 = hsflow._U16
 LAYOUTS = {"i420": YUV_I420, "nv12": YUV_NV12, YUV_I420: YUV_I420, YUV_NV12: YUV_NV12}
 # KIY's tile: a block takes 512 consecutive chroma samples of a pair at a time
 CHROMA_TILE = 512
@@ -62,7 +78,7 @@ def _even(rows, cols):
 
 
 def frame_bytes(rows: int, cols: int) -> int:
-    """Bytes of a packed 8-bit 4:2:0 frame."""
+    """Bytes of a packed 8-bit 4:2:0 frame: its samples, at any depth."""
     _even(rows, cols)
     return rows * cols * 3 // 2
 
@@ -130,12 +146,15 @@ def _chroma_pair(c0, c1, layout):
     belong to: I420 [B, 2, rc, cc] or [2, rc, cc], NV12 [B, rc, cc, 2] or
     [rc, cc, 2]."""
     for t, name in ((c0, "c0"), (c1, "c1")):
-        if torch is None or not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or \
+        if torch is None or not isinstance(t, torch.Tensor) or \
+                not (t.dtype == torch.uint8 or hsflow._is16(t.dtype)) or \
                 t.dim() not in (3, 4) or not t.is_cuda or not t.is_contiguous():
             raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, f"{name}: need a contiguous uint8 "
                                      "CUDA tensor, I420 [B, 2, rc, cc] or NV12 [B, rc, cc, 2]")
     if c1.shape != c0.shape:
         raise hsflow.HsflowError(hsflow.HSFLOW_ERR_SIZE, "c0/c1 differ in shape")
+    if c1.dtype != c0.dtype:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_SIZE, "c0/c1 differ in dtype")
     batch = c0.shape[0] if c0.dim() == 4 else 1
     shape = tuple(c0.shape[-3:])
     two, (rc, cc) = (shape[0], shape[1:]) if layout == YUV_I420 else (shape[2], shape[:2])
@@ -148,9 +167,11 @@ def _chroma_pair(c0, c1, layout):
 
 def _chroma_out(c0, nt, out, out_dtype):
     """out_c of `nt` times: [B, nt] + a chroma frame's shape (no B for a single
-    frame's chroma), float32 (default) or uint8."""
+    frame's chroma), float32 (default) or uint8; of 16-bit chroma float32 or
+    uint16 (int16)."""
     lead = tuple(c0.shape[:-3])
-    return hsflow._out_frames(out, lead + (nt,) + tuple(c0.shape[-3:]), out_dtype, c0.device)
+    return hsflow._out_frames(out, lead + (nt,) + tuple(c0.shape[-3:]), out_dtype, c0.device,
+                              wide=hsflow._is16(c0.dtype))
 
 
 def chroma_interp_device(c0, c1, uf, vf, ub, vb, times, layout=YUV_I420, counts_f=None,
@@ -164,7 +185,9 @@ def chroma_interp_device(c0, c1, uf, vf, ub, vb, times, layout=YUV_I420, counts_
     hsflow.consistency_device) and fallback (a fallback.Fallback): a pair that
     fails fallback.min_consistent(2 rc, 2 cc, min_share) gets
     fallback.frame_fallback_device's value.  out: float32 (default) or uint8,
-    [B, len(times)] + the chroma's shape.  Returns out.  Stream-ordered."""
+    [B, len(times)] + the chroma's shape.  Returns out.  Stream-ordered.
+    16-bit chroma (uint16 or int16 tensors; hsflow_chroma_interp16_device): the
+    same on the sample values, out float32 or uint16."""
     lay = _layout(layout)
     dims = _chroma_pair(c0, c1, lay)
     hsflow._check_planes(dims, uf=uf, vf=vf, ub=ub, vb=vb)
@@ -176,7 +199,11 @@ def chroma_interp_device(c0, c1, uf, vf, ub, vb, times, layout=YUV_I420, counts_
         import fallback as _fallback
         counts = [_fallback._counts(c, dims[2], c0.device, n)
                   for c, n in ((counts_f, "counts_f"), (counts_b, "counts_b"))]
-    hsflow._device_call("hsflow_chroma_interp_device", c0.device, stream, c0.data_ptr(),
+    if hsflow._is16(c0.dtype):  # cells null: KIY's definition
+        counts = [None] + counts
+    name = "hsflow_chroma_interp16_device" if hsflow._is16(c0.dtype) else \
+        "hsflow_chroma_interp_device"
+    hsflow._device_call(name, c0.device, stream, c0.data_ptr(),
                         c1.data_ptr(), lay, *dims, uf.data_ptr(), vf.data_ptr(), ub.data_ptr(),
                         vb.data_ptr(), *counts, fb, tm, len(tm), out.data_ptr(),
                         hsflow._out_code(out))
@@ -229,8 +256,8 @@ def chroma_interp_proj_device(c0, c1, uf, vf, ub, vb, times, cells, layout=YUV_I
     (hsflow_chroma_interp_proj_device, KIYP): temporal.downflow_device of both
     flow pairs, cells_down_device and projection.frame_interp_device on the U
     and on the V planes, bit for bit, in one launch; a sample whose four luma
-    cells are empty is chroma_interp_device's.  Every other argument as there.
-    Returns out.  Stream-ordered."""
+    cells are empty is chroma_interp_device's.  Every other argument as there,
+    16-bit chroma included.  Returns out.  Stream-ordered."""
     lay = _layout(layout)
     dims = _chroma_pair(c0, c1, lay)
     hsflow._check_planes(dims, uf=uf, vf=vf, ub=ub, vb=vb)
@@ -245,7 +272,9 @@ def chroma_interp_proj_device(c0, c1, uf, vf, ub, vb, times, cells, layout=YUV_I
         import fallback as _fallback
         counts = [_fallback._counts(c, dims[2], c0.device, n)
                   for c, n in ((counts_f, "counts_f"), (counts_b, "counts_b"))]
-    hsflow._device_call("hsflow_chroma_interp_proj_device", c0.device, stream, c0.data_ptr(),
+    name = "hsflow_chroma_interp16_device" if hsflow._is16(c0.dtype) else \
+        "hsflow_chroma_interp_proj_device"
+    hsflow._device_call(name, c0.device, stream, c0.data_ptr(),
                         c1.data_ptr(), lay, *dims, uf.data_ptr(), vf.data_ptr(), ub.data_ptr(),
                         vb.data_ptr(), cells.data_ptr(), *counts, fb, tm, len(tm),
                         out.data_ptr(), hsflow._out_code(out))
@@ -287,7 +316,11 @@ def flow_interp_yuv_device(y0, c0, y1, c1, times, levels: int, warps: int, windo
     init and cut as in hsflow.flow_interp_bgr_device and
     temporal.flow_interp_device; there is no projection.  Returns (out_y, out_c,
     flags, trusted), and cut behind them where it was asked for.
-    Stream-ordered.  flow_interp_yuv_proj_device is the form with a projection."""
+    Stream-ordered.  flow_interp_yuv_proj_device is the form with a projection.
+    16-bit frames (uint16 or int16 luma and chroma;
+    hsflow_flow_interp_yuv16_device with projection 0): out_y, flags, trusted and
+    cut are hsflow.flow_interp_device's on the luma as float32 (any sample above
+    255 in the pair), out_y and out_c float32 or uint16."""
     return _flow_interp_yuv(None, y0, c0, y1, c1, times, levels, warps, window, iters, alpha,
                             layout, median, rel, abs, out_y, out_c, out_dtype, flags, trusted,
                             workspace, stream, prefilter, smoothness, finest, fallback, init, cut)
@@ -306,7 +339,7 @@ def flow_interp_yuv_proj_device(y0, c0, y1, c1, times, levels: int, warps: int, 
     flags (FLAG_HOLE included), trusted and cut are its -- and
     chroma_interp_proj_device on the flows, cells and counts it leaves in the
     workspace (flow_interp_proj_workspace_bytes).  Returns as
-    flow_interp_yuv_device.  Stream-ordered."""
+    flow_interp_yuv_device; 16-bit frames as there.  Stream-ordered."""
     return _flow_interp_yuv(int(projection), y0, c0, y1, c1, times, levels, warps, window, iters,
                             alpha, layout, median, rel, abs, out_y, out_c, out_dtype, flags,
                             trusted, workspace, stream, prefilter, smoothness, finest, fallback,
@@ -317,17 +350,21 @@ def _flow_interp_yuv(projection, y0, c0, y1, c1, times, levels, warps, window, i
                      layout, median, rel, abs, out_y, out_c, out_dtype, flags, trusted, workspace,
                      stream, prefilter, smoothness, finest, fallback, init, cut):
     """Both fused device calls: projection None is hsflow_flow_interp_yuv_device,
-    else hsflow_flow_interp_yuv_pj_device with that projection."""
+    else hsflow_flow_interp_yuv_pj_device with that projection; 16-bit frames:
+    hsflow_flow_interp_yuv16_device (projection None: 0)."""
     lay = _layout(layout)
     dims = hsflow._frame_pair(y0, y1)
-    if y0.dtype != torch.uint8:
+    wide = hsflow._is16(y0.dtype)
+    if y0.dtype != torch.uint8 and not wide:
         raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "y0, y1: need uint8 luma planes")
     if _chroma_pair(c0, c1, lay) != dims or c0.device != y0.device:
         raise hsflow.HsflowError(hsflow.HSFLOW_ERR_SIZE,
                                  "the chroma is not that of the luma planes' shape")
+    if c0.dtype != y0.dtype:
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "luma and chroma differ in dtype")
     tm = hsflow._times_array(times)
     out_y, flags, trusted = hsflow._interp_outputs(y0, (), len(tm), out_y, out_dtype, flags,
-                                                   trusted)
+                                                   trusted, wide)
     out_c = _chroma_out(c0, len(tm), out_c, out_y.dtype)
     if out_c.dtype != out_y.dtype:
         raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "out_y and out_c differ in dtype")
@@ -345,6 +382,8 @@ def _flow_interp_yuv(projection, y0, c0, y1, c1, times, levels, warps, window, i
     name = "hsflow_flow_interp_yuv_device" if projection is None else \
         "hsflow_flow_interp_yuv_pj_device"
     proj = () if projection is None else (projection,)
+    if wide:
+        name, proj = "hsflow_flow_interp_yuv16_device", (projection or 0,)
     hsflow._device_call(name, y0.device, stream, y0.data_ptr(),
                         c0.data_ptr(), y1.data_ptr(), c1.data_ptr(), lay, *dims,
                         *hsflow._solve_args(levels, warps, median, window, iters, alpha, finest),
@@ -372,12 +411,27 @@ def interpolate_yuv(ctx, f0, f1, times, levels: int, warps: int, window: int, it
     Context.last_cut set.  projection None: no projection, and a context with
     the projection on is refused; 0 or 1: that, whatever the context's setting
     (hsflow_flow_interp_yuv_pj: the luma through the projected path, the chroma
-    through KIYP)."""
+    through KIYP).
+    np.uint16 frames (rows * cols * 3 / 2 16-bit samples each;
+    hsflow_flow_interp_yuv16): the same on the sample values, out_dtype uint16
+    (what uint8, the default, stands for) or float32; projection None is 0, and
+    the context's projection setting is not consulted."""
     lay = _layout(layout)
     n = frame_bytes(rows, cols)
+    kinds = {np.asarray(f).dtype for f in (f0, f1)}
+    wide = np.dtype(np.uint16) in kinds
+    if wide:  # the default stands for the frames' own type
+        out_dtype = np.uint16 if np.dtype(out_dtype) == np.uint8 else out_dtype
     frames = []
     for f, name in ((f0, "f0"), (f1, "f1")):
         a = np.ascontiguousarray(f)
+        if wide:
+            if a.dtype != np.uint16 or a.size != n:
+                raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, f"{name}: need a packed uint16 "
+                                         f"frame of {n} samples ({rows}x{cols} 4:2:0), as the "
+                                         f"other frame is; got {a.dtype} of {a.size}")
+            frames.append(a)
+            continue
         if a.dtype != np.uint8 or a.size != n:
             raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, f"{name}: need a packed uint8 frame "
                                      f"of {n} bytes ({rows}x{cols} 4:2:0)")
@@ -385,7 +439,10 @@ def interpolate_yuv(ctx, f0, f1, times, levels: int, warps: int, window: int, it
     tm = hsflow._times_array(times)
     nt = len(tm)
     out = np.empty((nt, n), out_dtype)
-    if out.dtype not in (np.uint8, np.float32):
+    if wide and out.dtype not in (np.uint16, np.float32):
+        raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "out_dtype: need uint16 or float32 for "
+                                 "uint16 frames")
+    if not wide and out.dtype not in (np.uint8, np.float32):
         raise hsflow.HsflowError(hsflow.HSFLOW_ERR_ARG, "out_dtype: need uint8 or float32")
     flags = np.empty((nt, rows, cols), np.uint8) if with_flags else None
     trusted = np.zeros(nt, np.uint32) if with_flags else None
@@ -394,9 +451,12 @@ def interpolate_yuv(ctx, f0, f1, times, levels: int, warps: int, window: int, it
     fplanes = (vp * nt)(*[flags[k].ctypes.data for k in range(nt)]) if with_flags else None
     name = "hsflow_flow_interp_yuv" if projection is None else "hsflow_flow_interp_yuv_pj"
     proj = () if projection is None else (int(projection),)
+    if wide:
+        name, proj = "hsflow_flow_interp_yuv16", (int(projection or 0),)
     ctx._call_with(prefilter, smoothness, name, frames[0].ctypes.data,
                    frames[1].ctypes.data, lay, int(rows), int(cols),
                    *hsflow._solve_args(levels, warps, median, window, iters, alpha), float(rel),
-                   float(abs), tm, nt, *proj, planes, hsflow._dtype_code(out), fplanes,
+                   float(abs), tm, nt, *proj, planes,
+                   U16 if out.dtype == np.uint16 else hsflow._dtype_code(out), fplanes,
                    trusted.ctypes.data if with_flags else None, finest=finest, fallback=fallback)
     return (out, flags, trusted) if with_flags else out

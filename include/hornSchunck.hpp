@@ -122,22 +122,40 @@ class hornSchunck {
     // conversion, the luma is the grey frame.  frames[k] is created like the
     // inputs.  The settings above apply.  projection -1: none, and with the
     // projection setting on the call throws; 0 or 1: that, whatever the setting
-    // (hsflow_flow_interp_yuv_pj).
+    // (hsflow_flow_interp_yuv_pj).  Two CV_16UC1 frames of the same shape are
+    // frames of 16-bit samples (yuv420p10le .. p16le, P010 .. P016) and give
+    // CV_16UC1 frames (hsflow_flow_interp_yuv16; projection -1 stands for 0).
     void getFrameInterpYuv(const cv::Mat &imagePrev, const cv::Mat &imageNext,
                            const std::vector<float> &times, int levels, int warps, int median,
                            std::vector<cv::Mat> &frames, int layout = HSFLOW_YUV_I420,
                            int projection = -1) {
         sync_params();
         if (imagePrev.empty() || imageNext.empty()) CV_Error(cv::Error::StsBadArg, "empty image");
-        if (imagePrev.type() != CV_8UC1 || imageNext.type() != CV_8UC1)
+        const bool wide = imagePrev.type() == CV_16UC1 && imageNext.type() == CV_16UC1;
+        if (!wide && (imagePrev.type() != CV_8UC1 || imageNext.type() != CV_8UC1))
             CV_Error(cv::Error::StsBadArg, "a 4:2:0 frame is CV_8UC1 of rows * 3 / 2 x cols");
         if (imagePrev.rows != imageNext.rows || imagePrev.cols != imageNext.cols)
             CV_Error(cv::Error::StsBadArg, "Image sizes are different");
-        if (imagePrev.rows % 3 || imagePrev.step != (size_t)imagePrev.cols ||
-            imageNext.step != (size_t)imageNext.cols)
+        const size_t dense = (size_t)imagePrev.cols * (wide ? 2 : 1);
+        if (imagePrev.rows % 3 || imagePrev.step != dense || imageNext.step != dense)
             CV_Error(cv::Error::StsBadArg,
                      "a 4:2:0 frame is continuous and rows * 3 / 2 rows high");
         const int rows = imagePrev.rows / 3 * 2, cols = imagePrev.cols;
+        if (wide) {  // CV_16UC1: 16-bit samples in and out (hsflow_flow_interp_yuv16)
+            std::vector<std::vector<uint16_t>> packed16;
+            guarded([&] {
+                impl_.getFrameInterpYuv((const uint16_t *)imagePrev.data,
+                                        (const uint16_t *)imageNext.data, layout, rows, cols,
+                                        times, levels, warps, median, packed16, nullptr,
+                                        projection);
+            });
+            frames.resize(packed16.size());
+            for (size_t k = 0; k < packed16.size(); ++k) {
+                frames[k].create(imagePrev.rows, cols, CV_16UC1);
+                std::memcpy(frames[k].data, packed16[k].data(), packed16[k].size() * 2);
+            }
+            return;
+        }
         std::vector<std::vector<uint8_t>> packed;
         guarded([&] {
             impl_.getFrameInterpYuv(imagePrev.data, imageNext.data, layout, rows, cols, times,

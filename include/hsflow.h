@@ -54,8 +54,10 @@ enum {
 };
 
 /* Element types.  U8 = CV_8UC1, F32 = CV_32FC1, F64 = CV_64FC1,
- * F16 = CV_16FC1 (config 5 inputs; input only). */
-enum { HSFLOW_U8 = 0, HSFLOW_F32 = 1, HSFLOW_F64 = 2, HSFLOW_F16 = 3 };
+ * F16 = CV_16FC1 (config 5 inputs; input only), U16 = CV_16UC1 (the 16-bit
+ * YUV 4:2:0 calls only, "16-bit YUV 4:2:0" below; every other call refuses it
+ * as it refuses an unknown code). */
+enum { HSFLOW_U8 = 0, HSFLOW_F32 = 1, HSFLOW_F64 = 2, HSFLOW_F16 = 3, HSFLOW_U16 = 4 };
 
 /* Largest windowSize accepted (hornSchunck.cpp:53 allows any; OpenCV would
  * take a few seconds per iteration at this size already). */
@@ -1326,7 +1328,8 @@ int hsflow_ctx_last_cut(const hsflow_ctx *ctx);
  * the same flows on its own grid.
  *
  * rows and cols are the luma's and both even (else HSFLOW_ERR_ARG);
- * rc = rows / 2, cc = cols / 2.  8-bit samples, dense planes.
+ * rc = rows / 2, cc = cols / 2.  8-bit samples, dense planes (16-bit samples:
+ * "16-bit YUV 4:2:0" further down).
  *   HSFLOW_YUV_I420  chroma [batch][2][rc][cc], the U plane then the V plane
  *   HSFLOW_YUV_NV12  chroma [batch][rc][cc][2], U and V interleaved
  * A packed frame p of rows * cols * 3 / 2 samples is y = p, c = p + rows * cols
@@ -1416,6 +1419,9 @@ int hsflow_flow_interp_yuv(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t *f1
  * 512 chroma samples of one pair and strides), and how it fetches the two
  * adjacent taps of an NV12 row: as four bytes (0, the default) or as one
  * unaligned 32-bit load (1); same bits.  Returns the previous setting. */
+/* The figure is the 8-bit policies' (5).  The 16-bit policies run under caps of
+ * their own, never larger: I420-16 four blocks per CU, NV12-16 five
+ * (hsflow_chroma_interp16_device). */
 int hsflow_chroma_interp_blocks_per_cu(void);
 int hsflow_set_chroma_nv12_loads(int wide);
 
@@ -1499,7 +1505,88 @@ int hsflow_flow_interp_yuv_pj(hsflow_ctx *ctx, const uint8_t *f0, const uint8_t 
 
 /* The cap of KIYP's grid in blocks per compute unit (tiles of 512 chroma
  * samples of one pair, striding, as KIY). */
+/* The figure is the 8-bit policies' (4); with cells the 16-bit policies run
+ * under I420-16 three blocks per CU, NV12-16 four. */
 int hsflow_chroma_interp_proj_blocks_per_cu(void);
+
+/* ---- 16-bit YUV 4:2:0: yuv420p10le .. p16le (I420), P010 .. P016 (NV12) ------
+ * The calls above take 8-bit samples, dense planes.  These take the frames a
+ * 10-, 12- or 16-bit decoder hands out: the same two layouts with 2-byte
+ * little-endian samples, in and out.
+ *
+ * A 16-bit sample is its value as a number, 0 .. 65535, whatever the bit depth:
+ * yuv420p10le holds 0 .. 1023, P010 the value shifted left by 6.  Every kernel
+ * converts a frame element to float on load and computes in f32, so a U16 plane
+ * gives, bit for bit, what the same values give as an HSFLOW_F32 plane in the
+ * 8-bit section's definitions -- with one stated exception, the pyramid: a U16
+ * pair is never treated as 8-bit.  K1's integrality test (integers in [0, 255]
+ * make the pyramid round every level to integers) is not run on U16 frames; the
+ * levels are always the unrounded S / 324.  That is what F32 frames get
+ * whenever either frame of the pair holds a sample above 255, so for such a
+ * pair the equality with the F32 call is exact on every level.
+ *
+ * A U16 output element is floorf(x + 0.5f) clamped to 0 .. 65535, NaN -> 0, of
+ * the f32 value x that the F32 output holds.  Sampling and blending are
+ * convex, so a 10-bit input never leaves 0 .. 1023 and the calls take no depth
+ * argument.  For P010 the low six bits of an output sample are in general not
+ * zero: the result is a valid P016 frame, and nothing is masked.
+ *
+ * Alpha: a frame scaled by k behaves like alpha divided by k.  Relative to the
+ * 8-bit recommendation of about 100, use alpha x 4 for 10-bit LSB-aligned
+ * content (yuv420p10le) and alpha x 256 for P010. */
+#define HSFLOW_HAS_YUV16 1
+
+/* KIY (cells NULL) or KIYP (cells: KS's, of the luma, 8-byte aligned) on
+ * 16-bit chroma: hsflow_chroma_interp_device's, or with cells
+ * hsflow_chroma_interp_proj_device's, definition on the sample values, layouts
+ * HSFLOW_YUV_I420 and HSFLOW_YUV_NV12 with 2-byte samples; out_c: [batch][nt]
+ * chroma frames of the same layout, dtype_out HSFLOW_U16 or HSFLOW_F32.  The
+ * contract is hsflow_chroma_interp_device's: the planes need element (2-byte;
+ * an F32 output 4-byte) alignment only, out_c is disjoint from every input,
+ * all arguments are checked before any device work, one launch,
+ * stream-ordered, capturable, no allocation. */
+int hsflow_chroma_interp16_device(const uint16_t *c0, const uint16_t *c1, int layout, int rows,
+                                  int cols, int batch, const float *uf, const float *vf,
+                                  const float *ub, const float *vb, const uint64_t *cells,
+                                  const uint32_t *counts_f, const uint32_t *counts_b,
+                                  const hsflow_fallback *fb, const float *times, int nt,
+                                  void *out_c, int dtype_out, void *stream);
+
+/* hsflow_flow_interp_yuv_pj_device on 16-bit frames: the luma through
+ * hsflow_flow_interp_fb_device's path as HSFLOW_U16 frames (prefilter,
+ * smoothness, finest level, init, projection 0 or 1 and fallback included; the
+ * pyramid as stated above), then hsflow_chroma_interp16_device on the flows,
+ * cells and counts left in the workspace.  out_y and out_c: dtype_out
+ * HSFLOW_U16 or HSFLOW_F32.  The workspace is
+ * hsflow_flow_interp_yuv_pj_workspace_bytes: the flows are f32 either way.
+ * Stream-ordered; never allocates or synchronises.  Limitation: do not replay a
+ * captured graph of this call more than once.  A first replay equals the eager
+ * call; later replays of a graph of the fused YUV calls (this one and
+ * hsflow_flow_interp_yuv_device / _pj_device alike) have been observed to differ
+ * from it -- a pair that passes the check judged a cut -- while eager calls on
+ * the same workspace stay right.  hsflow_chroma_interp16_device, one launch, is
+ * not affected. */
+int hsflow_flow_interp_yuv16_device(const uint16_t *y0, const uint16_t *c0, const uint16_t *y1,
+                                    const uint16_t *c1, int layout, int rows, int cols, int batch,
+                                    int levels, int finest, int warps, int median, int window,
+                                    int iters, float alpha, float rel, float abs_thr,
+                                    const float *times, int nt, int projection, void *out_y,
+                                    void *out_c, int dtype_out, uint8_t *flags,
+                                    uint32_t *trusted, uint8_t *cut, const hsflow_prefilter *pf,
+                                    const hsflow_smoothness *sm, const hsflow_flow_init *init,
+                                    const hsflow_fallback *fb, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
+/* The host form, hsflow_flow_interp_yuv_pj's on packed frames of rows * cols *
+ * 3 / 2 16-bit samples (f0, f1 and each out[k]; out of dtype_out HSFLOW_U16 or
+ * HSFLOW_F32).  Prefilter, smoothness, finest level, sequence mode and fallback
+ * of the context are honoured and hsflow_ctx_last_cut is set; the result equals
+ * hsflow_flow_interp_yuv16_device's bit for bit. */
+int hsflow_flow_interp_yuv16(hsflow_ctx *ctx, const uint16_t *f0, const uint16_t *f1, int layout,
+                             int rows, int cols, int levels, int warps, int median, int window,
+                             int iters, double alpha, float rel, float abs_thr,
+                             const float *times, int nt, int projection, void *const *out,
+                             int dtype_out, uint8_t *const *flags, uint32_t *trusted);
 
 /* ---- host utilities on the path to the hot loop ------------------------ */
 

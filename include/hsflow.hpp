@@ -196,6 +196,39 @@ class Context {
                                         HSFLOW_U8, flags ? fl.data() : nullptr, nullptr));
     }
 
+    // The same for packed frames of rows * cols * 3 / 2 16-bit samples each
+    // (yuv420p10le .. p16le: HSFLOW_YUV_I420; P010 .. P016: HSFLOW_YUV_NV12), in
+    // and out (hsflow.h, hsflow_flow_interp_yuv16).  A sample is its value, so
+    // alpha scales with the content: x 4 for 10-bit LSB-aligned samples, x 256
+    // for P010, relative to 8-bit.  projection 0 or 1; -1 stands for 0: the
+    // context's projection setting is not consulted.
+    void getFrameInterpYuv(const uint16_t *prev, const uint16_t *next, int layout, int rows,
+                           int cols, const std::vector<float> &times, int levels, int warps,
+                           int median, int windowSize, int maxIterations, double alpha,
+                           std::vector<std::vector<uint16_t>> &frames,
+                           std::vector<std::vector<uint8_t>> *flags = nullptr,
+                           int projection = -1) {
+        if (!prev || !next) throw Error(HSFLOW_ERR_ARG, "empty image");
+        if (rows < 2 || cols < 2 || rows % 2 || cols % 2)
+            throw Error(HSFLOW_ERR_ARG, "YUV 4:2:0 needs even rows and cols");
+        const size_t n = (size_t)rows * cols;
+        frames.resize(times.size());
+        if (flags) flags->resize(times.size());
+        std::vector<void *> out(times.size());
+        std::vector<uint8_t *> fl(times.size());
+        for (size_t k = 0; k < times.size(); ++k) {
+            frames[k].resize(n / 2 * 3);
+            out[k] = frames[k].data();
+            if (flags) (*flags)[k].resize(n), fl[k] = (*flags)[k].data();
+        }
+        check(hsflow_flow_interp_yuv16(ctx_, prev, next, layout, rows, cols, levels, warps,
+                                       median, windowSize, maxIterations, alpha,
+                                       HSFLOW_CONSISTENCY_REL, HSFLOW_CONSISTENCY_ABS,
+                                       times.data(), (int)times.size(),
+                                       projection < 0 ? 0 : projection, out.data(), HSFLOW_U16,
+                                       flags ? fl.data() : nullptr, nullptr));
+    }
+
   private:
     hsflow_ctx *ctx_ = nullptr;
 };
@@ -414,6 +447,15 @@ class HornSchunck {
     void getFrameInterpYuv(const uint8_t *prev, const uint8_t *next, int layout, int rows,
                            int cols, const std::vector<float> &times, int levels, int warps,
                            int median, std::vector<std::vector<uint8_t>> &frames,
+                           std::vector<std::vector<uint8_t>> *flags = nullptr,
+                           int projection = -1) {
+        ctx().getFrameInterpYuv(prev, next, layout, rows, cols, times, levels, warps, median,
+                                windowSize, maxIterations, alpha, frames, flags, projection);
+    }
+    // ... and for packed frames of 16-bit samples
+    void getFrameInterpYuv(const uint16_t *prev, const uint16_t *next, int layout, int rows,
+                           int cols, const std::vector<float> &times, int levels, int warps,
+                           int median, std::vector<std::vector<uint16_t>> &frames,
                            std::vector<std::vector<uint8_t>> *flags = nullptr,
                            int projection = -1) {
         ctx().getFrameInterpYuv(prev, next, layout, rows, cols, times, levels, warps, median,
